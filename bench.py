@@ -11,6 +11,13 @@ chunk buffers.  Signals are sharded over ranks with no collective on the data
 path (the barrier and a max-reduce of the elapsed time are timing only).
 
     python bench.py [--gpus N --steps K --warmup W] [--config c4|c3|c2|c5] [--engine auto|rocfft|fused]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line of that one workload
+(with the rooflines its own event timings give).  ``--full`` adds what takes runs of its own:
+the extra legs of the default C4 line (``--legs``: fp64, C2, C3, C5) and the CPU baselines.
+``--dump-outputs DIR`` writes, after the timed steps, what the last step left in the output
+buffers to ``DIR/<output kind>.npy`` (dump_outputs).
 
 Multi-GPU: under torchrun (WORLD_SIZE set) every process is one rank.  Without it,
 ``--gpus N`` (N > 1) makes this process a launcher that never touches the GPU: it starts
@@ -261,12 +268,51 @@ def fft_flops_per_row(n: int, kname: str) -> float:
     return 5.0 * n * math.log2(n) + 2.0 * n
 
 
+DUMP_MAX_BYTES = 32 << 20      # --dump-outputs writes at most this much array data
+DUMP_SEED = 20240521
+
+
+def dump_outputs(torch, path, bufs, S, C, F, n):
+    """Write what the last timed step left in the rotating output buffers: chunk i of a step
+    lands in bufs[i % len(bufs)], so the buffers hold the outputs of the step's last len(bufs)
+    chunks (every signal when one chunk covers them).  Those outputs, in signal order, are
+    one (signals, F, n) array; it is written whole when it fits DUMP_MAX_BYTES, else its
+    elements at a fixed (DUMP_SEED), sorted sample of flat indices.  Complex outputs are
+    stored as (..., 2) real pairs in the buffers' precision (float32 / float64)."""
+    starts = list(range(0, S, C))
+    last = [(i, s0, min(C, S - s0)) for i, s0 in enumerate(starts)][-len(bufs):]
+    parts = [bufs[i % len(bufs)][:c] for i, _, c in last]
+    real = [torch.view_as_real(p) if p.is_complex() else p.unsqueeze(-1) for p in parts]
+    width = real[0].shape[-1]
+    esz = real[0].element_size() * width
+    total = sum(c for _, _, c in last) * F * n
+    if total * esz <= DUMP_MAX_BYTES:
+        out = torch.cat([r.cpu() for r in real]).numpy()
+        out = out if width == 2 else out[..., 0]
+    else:
+        k = DUMP_MAX_BYTES // esz
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, size=k))
+        pieces, base = [], 0
+        for r in real:
+            m = r.shape[0] * F * n
+            sel = idx[(idx >= base) & (idx < base + m)] - base
+            pieces.append(r.reshape(m, width)[torch.from_numpy(sel).to(r.device)].cpu())
+            base += m
+        out = torch.cat(pieces).numpy()
+        out = out if width == 2 else out[:, 0]
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.save(path, np.ascontiguousarray(out))
+    log(f'[bench] wrote {path}: {out.shape} {out.dtype} (signals {last[0][1]}..{last[-1][1] + last[-1][2] - 1} '
+        f'of the last step, {"whole" if total * esz <= DUMP_MAX_BYTES else "sampled"})')
+
+
 def run_leg(args, torch, dist, nw, L, world, rank, dev, backend, cfg_name, dtype_override=None, fp64_leg=False,
-            overrides=True):
+            overrides=True, dump_dir=None):
     """One measured workload: warmup, barrier-bracketed timed steps, max over ranks.
     Returns (line fields, plan stats, extra) for rank 0's JSON line.  overrides=False: the
     config as CONFIGS names it (the extra legs of the default line ignore the diagnostic
-    flags; --epochs still scales the multi-epoch legs down, for tests)."""
+    flags; --epochs still scales the multi-epoch legs down, for tests).  dump_dir: where
+    dump_outputs writes this leg's outputs after the timed steps (every rank its own file)."""
     kind, epochs, chans, n, freqs, out_kind, dtype, text = CONFIGS[cfg_name]
     if args.epochs and (overrides or epochs > 1):
         epochs = args.epochs
@@ -339,6 +385,9 @@ def run_leg(args, torch, dist, nw, L, world, rank, dev, backend, cfg_name, dtype
     el = time.perf_counter() - t0
     el = max_over_ranks(torch, dist, el, dev if backend == 'nccl' else None)
     st = plan.stats()
+    if dump_dir:
+        name = out_kind if world == 1 else f'{out_kind}_rank{rank}'
+        dump_outputs(torch, os.path.join(os.path.abspath(dump_dir), name + '.npy'), bufs, S, C, F, n)
     points = float(S) * F_all * n * args.steps * (1 if by_scales else world)
     res = {'value': points / el, 'ms_per_step': el / args.steps * 1e3, 'steps': args.steps, 'warmup': args.warmup,
            'dtype': 'f64' if f64 else 'f32',
@@ -521,12 +570,19 @@ def main(argv=None):
                          'or the scale list of the same signals (strong scaling; the C5 split for '
                          'one long signal, SURVEY §8e); auto = scales for the one-signal config (C5), '
                          'signals otherwise')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: the extra legs of the default C4 '
+                         'line (--legs) and the CPU baselines (a plain run times its one workload only)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the outputs the last step left in the output '
+                         'buffers to DIR/<output kind>.npy (float32 / float64, complex as real pairs, '
+                         'at most 32 MiB: a fixed seeded sample of a larger output)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
     ap.add_argument('--no-fp64', action='store_true',
                     help='skip the fp64 leg (the same workload at the reference\'s complex128 precision, '
                          'reported under the "fp64" key of the default C4 line)')
     ap.add_argument('--legs', default=','.join(LEGS),
-                    help='extra legs of the default C4 line, comma-separated (default: all of '
+                    help='with --full: extra legs of the default C4 line, comma-separated (default: all of '
                          f'{",".join(LEGS)}; "none" for none)')
     ap.add_argument('--backend', default=None, choices=['nccl', 'gloo'],
                     help='process-group backend for N > 1 ranks (default: nccl = RCCL over xGMI; '
@@ -539,6 +595,8 @@ def main(argv=None):
                          'barriers and the max-over-ranks timing on CPU (tests)')
     ap.add_argument('--fail-rank', type=int, default=None, help=argparse.SUPPRESS)   # tests: that rank exits 3
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     bad = [l for l in args.legs.split(',') if l and l != 'none' and l not in LEGS]
     if bad:
         raise SystemExit(f'bench.py: unknown --legs {bad} (choose from {sorted(LEGS)})')
@@ -580,9 +638,10 @@ def main(argv=None):
     dev = torch.device('cuda', local)
     torch.cuda.set_device(dev)
 
-    res, st, extra = run_leg(args, torch, dist, nw, L, world, rank, dev, backend, args.config)
-    # The default (C4) line also carries BASELINE.json's other headline workloads, each measured
-    # in this same run after the previous leg's buffers are freed, with its own roofline:
+    res, st, extra = run_leg(args, torch, dist, nw, L, world, rank, dev, backend, args.config,
+                             dump_dir=args.dump_outputs)
+    # With --full the default (C4) line also carries BASELINE.json's other headline workloads, each
+    # measured in this same run after the previous leg's buffers are freed, with its own roofline:
     #   fp64: C4 at the reference's precision (complex128 out, base.py:399-406);
     #   c2:   Morlet cwt 64 x 16384 x 128 (wavelets.py:132-136);
     #   c3:   Morse power 512 x 64 x 4096 x 256 (the fused |.|^2 path, base.py:409-425);
@@ -591,7 +650,8 @@ def main(argv=None):
     default_line = (args.config == 'c4' and res['dtype'] == 'f32' and not args.dtype and not args.output and
                     not args.samples and not args.wavelet and not args.chunk)
     want = [l for l in args.legs.split(',') if l and l != 'none']
-    legs = [] if not default_line else [l for l in LEGS if l in want and not (args.no_fp64 and l == 'fp64')]
+    legs = [] if not (args.full and default_line) else [
+        l for l in LEGS if l in want and not (args.no_fp64 and l == 'fp64')]
     leg_out = {}
     for leg in legs:
         cfg_name, dt = LEGS[leg]
@@ -608,7 +668,7 @@ def main(argv=None):
 
     if rank == 0:
         cpu = cpu_pool = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log('[bench] cpu baseline ...')
             cpu = cpu_baseline(res['kind'], res['n'], res['freqs'], res['out_kind'])
             for k in ('sample_seconds', 'rows_done'):

@@ -42,9 +42,43 @@ def test_two_ranks_share_the_gpu_with_kernels():
     assert abs(d['value'] - pts / (d['ms_per_step'] * 2e-3)) <= 1e-6 * d['value']
 
 
+def test_plain_run_times_its_one_workload_only():
+    """Without --full the default line carries no extra leg and no CPU baseline, and --steps
+    is the number of timed steps behind ms_per_step."""
+    d, err = run_bench('--config', 'c4', '--epochs', '1', '--steps', '3', '--warmup', '1')
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['dtype'] == 'f32' and d['unit'] == 'points/s'
+    assert d['value'] == pytest.approx(64 * 16384 * 256 / (d['ms_per_step'] * 1e-3), rel=1e-9)
+    assert d['roofline']['kernel'] == 'nw_fused_kernel' and d['higher_is_better'] is True
+    assert d['fp64'] is None and d['cpu_baseline'] is None and d['cpu_baseline_pool'] is None
+    assert not any(k in d for k in ('c2', 'c3', 'c5'))
+    assert err.count('engine=') == 1 and 'cpu baseline' not in err
+
+
+def test_dump_outputs_holds_the_last_steps_outputs(tmp_path):
+    """--dump-outputs: C3 power of 64 signals in chunks of 24 leaves the last step's chunks
+    1 and 2 (signals 24..63) in the two rotating buffers; the file is bench.dump_outputs'
+    seeded sample of them, checked against the oracle on bench's own (seeded) inputs at the
+    C3 tolerance of test_gpu_bench_shapes.py (fp32 power: 2e-5 of max|ref|)."""
+    import numpy as np
+    import torch
+    import bench
+    from oracle import nw_oracle as O
+    d, _ = run_bench('--config', 'c3', '--epochs', '1', '--chunk', '24', '--steps', '2', '--warmup', '0',
+                     '--dump-outputs', str(tmp_path / 'out'))
+    assert d['steps'] == 2 and d['config']['chunk_signals'] == 24
+    got = np.load(tmp_path / 'out' / 'power.npy')
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_MAX_BYTES // 4,) and got.nbytes <= 64e6
+    x = bench.synth_device(torch, 64, 4096, seed=1000, device=torch.device('cuda', 0)).cpu().numpy()
+    freqs = np.arange(1, 257, dtype=np.float64)
+    ref = np.stack([np.abs(O.cwt('morse', x[s].astype(np.float64), freqs)) ** 2 for s in range(24, 64)])
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, ref.size, size=got.size))
+    err = np.max(np.abs(got - ref.reshape(-1)[idx])) / np.max(ref)
+    assert err <= 2e-5, err
+
+
 def test_c4_line_carries_an_fp64_leg():
     d, _ = run_bench('--config', 'c4', '--epochs', '2', '--steps', '1', '--warmup', '1', '--no-cpu-baseline',
-                     '--legs', 'fp64')
+                     '--full', '--legs', 'fp64')
     assert d['dtype'] == 'f32' and d['roofline']['kernel'] == 'nw_fused_kernel'
     assert 'c3' not in d and 'c5' not in d
     f = d['fp64']
@@ -60,7 +94,7 @@ def test_default_line_carries_c3_and_c5_legs():
     """BASELINE.json's C3 (fused |.|^2, base.py:409-425) and C5 (2^24 samples x 512 scales,
     fp32 and fp64, base.py:404-406) ride on the default line with their own rooflines."""
     d, _ = run_bench('--config', 'c4', '--epochs', '2', '--steps', '1', '--warmup', '1', '--no-cpu-baseline',
-                     '--legs', 'c2,c3,c5,c5_fp64', timeout=600)
+                     '--full', '--legs', 'c2,c3,c5,c5_fp64', timeout=600)
     assert d['fp64'] is None
     c2 = d['c2']                                 # Morlet cwt 64 x 16384 x 128 (wavelets.py:132-136)
     assert c2['dtype'] == 'f32' and c2['output'] == 'cwt' and c2['roofline']['kernel'] == 'nw_fused_kernel'
@@ -92,7 +126,8 @@ def test_two_ranks_split_c5_scales_with_kernels():
     §8e), with real two-pass launches on both ranks; value = the whole job's points / the
     slowest rank's time.  C2 rides the same line signal-sharded (weak)."""
     d, err = run_bench('--gpus', '2', '--backend', 'gloo', '--same-device', '--config', 'c4', '--epochs', '1',
-                       '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--legs', 'c2,c5', timeout=600)
+                       '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--full', '--legs', 'c2,c5',
+                       timeout=600)
     assert d['n_gpus'] == 2 and d['scaling'] == 'weak'
     c5 = d['c5']['fp32']
     assert c5['scaling'] == 'strong' and c5['parallelism'].startswith('scales2')

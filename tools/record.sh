@@ -15,7 +15,7 @@ fi
 # name | bench args (bench line) | pmc args | kernel for the PMC summary | summary config json
 record() {
   local name=$1 bargs=$2 pargs=$3 kern=$4 cfgjson=$5
-  timeout -k 10 400 python bench.py $bargs > $R/bench_$name.json 2> $R/bench_$name.log; rc=$?
+  timeout -k 10 400 python bench.py --full $bargs > $R/bench_$name.json 2> $R/bench_$name.log; rc=$?
   cat $R/bench_$name.json; [ $rc -ne 0 ] && { tail -3 $R/bench_$name.log; return $rc; }
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $R/prof_$name -o run --output-format csv -- python3 bench.py $pargs --no-cpu-baseline > $R/prof_$name.log 2>&1; rc=$?
   echo "rocprof $name rc=$rc"; [ $rc -ne 0 ] && { tail -3 $R/prof_$name.log; return $rc; }
