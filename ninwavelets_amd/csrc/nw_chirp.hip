@@ -34,9 +34,26 @@ constexpr int kTileFC = 8;    // scales per XCD tile
 constexpr int kTileGC = 4;    // signal groups per XCD tile
 constexpr int kRegOsz = 16;   // PassInfo without last-pass pairing: j = t + q*T everywhere
 
+// The register-DFT form of one kernel instantiation (nw_dft_reg.h): the fp64 phase-sum kernel
+// at M = 1024 (analytic rows) sits at 251 VGPRs with the DIF form and spills 12 B with the FMA
+// form (tools/regs.py), so it keeps DIF; every other instantiation holds or lowers its scratch
+// with the FMA form (fp64 M = 4096 phase sums 108 -> 52 B and 116 -> 68 B)
+template <typename T, int M, int E, int OUT, bool REALW>
+constexpr bool kChirpDif = sizeof(T) == 8 && M == 1024 && OUT == kOutPhSum && REALW;
+template <bool DIF, typename T, int R, int NZ = R>
+__device__ __forceinline__ void idft_sel(C2<T>* v) {
+    if constexpr (DIF) idft_br_dif<T, R, NZ>(v);
+    else idft_br<T, R, NZ>(v);
+}
+template <bool DIF, typename T, int R, typename W>
+__device__ __forceinline__ void idft_tw_sel(C2<T>* v, const W& w) {
+    if constexpr (DIF) idft_br_tw_dif<T, R>(v, w);
+    else idft_br_tw<T, R>(v, w);
+}
+
 // exchange P-1 -> P and pass P, as passes_from (nw_fft_dev.h) without the stores: the
 // last pass leaves its outputs in registers, v[q*R + i] = output j + bitrev(i)*NS, j = t + q*T
-template <typename T, int N, int E, int P>
+template <typename T, int N, int E, int P, bool DIF = false>
 __device__ __forceinline__ void passes_regs(C2<T>* v, T* lds, int t, const C2<Sc<T>>* __restrict__ tw) {
     using S = Sc<T>;   // T = f2: two signals per lane value, twiddles shared
     using I = PassInfo<N, E, P, kRegOsz>;
@@ -58,16 +75,12 @@ __device__ __forceinline__ void passes_regs(C2<T>* v, T* lds, int t, const C2<Sc
         lds_read<T, N, E, P, 1, kRegOsz>(v, lds, t);
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            if constexpr (TABLED) {
-                const C2<S>* tab = Tab1<T, N, E>::table(lds) + I::bfly(t, q) % I::NS;
-#pragma unroll
-                for (int r = 1; r < R; ++r) v[q * R + r] = cmul(v[q * R + r], tab[(r - 1) * I::NS]);
-            } else {
-                twiddle_apply<T, R>(v + q * R, pb[q]);
-            }
-            idft_br<T, R>(v + q * R);
+            if constexpr (TABLED)
+                idft_tw_sel<DIF, T, R>(v + q * R, TwTable<S, R, I::NS, false>{Tab1<T, N, E>::table(lds) + I::bfly(t, q) % I::NS});
+            else
+                idft_tw_sel<DIF, T, R>(v + q * R, TwPowers<S, R>(pb[q]));
         }
-        passes_regs<T, N, E, P + 1>(v, lds, t, tw);
+        passes_regs<T, N, E, P + 1, DIF>(v, lds, t, tw);
     }
 }
 
@@ -113,6 +126,7 @@ __global__ __launch_bounds__(M / E, (kChirpWps<T, M, E, OUT>)) void nw_chirp_ker
     constexpr int TT = G::T;
     constexpr int LP = G::npass() - 1;
     using IL = PassInfo<M, E, LP, kRegOsz>;
+    constexpr bool DIF = kChirpDif<T, M, E, OUT, REALW>;
     static_assert(PassInfo<M, E, 1, kRegOsz>::R == E, "pass 1 must be radix E (pass-0 layout reads)");
     using O = typename OutT<OUT, T>::type;
     using WT = typename WRow<T, REALW>::type;
@@ -158,13 +172,13 @@ __global__ __launch_bounds__(M / E, (kChirpWps<T, M, E, OUT>)) void nw_chirp_ker
                 }
                 v[r] = C2<T>{a.re, -a.im};
             }
-            idft_br<T, E, NZ>(v);
+            idft_sel<DIF, T, E, NZ>(v);
         };
         if (nz <= 1) pass0.template operator()<1>();
         else if (nz <= 2) pass0.template operator()<2>();
         else if (nz <= 4) pass0.template operator()<4>();
         else pass0.template operator()<E / 2>();
-        passes_regs<T, M, E, 1>(v, lds, t, tw);
+        passes_regs<T, M, E, 1, DIF>(v, lds, t, tw);
         // P[m] = conj(v[m]) * Bh[m]
 #pragma unroll
         for (int q = 0; q < IL::Q; ++q)
@@ -183,8 +197,8 @@ __global__ __launch_bounds__(M / E, (kChirpWps<T, M, E, OUT>)) void nw_chirp_ker
         lds_write<T, M, E, LP, 1>(v, lds, t);
         lds_barrier();
         lds_read<T, M, E, 1, 1, kRegOsz>(v, lds, t);
-        idft_br<T, E>(v);
-        passes_regs<T, M, E, 1>(v, lds, t, tw);
+        idft_sel<DIF, T, E>(v);
+        passes_regs<T, M, E, 1, DIF>(v, lds, t, tw);
         // y[n] = c(n) y'[n] for n < N (|y|, |y|^2: |c(n)| = 1, the chirp is skipped)
         O* orow = reinterpret_cast<O*>(out) + (s * d.nfreq + fi) * (int64_t)n;
         // epoch partial sums (kOutPSum / kOutPhSum): the block's fp64 row (group sg, scale fi)

@@ -1,5 +1,5 @@
 // nw_fft_dev.h — device building blocks of the on-chip inverse FFT engines (gfx950):
-// complex helpers, register radix-2 DIF networks, twiddles (v_sin/v_cos or exact table),
+// the register DFTs (nw_dft_reg.h), their twiddles (v_sin/v_cos or exact table),
 // the padded half-image LDS exchange, Stockham pass geometry, LDS-DMA, DPP transposes
 // and the last-pass store forms.  Included by nw_fused.hip (n <= 16384) and
 // nw_large.hip (the two-pass engine for n up to 2^24); header-only device templates.
@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "nw_dcheck.h"
+#include "nw_dft_reg.h"
 #include "nw_internal.h"
 
 // Tuning constants; each was measured against its alternatives (numbers in DESIGN.md §4).
@@ -32,14 +33,7 @@ namespace nw {
 namespace {
 
 
-template <typename T> struct C2 {
-    T re, im;
-};
-
-// two fp32 lanes of one VGPR pair: C2<f2> is a PAIR of complex numbers (a.re, b.re),
-// (a.im, b.im) on which every DIF / twiddle template runs as packed math
-// (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32: two fp32 operations per instruction)
-typedef float f2 __attribute__((ext_vector_type(2)));
+// pairs of complex numbers <-> their halves (C2<f2>, nw_dft_reg.h)
 __device__ __forceinline__ C2<f2> pk(C2<float> a, C2<float> b) { return {f2{a.re, b.re}, f2{a.im, b.im}}; }
 __device__ __forceinline__ C2<float> lo(C2<f2> p) { return {p.re.x, p.im.x}; }
 __device__ __forceinline__ C2<float> hi(C2<f2> p) { return {p.re.y, p.im.y}; }
@@ -49,20 +43,6 @@ __device__ __forceinline__ double mul_nocontract(double a, double b) {
 #pragma clang fp contract(off)
     return a * b;
 }
-
-template <typename T> __device__ __forceinline__ C2<T> cmul(C2<T> a, C2<T> b) {
-    return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
-}
-// a pair of complex numbers (two signals) times one complex number (a shared twiddle):
-// the scalar operand is splat across both halves of every packed op
-__device__ __forceinline__ C2<f2> cmul(C2<f2> a, C2<float> b) {
-    return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
-}
-
-// scalar type of a lane value: C2<f2> carries two signals' values of one float element
-template <typename T> struct ScalarOf { using type = T; };
-template <> struct ScalarOf<f2> { using type = float; };
-template <typename T> using Sc = typename ScalarOf<T>::type;
 
 // --- memory ops addressed as wave-uniform base (SGPR pair) + 32-bit per-lane byte
 // offset: `global_load/store ... v_off, s[base:base+1]` (saddr form), i.e. one VGPR
@@ -85,85 +65,6 @@ __device__ __forceinline__ const P* at(const P* base, uint32_t lane_off, uint32_
     asm volatile("" : "+v"(lane_off));
     return reinterpret_cast<const P*>(reinterpret_cast<const char*>(base) + (lane_off + c));
 }
-
-// cos(2*pi*i/32), i = 0..31
-__device__ constexpr double kCos32[32] = {
-    1.0, 0.98078528040323043, 0.92387953251128674, 0.83146961230254524, 0.70710678118654757,
-    0.55557023301960218, 0.38268343236508978, 0.19509032201612825, 0.0, -0.19509032201612825,
-    -0.38268343236508978, -0.55557023301960218, -0.70710678118654757, -0.83146961230254524,
-    -0.92387953251128674, -0.98078528040323043, -1.0, -0.98078528040323043, -0.92387953251128674,
-    -0.83146961230254524, -0.70710678118654757, -0.55557023301960218, -0.38268343236508978,
-    -0.19509032201612825, 0.0, 0.19509032201612825, 0.38268343236508978, 0.55557023301960218,
-    0.70710678118654757, 0.83146961230254524, 0.92387953251128674, 0.98078528040323043};
-
-// a * exp(+2 pi i K / LEN) for compile-time K, LEN (LEN | 32); trivial angles special-cased
-template <typename T, int K, int LEN>
-__device__ __forceinline__ C2<T> twc(C2<T> a) {
-    constexpr int idx = K * (32 / LEN);
-    if constexpr (idx == 0) {
-        return a;
-    } else if constexpr (idx == 8) {                  // +i
-        return {-a.im, a.re};
-    } else if constexpr (idx == 4) {                  // (1+i)/sqrt2
-        constexpr T h = (T)0.70710678118654757;
-        return {h * (a.re - a.im), h * (a.re + a.im)};
-    } else if constexpr (idx == 12) {                 // (-1+i)/sqrt2
-        constexpr T h = (T)0.70710678118654757;
-        return {-h * (a.re + a.im), h * (a.re - a.im)};
-    } else {
-        constexpr T c = (T)kCos32[idx];
-        constexpr T s = (T)kCos32[(idx + 24) % 32];   // sin(x) = cos(x - pi/2)
-        return {a.re * c - a.im * s, a.re * s + a.im * c};
-    }
-}
-
-template <int R> __host__ __device__ constexpr int bitrev(int i) {
-    int r = 0;
-    for (int b = 1; b < R; b <<= 1) {
-        r = (r << 1) | (i & 1);
-        i >>= 1;
-    }
-    return r;
-}
-
-// radix-2 DIF butterflies of one stage (half size H), unrolled by template recursion.
-// NZ: only the first NZ elements of every group of 2H are nonzero (pruned inputs): a
-// butterfly whose partner is zero is a copy plus a twiddle, one with both zero is skipped
-// (exact: u + 0 = u), and every group keeps a nonzero prefix of min(NZ, H) after the stage.
-template <typename T, int R, int H, int G, int K, int NZ>
-__device__ __forceinline__ void dif_bfly(C2<T>* a) {
-    if constexpr (G < R) {
-        if constexpr (K < H) {
-            if constexpr (K + H < NZ) {
-                const C2<T> u = a[G + K], w = a[G + K + H];
-                a[G + K] = {u.re + w.re, u.im + w.im};
-                a[G + K + H] = twc<T, K, 2 * H>(C2<T>{u.re - w.re, u.im - w.im});
-            } else if constexpr (K < NZ) {
-                a[G + K + H] = twc<T, K, 2 * H>(a[G + K]);
-            }
-            dif_bfly<T, R, H, G, K + 1, NZ>(a);
-        } else {
-            dif_bfly<T, R, H, G + 2 * H, 0, NZ>(a);
-        }
-    }
-}
-
-template <typename T, int R, int H, int NZ>
-__device__ __forceinline__ void dif_stages(C2<T>* a) {
-    if constexpr (H >= 1) {
-        dif_bfly<T, R, H, 0, 0, NZ>(a);
-        dif_stages<T, R, H / 2, (NZ < H ? NZ : H)>(a);
-    }
-}
-
-// inverse DFT of R registers, natural-order input, bit-reversed output; inputs r >= NZ
-// are zero (their registers must hold zeros)
-template <typename T, int R, int NZ = R>
-__device__ __forceinline__ void idft_br(C2<T>* v) {
-    if constexpr (R > 1) dif_stages<T, R, R / 2, NZ>(v);
-}
-
-template <int R> constexpr int ilog2() { return R <= 1 ? 0 : 1 + ilog2<R / 2>(); }
 
 // v[r] *= w^(r m), w = exp(2 pi i / NSR), r = 1..R-1.  The base powers w^(m 2^k)
 // come from the exact table tw[i] = exp(2 pi i i / N) (L2-resident); every other
@@ -193,18 +94,24 @@ __device__ __forceinline__ void twiddle_bases(C2<T>* p, int m, const C2<T>* __re
         }
     }
 }
+// idft_br of the registers twiddled by the powers of the bases p (nw_dft_reg.h: the twiddles
+// fold into the first DIT stage)
 template <typename T, int R, typename P>
-__device__ __forceinline__ void twiddle_apply(C2<T>* v, const C2<P>* p) {
-    constexpr int LR = ilog2<R>();
-#pragma unroll
-    for (int r = 1; r < R; ++r) {
-        C2<P> w = p[__builtin_ctz(r)];
-#pragma unroll
-        for (int k = __builtin_ctz(r) + 1; k < LR; ++k)
-            if (r & (1 << k)) w = cmul(w, p[k]);
-        v[r] = cmul(v[r], w);
-    }
+__device__ __forceinline__ void twiddle_dft(C2<T>* v, const C2<P>* p) {
+    idft_br_tw<T, R>(v, TwPowers<P, R>(p));
 }
+// ... and by one butterfly's column of the pass-1 table (Tab1: power r at tab[(r - 1) * NS]).
+// FENCE: at most about 8 table twiddles in flight (more of them live cost registers)
+template <typename S, int R, int NS, bool FENCE> struct TwTable {
+    using scalar = S;
+    const C2<S>* tab;
+    __device__ __forceinline__ C2<S> lo(int r) const { return tab[(r - 1) * NS]; }
+    __device__ __forceinline__ C2<S> hi(int r) const {
+        const C2<S> w = tab[(r + R / 2 - 1) * NS];
+        if (FENCE && r % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+        return w;
+    }
+};
 
 // Padded LDS half image (one real component at a time): 2 extra slots after every
 // kPadG<E> slots (E = elements per thread; 32 slots for E = 16, E otherwise).  Pairs
@@ -825,20 +732,13 @@ __device__ __forceinline__ void passes_from(C2<T>* v, T* lds, int t, const C2<Sc
         NW_STAMP(st, 2 * P - 1);               // exchange P-1 -> P
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-#ifndef NW_ABL_NOTWIDDLE
-            if constexpr (TABLED) {
-                const C2<S>* tab = Tab1<T, N, E>::table(lds) + I::bfly(t, q) % I::NS;
-#pragma unroll
-                for (int r = 1; r < R; ++r) {
-                    v[q * R + r] = cmul(v[q * R + r], tab[(r - 1) * I::NS]);
-                    if (r % 8 == 7) __builtin_amdgcn_sched_barrier(0);   // <= 8 twiddles in flight
-                }
-            } else if constexpr (!(std::is_same<T, float>::value && Q % 2 == 0)) {
-                twiddle_apply<T, R>(v + q * R, pb[q]);
-            }
+#ifdef NW_ABL_NOTWIDDLE
+            constexpr bool TWIDDLED = false;
+#else
+            constexpr bool TWIDDLED = true;
 #endif
-            if constexpr (std::is_same<T, float>::value && Q % 2 == 0) {
-                // butterflies q, q+1 as one packed pair: identical DIF networks, per-butterfly
+            if constexpr (std::is_same<T, float>::value && Q % 2 == 0 && !(TWIDDLED && TABLED)) {
+                // butterflies q, q+1 as one packed pair: identical networks, per-butterfly
                 // twiddles packed side by side
                 if (q % 2 == 0) {
                     C2<f2> pv[R];
@@ -846,22 +746,25 @@ __device__ __forceinline__ void passes_from(C2<T>* v, T* lds, int t, const C2<Sc
                     for (int i = 0; i < R; ++i)
                         pv[i] = pk(reinterpret_cast<C2<float>*>(v)[q * R + i],
                                    reinterpret_cast<C2<float>*>(v)[(q + 1) * R + i]);
-#ifndef NW_ABL_NOTWIDDLE
-                    if constexpr (!TABLED) {
+                    if constexpr (TWIDDLED) {
                         C2<f2> pp[LR > 0 ? LR : 1];
 #pragma unroll
                         for (int k = 0; k < LR; ++k)
                             pp[k] = pk(reinterpret_cast<C2<float>*>(pb[q])[k], reinterpret_cast<C2<float>*>(pb[q + 1])[k]);
-                        twiddle_apply<f2, R>(pv, pp);
+                        twiddle_dft<f2, R>(pv, pp);
+                    } else {
+                        idft_br<f2, R>(pv);
                     }
-#endif
-                    idft_br<f2, R>(pv);
 #pragma unroll
                     for (int i = 0; i < R; ++i) {
                         reinterpret_cast<C2<float>*>(v)[q * R + i] = lo(pv[i]);
                         reinterpret_cast<C2<float>*>(v)[(q + 1) * R + i] = hi(pv[i]);
                     }
                 }
+            } else if constexpr (TWIDDLED && TABLED) {
+                idft_br_tw<T, R>(v + q * R, TwTable<S, R, I::NS, true>{Tab1<T, N, E>::table(lds) + I::bfly(t, q) % I::NS});
+            } else if constexpr (TWIDDLED) {
+                twiddle_dft<T, R>(v + q * R, pb[q]);
             } else {
                 idft_br<T, R>(v + q * R);
             }

@@ -40,6 +40,9 @@
 // hits, the row pass loses its Xt reuse across the scales of a tile.
 #include <cstdlib>
 
+// fp64 register DFTs of this file keep the DIF form (nw_dft_reg.h: the 256-VGPR row kernels
+// gain scratch with the FMA form)
+#define NW_DFT_DIF_F64 1
 #include "nw_fft_dev.h"
 
 namespace nw {
@@ -818,8 +821,7 @@ __device__ __forceinline__ void col_passes(C2<T>* v, T* lds, int u, int c, void*
         for (int q = 0; q < Q; ++q) {
             C2<T> pb[LR > 0 ? LR : 1];
             twiddle_bases<T, R, N1, NS * R>(pb, (u + q * U) % NS, tw1);
-            twiddle_apply<T, R>(v + q * R, pb);
-            idft_br<T, R>(v + q * R);
+            twiddle_dft<T, R>(v + q * R, pb);
         }
     }
     if constexpr (P + 1 < G::npass()) {
@@ -999,8 +1001,7 @@ __device__ __forceinline__ void colp_passes(C2<f2>* v, f2* lds, int u, int cp, v
         for (int q = 0; q < Q; ++q) {
             C2<float> pb[LR > 0 ? LR : 1];                  // shared by the two columns
             twiddle_bases<float, R, N1, NS * R>(pb, (u + q * U) % NS, nullptr);
-            twiddle_apply<f2, R>(v + q * R, pb);
-            idft_br<f2, R>(v + q * R);
+            twiddle_dft<f2, R>(v + q * R, pb);
         }
     }
     if constexpr (P + 1 < G::npass()) {
