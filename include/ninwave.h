@@ -66,9 +66,12 @@ extern "C" {
 #define NW_TIMING_CHAIN  0x800u/* with NW_TIMING: the plan's stream carries nothing but this plan's
                                   executes between two nw_plan_sync / nw_plan_stats calls (a
                                   dedicated benchmark stream), so each stage -- the first of an
-                                  execute too -- starts at the previous stage's end event and no
-                                  event marker enters the stream (the stop events ride on the
-                                  kernel dispatches themselves)                                 */
+                                  execute too -- starts at the previous stage's end event.  No
+                                  event marker enters the stream around kernel-only stages (their
+                                  stop events ride on the kernel dispatches themselves); rocFFT
+                                  and memcpy stages still record their end events.  The first
+                                  stage of an execute includes any idle gap since the previous
+                                  execute                                                       */
 #define NW_NO_CHIRP      0x400u/* auto engine: keep the rocFFT engine for lengths the chirp-z fused
                                   form would take (non-power-of-two n, 2n-1 <= 16384 fp32 /
                                   8192 fp64, and n < 1024; up to n < 16384 / 8192 when every

@@ -1,6 +1,8 @@
 // nw_host.cpp — host-only logic of the C ABI (see nw_host.h); no HIP calls.
 #include "nw_host.h"
 
+#include "../../include/ninwave.h"
+
 #include <sys/mman.h>
 
 #include <algorithm>
@@ -180,6 +182,43 @@ bool morse_may_overflow(double b, double r, double delta, int64_t len_valid, con
     if (fmin == 0.0 || len_valid < 2 || b <= 0.0) return false;
     const double xmax = (double)(len_valid - 1) * delta / fmin;
     return xmax > 1.0 && b * std::log2(xmax) >= 1000.0;
+}
+
+StockParams stock_params(int kind, const double* params, int nparams) {
+    StockParams s{};
+    if (kind == NW_MORSE) {
+        s.b = nparams > 0 ? params[0] : 17.5;
+        s.r = nparams > 1 ? params[1] : 3.0;
+        s.b_over_r = s.b / s.r;
+    } else if (kind == NW_MORLET) {
+        s.sigma = nparams > 0 ? params[0] : 7.0;
+        const bool gabor = nparams > 1 && params[1] != 0.0;
+        const double s2 = s.sigma * s.sigma;
+        const double c = nparams > 2 ? params[2] : std::pow(1.0 + std::exp(-s2) - 2.0 * std::exp(-3.0 / 4.0 * s2), -0.5);
+        s.cpi = c * std::pow(M_PI, -0.25);
+        s.kappa = nparams > 3 ? params[3] : (gabor ? 0.0 : std::exp(-std::pow(s.sigma, 2.0) / 2.0));
+    } else if (kind == NW_MEXICAN_HAT) {
+        s.sigma = nparams > 0 ? params[0] : 7.0;
+    }
+    return s;
+}
+
+double morlet_peak(double sigma, double freq) { return sigma / (1.0 - std::exp(-sigma * freq)); }
+
+RowViewLayout row_view_layout(int U, size_t map_len, size_t table_row_bytes) {
+    const size_t u = (size_t)U;
+    auto up = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
+    RowViewLayout l{};
+    l.idx = 0;
+    l.offs = up(u * 4, 16);
+    l.order = l.offs + up((u + 1) * 4, 16);
+    l.freq = l.order + up(map_len * 4, 16);
+    l.peak = l.freq + up(u * 8, 16);
+    l.xstep = l.peak + up(u * 8, 16);
+    l.row_len = l.xstep + up(u * 4, 16);
+    l.table = up(l.row_len + u * 8, 256);
+    l.bytes = l.table + u * table_row_bytes;
+    return l;
 }
 
 size_t advise_output(char* dst, size_t bytes) {

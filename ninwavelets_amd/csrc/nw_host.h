@@ -68,5 +68,25 @@ size_t advise_output(char* dst, size_t bytes);
 // overflow-checked forms, which reproduce the reference's inf / NaN (wavelets.py:65-74)
 bool morse_may_overflow(double b, double r, double delta, int64_t len_valid, const double* freqs, int nfreq);
 
+// Parameters of the stock analytic wavelets from a caller's params[nparams], defaults filled in:
+// Morse (b, r) = (17.5, 3) (wavelets.py:65-74); Morlet (sigma, gabor, c, k) with c and k from
+// sigma unless given, k = 0 for Gabor (wavelets.py:118-136), cpi = c * pi^(-1/4); MexicanHat
+// (sigma).  Fields of other kinds are 0.
+struct StockParams {
+    double b, r, b_over_r;
+    double sigma, cpi, kappa;
+};
+StockParams stock_params(int kind, const double* params, int nparams);
+// Morlet p(f) = sigma / (1 - exp(-sigma f))
+double morlet_peak(double sigma, double freq);
+
+// Byte layout of a row view (nw_api.cpp, RowView): the indices of its U rows, the scatter map
+// (offs[U + 1], order[map_len]) and the gathered per-row arrays, then the U table rows of
+// table_row_bytes each (0: no table).  Sections start on 16 B, the table rows on 256 B.
+struct RowViewLayout {
+    size_t idx, offs, order, freq, peak, xstep, row_len, table, bytes;
+};
+RowViewLayout row_view_layout(int U, size_t map_len, size_t table_row_bytes);
+
 }  // namespace host
 }  // namespace nw

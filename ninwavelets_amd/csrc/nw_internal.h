@@ -49,7 +49,7 @@ struct WDesc {
 
 template <typename T> struct cplx { T re, im; };
 
-// Timed launches (NW_TIMING): staged() (nw_api.cpp) hands the two events of a stage to the
+// Timed launches (NW_TIMING): run_stage() (nw_api.cpp) hands the two events of a stage to the
 // kernel launches the stage makes through nw_launch -- the first launch takes the start event,
 // every launch the stop event -- and hipExtLaunchKernel stamps them with the dispatch's own
 // begin / end (no marker packets between the kernels: recorded with hipEventRecord, the two

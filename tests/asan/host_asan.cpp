@@ -1,8 +1,9 @@
 // CPU driver for the sanitizer build of the engine's host-only logic (nw_host.cpp):
 // built with -fsanitize=address,undefined by tests/test_host_asan.py.
 //   host_asan self      : invariant checks of group_rows / block_of / parallel_copy / advise_output /
-//                         normal_rows
+//                         normal_rows / row_view_layout / stock_params
 //   host_asan grid      : stdin "real_length sfreq interpolate" -> "len_valid len_full delta"
+#include <cmath>
 #include <cstdio>
 #include <functional>
 #include <cstdlib>
@@ -11,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/ninwave.h"
 #include "../../ninwavelets_amd/csrc/nw_host.h"
 
 using namespace nw::host;
@@ -140,6 +142,49 @@ static void self_checks() {
         const double tiny[3] = {7.0, 10.0, 0.01};
         CHECK(!normal_rows(mh == 1, tiny + (mh ? 0 : 1), mh ? 3 : 2, fr.data(), (int)fr.size(), rows, &lmax, &total,
                            &sigma));
+    }
+    // row_view_layout: the sections ascend without overlap, aligned (16 B, table rows 256 B),
+    // and end at the returned total
+    for (int U = 0; U <= 40; ++U)
+        for (size_t map_len : {size_t(0), size_t(1), size_t(U), size_t(2 * U + 3), size_t(1000)})
+            for (size_t trow : {size_t(0), size_t(16), size_t(40), size_t(4096)}) {
+                const RowViewLayout l = row_view_layout(U, map_len, trow);
+                const size_t u = (size_t)U;
+                const size_t start[] = {l.idx, l.offs, l.order, l.freq, l.peak, l.xstep, l.row_len, l.table};
+                const size_t size[] = {u * 4, (u + 1) * 4, map_len * 4, u * 8, u * 8, u * 4, u * 8, u * trow};
+                CHECK(l.idx == 0);
+                for (int s = 0; s < 8; ++s) {
+                    CHECK(start[s] % (s == 7 ? 256 : 16) == 0);
+                    const size_t next = s < 7 ? start[s + 1] : l.bytes;
+                    CHECK(start[s] + size[s] <= next);
+                }
+                CHECK(l.table + u * trow == l.bytes);
+            }
+    // stock_params against the formulas written out (wavelets.py:65-74, 118-136)
+    {
+        const StockParams m0 = stock_params(NW_MORSE, nullptr, 0);
+        CHECK(m0.b == 17.5 && m0.r == 3.0 && m0.b_over_r == 17.5 / 3.0);
+        CHECK(m0.sigma == 0.0 && m0.cpi == 0.0 && m0.kappa == 0.0);
+        const double mp[2] = {4.0, 0.7};
+        const StockParams m1 = stock_params(NW_MORSE, mp, 2);
+        CHECK(m1.b == 4.0 && m1.r == 0.7 && m1.b_over_r == 4.0 / 0.7);
+        const double quarter = std::pow(M_PI, -0.25);
+        auto c_of = [](double s) { return std::pow(1.0 + std::exp(-s * s) - 2.0 * std::exp(-3.0 / 4.0 * (s * s)), -0.5); };
+        const StockParams l0 = stock_params(NW_MORLET, nullptr, 0);
+        CHECK(l0.sigma == 7.0 && l0.cpi == c_of(7.0) * quarter && l0.kappa == std::exp(-std::pow(7.0, 2.0) / 2.0));
+        CHECK(l0.b == 0.0 && l0.r == 0.0 && l0.b_over_r == 0.0);
+        for (int gabor = 0; gabor < 2; ++gabor) {
+            const double lp[4] = {5.5, (double)gabor, 1.25, 0.125};
+            const StockParams l2 = stock_params(NW_MORLET, lp, 2);   // c and k from sigma
+            CHECK(l2.sigma == 5.5 && l2.cpi == c_of(5.5) * quarter);
+            CHECK(l2.kappa == (gabor ? 0.0 : std::exp(-std::pow(5.5, 2.0) / 2.0)));
+            const StockParams l4 = stock_params(NW_MORLET, lp, 4);   // every parameter given
+            CHECK(l4.sigma == 5.5 && l4.cpi == 1.25 * quarter && l4.kappa == 0.125);
+        }
+        const double hp[1] = {3.0};
+        CHECK(stock_params(NW_MEXICAN_HAT, nullptr, 0).sigma == 7.0 && stock_params(NW_MEXICAN_HAT, hp, 1).sigma == 3.0);
+        CHECK(stock_params(NW_SHANNON, nullptr, 0).sigma == 0.0 && stock_params(NW_HAAR, hp, 1).sigma == 0.0);
+        CHECK(morlet_peak(7.0, 2.0) == 7.0 / (1.0 - std::exp(-7.0 * 2.0)));
     }
 }
 

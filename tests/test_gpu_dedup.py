@@ -142,6 +142,23 @@ def test_table_rows_repeat_by_content():
     np.testing.assert_array_equal(outs[0][0], outs[1][0])
 
 
+@pytest.mark.parametrize('bad', [lambda n: [n + 1, n, n], lambda n: [n, -1, n]])
+def test_rejected_set_wavelet_keeps_the_previous_table(bad):
+    """A set_wavelet refused for its row_len leaves the attached table as it was: the next
+    execute gives the same bits."""
+    n, F = 1024, 3
+    rng = np.random.default_rng(6)
+    table = rng.standard_normal((F, n)) + 1j * rng.standard_normal((F, n))
+    g = L.nw_grid(1.0, n, n)
+    x = synth(2, n, 38)
+    p = nw.Plan(n, F, 'float32', max_batch=2)
+    p.set_wavelet('table', [], np.arange(1., F + 1), g, table=table)
+    a = p.execute(x, out_kind='cwt').copy()
+    with pytest.raises(ValueError, match='row_len out of range'):   # NW_E_INVALID (_lib.check)
+        p.set_wavelet('table', [], np.arange(1., F + 1), g, table=2 * table, row_len=bad(n))
+    assert p.execute(x, out_kind='cwt').tobytes() == a.tobytes()
+
+
 def test_device_tensor_output_with_repeated_rows():
     torch = pytest.importorskip('torch')
     n, F, S = 16384, 16, 4
