@@ -7,8 +7,9 @@ a frequency list picked so the rows run every pass-0 variant (pruned idft_br<T, 
 kernel instantiates.  Which variant a row runs follows from its support: the last bin above
 kTailRel x the row's max |W| (nw_internal.h), rounded as wsupport_kernel / pass0_variant
 (nw_fused.hip) round it.  nw_plan_row_support serves the two-pass engine's plans only (it fails
-on a one-pass plan), so the supports here are read off the plan's own W rows with that rule;
-the set of variants hit must equal the instantiated set -- a miss fails, it is not skipped.
+on a one-pass plan), so the supports here are read off the plan's own W rows with that rule
+(tests/fused_variants.py, shared with the table rows' test); the set of variants hit must equal
+the instantiated set -- a miss fails, it is not skipped.
 
 Other forms: one chirp-z length (n = 1201) and the smallest two-pass length (n = 2^15, 4
 scales; its rows' supports through nw_plan_row_support).
@@ -18,6 +19,7 @@ oracle.nw_oracle, for cwt and power alike."""
 import numpy as np
 import pytest
 
+from fused_variants import instantiated_variants, row_wnz, variant_of
 from oracle import nw_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -29,47 +31,7 @@ TOL = {'float64': 1e-12, 'float32': 1e-5}
 SFREQ = 1000.
 S = 3
 KINDS = {'morse': (nw.Morse, {}), 'morlet': (nw.Morlet, {})}
-TAIL_REL = {'float64': 2.0 ** -72, 'float32': 2.0 ** -56}      # kTailRel (nw_internal.h)
 CANDIDATES = np.geomspace(0.6, 480.0, 160)
-
-
-def elems_per_thread(n):
-    """E of the fused kernels (nw_fused.hip, NW_FUSED_SIZES): 16 up to n = 4096, 32 above."""
-    return 16 if n <= 4096 else 32
-
-
-def instantiated_variants(n, dtype, out, pair):
-    """The pass-0 variants NZ of the kernel that runs (n, dtype, out): pass0_variant
-    (nw_fused.hip) for the single-signal kernel, the pair kernel's own ladder."""
-    e = elems_per_thread(n)
-    if pair:
-        return {4, 8, 12, e}
-    v = {4, 8, e}
-    if e > 16:
-        v |= {16, 24}
-        if dtype == 'float32' or out == 'cwt':
-            v |= {12, 20}
-    return v
-
-
-def row_wnz(row, n, dtype):
-    """wnz of one W row as wsupport_kernel builds it: pass-0 elements reaching the support,
-    rounded up to 1, 2, 4, 8, then to a multiple of 4, capped at E."""
-    e = elems_per_thread(n)
-    mag = np.abs(np.asarray(row))
-    mag = np.where(np.isfinite(mag), mag, 0.0)
-    above = np.nonzero(mag > TAIL_REL[dtype] * mag.max())[0]
-    need = 1 if above.size == 0 else int(above[-1]) // (n // e) + 1
-    p2 = 1
-    while p2 < need and p2 < 8:
-        p2 *= 2
-    if p2 < need:
-        p2 = (need + 3) // 4 * 4
-    return min(p2, e), need
-
-
-def variant_of(wnz, variants):
-    return min(v for v in variants if v >= max(wnz, 4))
 
 
 _picked = {}
