@@ -21,7 +21,8 @@
 //                per 1024-thread workgroup, C * 2e B contiguous per k1 read), epilogue y / |y|
 //                / |y|^2 stored to out[f][n2 + N2 n1] (256-B contiguous runs at N1 = 1024)
 //
-// fp64: E = 32 rows (16 for table rows), 32 elements per thread in the column pass, the
+// fp64: rows of E = 32 at N2 >= 8192 and 16 below, as fp32 (its complex table rows: always
+// 16), 32 elements per thread in the column pass, the
 // column twiddles from two exact split tables and a per-thread recurrence, Morse rows in
 // the log domain (RowW<double>).
 //
@@ -69,7 +70,7 @@ template <typename T> constexpr int kColThreads = sizeof(T) == 8 ? 512 : 1024;
 // profiles/r04_c5_fchunk.txt)
 constexpr size_t kBBudget = size_t(8) << 30;
 
-// N2 (on-chip rows) and its elements per thread E: the nw_fused sizes (fp64: E = 16, N2 <= 8192)
+// N2 (on-chip rows) and its elements per thread E, both dtypes: 32 from N2 = 8192 up, 16 below
 template <typename T, int N2> constexpr int kRowE = N2 >= 8192 ? 32 : 16;
 // complex table rows (wavelet_bin loads) spill at fp64 E = 32: E = 16 there
 template <typename T, int N2> constexpr int kRowETab = sizeof(T) == 8 ? 16 : kRowE<T, N2>;
@@ -1150,7 +1151,7 @@ hipError_t launch_cols(int out_kind, int f0, int nf, const C2<T>* B, void* out, 
     return hipGetLastError();
 }
 
-// n = N1 * N2: N2 = min(n / 32, 16384 (fp32) or 8192 (fp64)), N1 = n / N2 >= 32
+// n = N1 * N2: N2 = min(n / 32, 16384) in both dtypes (kMaxN2), N1 = n / N2 >= 32
 struct Split {
     int n1, n2;
 };

@@ -125,8 +125,9 @@ def test_large_support_pruning_edges():
 @pytest.mark.parametrize('n', [1 << 15, 1 << 16, 1 << 18, 1 << 19, 1 << 21])
 @pytest.mark.parametrize('kind', ['morse', 'morlet', 'shannon'])
 def test_large_fp64_against_oracle(kind, n):
-    """The fp64 two-pass form (N2 <= 8192 on chip, N1 = 32 .. 256 here; pass-0 column
-    twiddles from two exact tables) for the analytic kinds at the default compute dtype."""
+    """The fp64 two-pass form (the fp32 split: N2 <= 16384 on chip, 2^19 is 32 x 16384; N1 = 32
+    .. 128 here; pass-0 column twiddles from two exact tables) for the analytic kinds at the
+    default compute dtype."""
     x = synth(1, n, seed=n % 997 + len(kind))[0].astype(np.float64)
     freqs = np.array([0.5, 3.0, 17.0, 60.0, 250.0, 400.0])
     w = CLASSES[kind](1000)

@@ -368,3 +368,31 @@ def test_pool_advice_skipped_without_the_symbol(monkeypatch):
         pass
     monkeypatch.setattr(engine.L, 'lib', lambda: OldLib())
     engine.HostPool._nw_advise(np.empty(16))                   # no AttributeError
+
+
+def test_large_variants_helper_restates_the_two_pass_dispatch():
+    """tests/large_variants.py against nw_large.hip: the splits at both ends and at the switch
+    from growing N2 to growing N1, and the three pass-0 ladders."""
+    import large_variants as V
+    assert V.split(1 << 15) == (32, 1024)
+    assert V.split(1 << 19) == (32, 16384)
+    assert V.split(1 << 20) == (64, 16384)
+    assert V.split(1 << 24) == (1024, 16384)
+    for dtype in ('float32', 'float64'):
+        for table in (False, True):
+            assert V.ladder(16, dtype, table) == {4, 8, 16}
+    assert V.ladder(32, 'float32', False) == {4, 8, 12, 16, 20, 24, 32}
+    assert V.ladder(32, 'float64', False) == V.ladder(32, 'float32', True) == {4, 8, 16, 24, 32}
+    assert [V.row_elems(n2, 'float64', True) for n2 in (1024, 8192, 16384)] == [16, 16, 16]
+    assert [V.row_elems(n2, 'float32', True) for n2 in (4096, 8192)] == [16, 32]
+    assert [V.row_elems(n2, 'float64', False) for n2 in (4096, 8192, 16384)] == [16, 32, 32]
+    # need_of: one element past the support's last bin, never below 1; the step inside a group
+    t = 16384 // 32
+    assert V.need(5, 7, 32, t) == 1 and V.need(0, 0, 32, t) == 1
+    km = 16 * 32 * t + 1
+    assert [V.need(km, k1, 32, t) for k1 in range(4)] == [17, 17, 16, 16]
+    assert V.variant(17, V.ladder(32, 'float32', False)) == 20 and V.variant(17, V.ladder(32, 'float64', False)) == 24
+    assert V.row_group(7) == 1 and V.row_group(8) == 4
+    assert V.from_lds(32, 'float32', False, 16) and not V.from_lds(32, 'float32', False, 20)
+    assert not V.from_lds(32, 'float64', False, 4) and not V.from_lds(32, 'float32', True, 4)
+    assert not V.from_lds(16, 'float32', False, 4)
