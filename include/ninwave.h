@@ -142,6 +142,7 @@ typedef struct nw_stats {
 #define NW_K_CHIRP       3   /* nw_chirp_kernel (chirp-z form)                               */
 #define NW_K_TWO_PASS    4   /* rows_kernel + cols_kernel (n > 16384; cols writes the output) */
 #define NW_K_MULTIPLY    5   /* k1_multiply + rocFFT inverse (+ k2_epilogue): rocFFT engine   */
+#define NW_K_FUSED_DECIM 6   /* nw_fused_decim_kernel (one pass, decimated rows)             */
 
 typedef struct nw_plan nw_plan;
 
@@ -169,6 +170,12 @@ int nw_trans_grid(double real_length, double sfreq, int interpolate, nw_grid* gr
  * FFTs of W*X, then column FFTs + epilogue); fp32 and fp64 alike. */
 int nw_fused_supported(int64_t n, int dtype);
 
+/* Host-only (no GPU): whether a plan of (n, dtype) can decimate its output rows by decim on
+ * the device (nw_plan_set_decim): power-of-two n with 2048 <= n <= 16384, power-of-two
+ * decim >= 2 with n / decim >= 1024, fp32 or fp64.  The reference's decim is the one
+ * MorseMNE.cwt passes through to MNE (wavelets.py:170-191). */
+int nw_decim_supported(int64_t n, int dtype, int decim);
+
 /* Create a plan for signals of n samples, up to max_batch signals per device
  * chunk, nfreq scales.  flags: NW_INTERPOLATE | NW_ENGINE_* | NW_TIMING. */
 int nw_plan_create(nw_plan** plan, int device, int64_t n, int64_t max_batch,
@@ -188,6 +195,15 @@ int nw_plan_create(nw_plan** plan, int device, int64_t n, int64_t max_batch,
 int nw_plan_set_wavelet(nw_plan* plan, int kind, const double* params, int nparams,
                         const double* freqs, const nw_grid* grid, const void* table,
                         const int64_t* row_len);
+
+/* Time decimation (the decim of MorseMNE.cwt, wavelets.py:170-191): every output row of the
+ * plan holds the n / decim samples y[0], y[decim], y[2 decim], ... of the full row, computed as
+ * the (n / decim)-point inverse transform of the folded product (exact; nw_fused_decim_kernel),
+ * so outputs are (nsig, nfreq, n / decim), or (nfreq, n / decim) for the reduction kinds.  The
+ * wavelet is still attached for the full length n.  Call it before the first nw_execute
+ * (NW_E_STATE afterwards); decim = 1 is a no-op; NW_E_INVALID where nw_decim_supported is 0 or
+ * the plan runs the rocFFT engine.  Plans of one nw_execute_multi* call must share decim. */
+int nw_plan_set_decim(nw_plan* plan, int decim);
 
 /* Shape of the attached wavelet's cached rows: len_full (the table width; for the
  * device-built NW_MEXICAN_HAT / NW_HAAR tables the longest row) and, if row_len is not

@@ -41,7 +41,7 @@ NW_OUT_POWER_MEAN, NW_OUT_ITC, NW_OUT_POWER_SUM, NW_OUT_PHASE_SUM = 3, 4, 5, 6
 NW_MEM_HOST, NW_MEM_DEVICE = 0, 1
 # nw_stats.kernel -> the kernel name rocprofv3 shows
 KERNEL_NAMES = {0: None, 1: 'nw_fused_kernel', 2: 'nw_fused_pair_kernel', 3: 'nw_chirp_kernel',
-                4: 'cols_kernel', 5: 'k1_multiply'}
+                4: 'cols_kernel', 5: 'k1_multiply', 6: 'nw_fused_decim_kernel'}
 NW_BL = {'mean': 0, 'ratio': 1, 'percent': 2, 'log': 3, 'zscore': 4, 'zlog': 5}
 
 
@@ -76,6 +76,8 @@ SIGNATURES = [
     ('nw_device_count', ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     ('nw_trans_grid', ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.POINTER(nw_grid)]),
     ('nw_fused_supported', ctypes.c_int, [_I64, ctypes.c_int]),
+    ('nw_decim_supported', ctypes.c_int, [_I64, ctypes.c_int, ctypes.c_int]),
+    ('nw_plan_set_decim', ctypes.c_int, [_P, ctypes.c_int]),
     ('nw_plan_create', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _I64, _I64, ctypes.c_int32,
                                       ctypes.c_int, ctypes.c_uint32]),
     ('nw_plan_set_wavelet', ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
@@ -172,3 +174,9 @@ def trans_grid(real_length: float, sfreq: float, interpolate: bool) -> nw_grid:
 
 def fused_supported(n: int, dtype: int) -> bool:
     return bool(lib().nw_fused_supported(int(n), int(dtype)))
+
+
+def decim_supported(n: int, dtype: int, decim: int) -> bool:
+    """Whether a plan of (n, dtype) decimates by ``decim`` on the device (nw_decim_supported;
+    host-only, no GPU needed)."""
+    return bool(lib().nw_decim_supported(int(n), int(dtype), int(decim)))

@@ -26,7 +26,7 @@ import numpy as np
 from scipy.fftpack import fft, ifft
 
 from . import _lib as L
-from .engine import REDUCTIONS, Plan, execute_multi, np_dtype
+from .engine import REDUCTIONS, Plan, check_decim, execute_multi, np_dtype
 from .engine import make_wavelets as _make_wavelets_dev
 
 # Device working-set budget per plan chunk (bytes); signals are streamed through it.
@@ -282,8 +282,8 @@ class WaveletBase:
 
     # ------------------------------------------------------------------ execution
     def _plan(self, n: int, nsig: int, device: int, scales: tuple[int, int] | None = None,
-              slot: int = 0) -> Plan:
-        """The cached plan for (n, batch, device) -- of the scale slice [f0, f1) when
+              slot: int = 0, decim: int = 1) -> Plan:
+        """The cached plan for (n, batch, device, decim) -- of the scale slice [f0, f1) when
         ``scales`` is given (scale-sharded multi-device calls).  ``slot`` is the shard
         index of a multi-device call: a plan is not reentrant, so ``devices=[0, 0]`` gets
         one plan per shard, never one plan driven from two host threads."""
@@ -297,10 +297,10 @@ class WaveletBase:
         while batch < min(nsig, cap):
             batch *= 2
         batch = min(batch, cap)
-        key = (n, nf, self.dtype.str, bool(self.interpolate), device, batch, self.engine, f0, slot)
+        key = (n, nf, self.dtype.str, bool(self.interpolate), device, batch, self.engine, f0, slot, decim)
         plan = self._plans.get(key)
         if plan is None:
-            plan = Plan(n, nf, self.dtype, device, batch, self.interpolate, self.engine)
+            plan = Plan(n, nf, self.dtype, device, batch, self.interpolate, self.engine, decim=decim)
             self._plans[key] = plan
         self._plans.move_to_end(key)
         if plan.wavelet_token != c.version:
@@ -324,17 +324,27 @@ class WaveletBase:
             total -= sizes[k]
             p.close()
 
-    def _run(self, x: np.ndarray, out_kind: str) -> np.ndarray:
-        """x: (..., n) signals -> (..., F, n) on the device(s); the plan cache is trimmed
-        to ``plan_cache_bytes`` after the call (its buffers grow during the call)."""
+    def _device_decim(self, n: int, decim: int) -> bool:
+        """Whether the plans decimate by ``decim`` themselves (nw_plan_set_decim); elsewhere the
+        full device result is sliced."""
+        if decim == 1 or self.engine == 'rocfft':
+            return False
+        return L.decim_supported(n, L.NW_F32 if self.dtype == np.float32 else L.NW_F64, decim)
+
+    def _run(self, x: np.ndarray, out_kind: str, decim: int = 1) -> np.ndarray:
+        """x: (..., n) signals -> (..., F, ceil(n / decim)) on the device(s); the plan cache is
+        trimmed to ``plan_cache_bytes`` after the call (its buffers grow during the call)."""
         self._used = 1
         try:
-            return self._run_plans(x, out_kind)
+            if self._device_decim(x.shape[-1], decim):
+                return self._run_plans(x, out_kind, decim)
+            out = self._run_plans(x, out_kind)
+            return out if decim == 1 else np.ascontiguousarray(out[..., ::decim])
         finally:
             if len(self._plans) > 1:
                 self._evict_plans(keep=max(1, self._used))
 
-    def _run_plans(self, x: np.ndarray, out_kind: str) -> np.ndarray:
+    def _run_plans(self, x: np.ndarray, out_kind: str, decim: int = 1) -> np.ndarray:
         """Several devices shard the signals, or -- with fewer signals than devices (one
         long signal) -- the scales."""
         n = x.shape[-1]
@@ -343,7 +353,8 @@ class WaveletBase:
         nf = len(self._cache.freqs)
         if len(devs) > 1 and nsig < len(devs) and nf >= len(devs):
             from .dist import shard
-            plans = [self._plan(n, nsig, d, shard(nf, i, len(devs)), slot=i) for i, d in enumerate(devs)]
+            plans = [self._plan(n, nsig, d, shard(nf, i, len(devs)), slot=i, decim=decim)
+                     for i, d in enumerate(devs)]
             self._used = len(plans)
             out = execute_multi(plans, x.reshape(nsig, n), out_kind, shard='scales')
             if out_kind in REDUCTIONS:
@@ -351,14 +362,14 @@ class WaveletBase:
             return out.reshape(x.shape[:-1] + out.shape[-2:])
         if len(devs) > 1 and nsig > 1:
             per = -(-nsig // len(devs))          # the largest balanced block (dist.shard)
-            plans = [self._plan(n, per, d, slot=i) for i, d in enumerate(devs)]
+            plans = [self._plan(n, per, d, slot=i, decim=decim) for i, d in enumerate(devs)]
             self._used = len(plans)
             out = execute_multi(plans, x.reshape(nsig, n), out_kind)
             if out_kind in REDUCTIONS:
                 return out
             return out.reshape(x.shape[:-1] + out.shape[-2:])
         self._used = 1
-        return self._plan(n, nsig, devs[0]).execute(x, out_kind=out_kind)
+        return self._plan(n, nsig, devs[0], decim=decim).execute(x, out_kind=out_kind)
 
     def _broadcast_quirk(self, wave: np.ndarray, out_kind: str) -> np.ndarray:
         """2-D (1, N) input: the reference pads the rows to wave.shape[0] = 1 and
@@ -381,38 +392,46 @@ class WaveletBase:
         finally:
             self._cache = saved
 
-    def _transform(self, wave, freqs, reuse: bool, out_kind: str) -> np.ndarray:
+    def _transform(self, wave, freqs, reuse: bool, out_kind: str, decim=1) -> np.ndarray:
+        decim = check_decim(decim)
         wave = np.asarray(wave)
         if (not reuse) or self._cache is None:
             self._build_cache(freqs, wave.shape[0] / self.sfreq)
         if wave.ndim == 1:
-            return self._run(wave, out_kind)
+            return self._run(wave, out_kind, decim)
         if wave.ndim == 2 and wave.shape[0] == 1:
-            return self._broadcast_quirk(wave, out_kind)
+            out = self._broadcast_quirk(wave, out_kind)
+            return out if decim == 1 else np.ascontiguousarray(out[..., ::decim])
         raise ValueError(f'cwt takes one 1-D signal (or the (1, N) form); got shape {wave.shape}. '
                          'Use cwt_batch for batches of signals.')
 
-    def cwt(self, wave: np.ndarray, freqs, reuse: bool = True) -> np.ndarray:
-        """Complex CWT (F, N) of one signal (base.py:378-407)."""
-        return self._transform(wave, freqs, reuse, 'cwt')
+    def cwt(self, wave: np.ndarray, freqs, reuse: bool = True, decim: int = 1) -> np.ndarray:
+        """Complex CWT (F, N) of one signal (base.py:378-407).  ``decim`` (not in the reference's
+        cwt; MNE's decim, as MorseMNE.cwt passes it, wavelets.py:170-191) keeps every decim-th
+        sample: exactly ``cwt(...)[..., ::decim]``, (F, ceil(N / decim)), computed at that size
+        on the device where ``L.decim_supported`` and sliced from the full device result
+        elsewhere.  The wavelet cache is built from the full length either way."""
+        return self._transform(wave, freqs, reuse, 'cwt', decim)
 
-    def power(self, wave: np.ndarray, freqs=None, reuse: bool = True) -> np.ndarray:
-        """|cwt|^2 (base.py:409-425), fused on the device."""
-        return self._transform(wave, freqs, reuse, 'power')
+    def power(self, wave: np.ndarray, freqs=None, reuse: bool = True, decim: int = 1) -> np.ndarray:
+        """|cwt|^2 (base.py:409-425), fused on the device; ``decim`` as in cwt."""
+        return self._transform(wave, freqs, reuse, 'power', decim)
 
-    def abs(self, wave: np.ndarray, freqs=None, reuse: bool = True) -> np.ndarray:
-        """|cwt| (base.py:427-443), fused on the device."""
-        return self._transform(wave, freqs, reuse, 'abs')
+    def abs(self, wave: np.ndarray, freqs=None, reuse: bool = True, decim: int = 1) -> np.ndarray:
+        """|cwt| (base.py:427-443), fused on the device; ``decim`` as in cwt."""
+        return self._transform(wave, freqs, reuse, 'abs', decim)
 
     def cwt_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True,
-                  out: str = 'cwt') -> np.ndarray:
+                  out: str = 'cwt', decim: int = 1) -> np.ndarray:
         """Batched CWT of (..., N) signals -> (..., F, N) in one device call, or (F, N)
         for the reductions over all signals: ``power_mean``, ``itc`` (the compute
         dtype), ``power_sum`` (float64) and ``phase_sum`` (complex128).
 
         Equivalent to stacking ``cwt(w, freqs, reuse)`` over the leading axes
         (the per-epoch loop of mneutils.py:39): the cache is built from the
-        first call's length if absent, then shared by every signal."""
+        first call's length if absent, then shared by every signal.  ``decim`` as in cwt:
+        the last axis holds the samples ``[..., ::decim]`` of the undecimated result."""
+        decim = check_decim(decim)
         waves = np.asarray(waves)
         if waves.ndim < 1:
             raise ValueError('waves must have a trailing sample axis')
@@ -420,7 +439,7 @@ class WaveletBase:
             self._build_cache(freqs, waves.shape[-1] / self.sfreq)
         if out not in ('cwt', 'abs', 'power') + REDUCTIONS:
             raise ValueError(f"out must be one of cwt, abs, power, {', '.join(REDUCTIONS)}; got {out!r}")
-        return self._run(waves, out)
+        return self._run(waves, out, decim)
 
     def plan_stats(self) -> list:
         """Per-plan device stage timings (nw_plan_stats)."""

@@ -65,8 +65,8 @@ const char* out_name(int k) {
 }
 const char* kernel_name(int64_t k) {
     static const char* names[] = {"none", "nw_fused_kernel", "nw_fused_pair_kernel", "nw_chirp_kernel",
-                                  "rows_kernel + cols_kernel", "k1_multiply + rocFFT"};
-    return k >= 0 && k < 6 ? names[k] : "?";
+                                  "rows_kernel + cols_kernel", "k1_multiply + rocFFT", "nw_fused_decim_kernel"};
+    return k >= 0 && k < 7 ? names[k] : "?";
 }
 const char* dtype_name(int dt) { return dt == NW_F32 ? "float32" : "float64"; }
 
@@ -230,6 +230,11 @@ struct nw_plan {
     int device = 0;
     int64_t n = 0, nh = 0, max_batch = 0;
     int nfreq = 0, dtype = NW_F32;
+    // time decimation (nw_plan_set_decim): every output row holds the n / decim samples
+    // y[0], y[decim], ... of the full row; fixed before the first execute
+    int decim = 1;
+    bool executed = false;
+    int64_t n_out() const { return n / decim; }
     uint32_t flags = 0;
     Form form = FORM_ROCFFT;
     // auto engine, chirp-z length with 2n - 1 > M_max: chirp-z only if some row's support fits
@@ -658,6 +663,12 @@ int run_one_pass(nw_plan* p, const nw::WDesc& d, const void* xs_dev, int64_t c, 
                                nw::fused_power_partials(d, p->dtype, out_kind == OUT_PHSUM, p->d_X.ptr, p->d_wtab.ptr,
                                                         dst, c, p->stream));
     }
+    if (p->decim > 1) {
+        p->stats.kernel = NW_K_FUSED_DECIM;
+        return NW_KERNEL_STAGE(p, ST_FUSED, table_was_valid,
+                               nw::launch_fused_decim(d, p->dtype, out_kind, p->decim, p->d_X.ptr, p->d_wtab.ptr, dst, c,
+                                                      p->stream));
+    }
     p->stats.kernel = nw::fused_kernel_id(p->n, p->dtype, d.kind);
     // the forward stage was the last thing enqueued unless the table was built after it
     return NW_KERNEL_STAGE(p, ST_FUSED, table_was_valid,
@@ -747,8 +758,8 @@ int run_chunk(nw_plan* p, const nw::WDesc& d, const void* xs_dev, int64_t c, voi
               bool dst_is_final) {
     if (!p->uniq.U) return run_chunk_rows(p, d, xs_dev, c, dst, out_kind, dst_is_final);
     const bool psum = out_kind == OUT_PSUM || out_kind == OUT_PHSUM;   // fp64 partial rows, one per block of signals
-    const size_t row = psum ? (size_t)p->n * sizeof(double) * (out_kind == OUT_PHSUM ? 2 : 1)
-                            : (size_t)p->n * (out_kind == NW_OUT_CWT ? 2 : 1) * p->esz;
+    const size_t row = psum ? (size_t)p->n_out() * sizeof(double) * (out_kind == OUT_PHSUM ? 2 : 1)
+                            : (size_t)p->n_out() * (out_kind == NW_OUT_CWT ? 2 : 1) * p->esz;
     const int64_t crows = psum ? nw::fused_psum_groups(c) : c;
     NW_TRY(p->d_uout.ensure((size_t)c * p->uniq.U * row));   // crows <= c
     // d_uout is scratch of the CWT's row size: K1 may write it
@@ -769,7 +780,7 @@ bool is_phase(int out_kind) { return out_kind == NW_OUT_ITC || out_kind == NW_OU
 // np.mean over an empty axis.
 int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, void* out, int out_kind, bool host) {
     const bool phase = is_phase(out_kind);
-    const int64_t fn = (int64_t)p->nfreq * p->n;
+    const int64_t fn = (int64_t)p->nfreq * p->n_out();
     const size_t acc_bytes = (size_t)fn * (phase ? 2 : 1) * sizeof(double);
     NW_TRY(p->d_acc.ensure(acc_bytes));
     double* const acc = (double*)p->d_acc.ptr;
@@ -789,7 +800,9 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
         NW_TRY(chirp_table(p, d));   // the rows' M classes decide (chirp_psum_ok)
         chirp_psum = !p->over.U && nw::chirp_psum_ok(p->dtype, phase, p->chirp_counts);
     }
-    const bool psum = (p->form == FORM_ONE_PASS && nw::fused_psum_supported(p->n, p->dtype, d.kind, phase)) || chirp_psum;
+    // (a decimated plan has no partial-sum kernel: its per-signal rows take the chunk path)
+    const bool psum = (p->form == FORM_ONE_PASS && p->decim == 1 && nw::fused_psum_supported(p->n, p->dtype, d.kind, phase)) ||
+                      chirp_psum;
     const int sig_kind = psum ? (phase ? OUT_PHSUM : OUT_PSUM) : (fused && !phase) ? NW_OUT_POWER : NW_OUT_CWT;
     nw_logf(1, "plan %p: %s over %lld signals: %s", (void*)p, out_name(out_kind), (long long)nsig,
             psum ? "fp64 block partial sums inside the transform kernel"
@@ -947,6 +960,27 @@ int nw_trans_grid(double real_length, double sfreq, int interpolate, nw_grid* g)
 
 int nw_fused_supported(int64_t n, int dtype) {
     return nw::fused_supported(n, dtype) || nw::large_supported(n, dtype) || nw::chirp_supported(n, dtype) ? 1 : 0;
+}
+
+int nw_decim_supported(int64_t n, int dtype, int decim) { return nw::decim_supported(n, dtype, decim) ? 1 : 0; }
+
+int nw_plan_set_decim(nw_plan* p, int decim) {
+    if (!p) return fail(NW_E_INVALID, "nw_plan_set_decim: null plan");
+    if (p->executed) return fail(NW_E_STATE, "nw_plan_set_decim: call it before the first execute");
+    if (decim == 1) {
+        p->decim = 1;
+        return NW_OK;
+    }
+    if (!nw::decim_supported(p->n, p->dtype, decim))
+        return fail(NW_E_INVALID, "nw_plan_set_decim: decim " + std::to_string(decim) + " is not supported at n " +
+                                      std::to_string(p->n) + " (nw_decim_supported: power-of-two n 2048 .. 16384, "
+                                      "power-of-two decim with n / decim >= 1024)");
+    if (p->form != FORM_ONE_PASS)
+        return fail(NW_E_INVALID, "nw_plan_set_decim: the rocFFT engine does not decimate (slice its full result)");
+    p->decim = decim;
+    nw_logf(1, "plan %p: decim %d: rows of %lld samples from the folded spectrum (nw_fused_decim_kernel)", (void*)p,
+            decim, (long long)p->n_out());
+    return NW_OK;
 }
 
 int nw_plan_create(nw_plan** out, int device, int64_t n, int64_t max_batch, int32_t nfreq, int dtype,
@@ -1204,6 +1238,7 @@ int nw_execute(nw_plan* p, const void* x, int64_t nsig, void* out, int out_kind,
     if (is_reduction(out_kind) && !out) return fail(NW_E_INVALID, "nw_execute: null out");
     if (nsig == 0 && !is_reduction(out_kind)) return NW_OK;
     DeviceGuard guard(p->device);
+    p->executed = true;
     const nw::WDesc d = exec_rows(p);
     // settle the form of a tentative length before any buffer choice
     if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
@@ -1216,7 +1251,7 @@ int nw_execute(nw_plan* p, const void* x, int64_t nsig, void* out, int out_kind,
     }
 
     const size_t out_elem = (out_kind == NW_OUT_CWT ? 2 : 1) * p->esz;
-    const size_t row_out = (size_t)p->nfreq * p->n * out_elem;  // one signal's output bytes
+    const size_t row_out = (size_t)p->nfreq * p->n_out() * out_elem;  // one signal's output bytes
     const bool host = mem == NW_MEM_HOST;
     // host buffers: the chunk's result on the device before it is read back (rocFFT form, CWT:
     // the complex result is read back straight from d_Y)
@@ -1304,7 +1339,7 @@ int on_each_plan(nw_plan* const* plans, int nplans, F&& fn) {
 int execute_multi_reduce(nw_plan* const* plans, int nplans, const void* x, int64_t nsig, void* out, int out_kind) {
     const nw_plan* p0 = plans[0];
     const bool phase = is_phase(out_kind);
-    const int64_t fn = (int64_t)p0->nfreq * p0->n;
+    const int64_t fn = (int64_t)p0->nfreq * p0->n_out();
     const size_t comps = (size_t)fn * (phase ? 2 : 1);
     const size_t x_row = (size_t)p0->n * p0->esz;
     std::vector<std::vector<double>> part(nplans);
@@ -1339,7 +1374,7 @@ int execute_multi_reduce(nw_plan* const* plans, int nplans, const void* x, int64
 int reduce_partials(nw_plan* const* plans, int nplans, int out_kind, int64_t total, void* out0) {
     nw_plan* p0 = plans[0];
     const bool phase = is_phase(out_kind);
-    const int64_t fn = (int64_t)p0->nfreq * p0->n;
+    const int64_t fn = (int64_t)p0->nfreq * p0->n_out();
     const int64_t comps = fn * (phase ? 2 : 1);
     const size_t acc_bytes = (size_t)comps * sizeof(double);
     DeviceGuard g(p0->device);
@@ -1362,6 +1397,9 @@ int check_same_config(nw_plan* const* plans, int nplans, const char* who) {
     for (int i = 1; i < nplans; ++i)
         if (plans[i]->n != plans[0]->n || plans[i]->nfreq != plans[0]->nfreq || plans[i]->dtype != plans[0]->dtype)
             return fail(NW_E_INVALID, std::string(who) + ": plans must share n, nfreq and dtype");
+    for (int i = 1; i < nplans; ++i)
+        if (plans[i]->decim != plans[0]->decim)
+            return fail(NW_E_INVALID, std::string(who) + ": plans must share decim");
     return NW_OK;
 }
 
@@ -1378,7 +1416,7 @@ int nw_execute_multi(nw_plan* const* plans, int nplans, const void* x, int64_t n
     if (nsig < 0) return fail(NW_E_INVALID, "nw_execute_multi: nsig < 0");
     if (is_reduction(out_kind)) return execute_multi_reduce(plans, nplans, x, nsig, out, out_kind);
     const size_t x_row = (size_t)p0->n * p0->esz;
-    const size_t o_row = (size_t)p0->nfreq * p0->n * (out_kind == NW_OUT_CWT ? 2 : 1) * p0->esz;
+    const size_t o_row = (size_t)p0->nfreq * p0->n_out() * (out_kind == NW_OUT_CWT ? 2 : 1) * p0->esz;
     return on_each_plan(plans, nplans, [&](int i) {
         int64_t s0 = 0, cnt = 0;
         block_of(nsig, i, nplans, &s0, &cnt);
@@ -1409,7 +1447,7 @@ int nw_execute_multi_device(nw_plan* const* plans, int nplans, const void* const
     // reductions: per-device fp64 partial sums (each plan's d_part), then device 0's gather
     // buffer (plans[0]->d_gather); both persist on the plans and are freed with them
     if (reduce) {
-        const size_t acc_bytes = (size_t)plans[0]->nfreq * plans[0]->n * (phase ? 2 : 1) * sizeof(double);
+        const size_t acc_bytes = (size_t)plans[0]->nfreq * plans[0]->n_out() * (phase ? 2 : 1) * sizeof(double);
         for (int i = 0; i < nplans; ++i) {
             DeviceGuard g(plans[i]->device);
             const int r = plans[i]->d_part.ensure(acc_bytes);
@@ -1435,6 +1473,8 @@ int nw_execute_multi_scales(nw_plan* const* plans, int nplans, const void* x, in
         if (!plans[i] || plans[i]->n != p0->n || plans[i]->dtype != p0->dtype ||
             (plans[i]->flags & NW_INTERPOLATE) != (p0->flags & NW_INTERPOLATE))
             return fail(NW_E_INVALID, "nw_execute_multi_scales: plans must share n, dtype and interpolate");
+    for (int i = 1; i < nplans; ++i)
+        if (plans[i]->decim != p0->decim) return fail(NW_E_INVALID, "nw_execute_multi_scales: plans must share decim");
     if (out_kind < NW_OUT_CWT || out_kind > NW_OUT_PHASE_SUM)
         return fail(NW_E_INVALID, "nw_execute_multi_scales: bad out_kind");
     if (nsig < 0) return fail(NW_E_INVALID, "nw_execute_multi_scales: nsig < 0");
@@ -1449,7 +1489,7 @@ int nw_execute_multi_scales(nw_plan* const* plans, int nplans, const void* x, in
     size_t oe = (out_kind == NW_OUT_CWT ? 2 : 1) * p0->esz;
     if (out_kind == NW_OUT_POWER_SUM) oe = sizeof(double);
     if (out_kind == NW_OUT_PHASE_SUM) oe = 2 * sizeof(double);
-    const size_t x_row = (size_t)p0->n * p0->esz, o_scale = (size_t)p0->n * oe;
+    const size_t x_row = (size_t)p0->n * p0->esz, o_scale = (size_t)p0->n_out() * oe;
     return on_each_plan(plans, nplans, [&](int i) {
         nw_plan* p = plans[i];
         if (is_reduction(out_kind) || nsig <= 1)   // the rows are contiguous in out

@@ -956,6 +956,30 @@ int fused_kernel_id(int64_t n, int dtype, int kind) {
     return NW_K_NONE;
 }
 
+// launch_n's grid for the single-signal output kernel (the decimated kernel maps its blocks alike)
+bool fused_shape(int64_t n, int dtype, int64_t nsig, int nfreq, FusedShape* sh) {
+#define NW_SHAPE(TY, NN, EE)                                                   \
+    if (n == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64)) {             \
+        sh->e = EE;                                                            \
+        sh->group = group_for(kGroupOut<TY, NN>, nsig, nfreq);                 \
+        sh->tile_f = kTileFT<TY>;                                              \
+        const int64_t nsg = (nsig + sh->group - 1) / sh->group;                \
+        sh->tile_g = tile_g_of(nsg, kTileGOut<TY, NN>);                        \
+        sh->nsg_pad = (nsg + 8 * sh->tile_g - 1) / (8 * sh->tile_g) * (8 * sh->tile_g); \
+        sh->blocks = sh->nsg_pad * ((nfreq + sh->tile_f - 1) / sh->tile_f) * sh->tile_f; \
+        return sh->blocks <= 0x7fffffff && sh->nsg_pad <= 0x7fffffff;          \
+    }
+    NW_FUSED_TABLE(NW_SHAPE)
+#undef NW_SHAPE
+    return false;
+}
+
+const int* fused_wnz(const void* wtab, int64_t n, int nfreq, int dtype, int kind) {
+    const size_t esz = dtype == NW_F32 ? sizeof(float) : sizeof(double);
+    return reinterpret_cast<const int*>(reinterpret_cast<const char*>(wtab) +
+                                        wtab_row_bytes(n, nfreq, esz, kind != NW_TABLE));
+}
+
 hipError_t launch_fused(const WDesc& d, int dtype, int out_kind, const void* X, const void* wtab, void* out,
                         int64_t nsig, hipStream_t s) {
     const bool realw = d.kind != NW_TABLE;

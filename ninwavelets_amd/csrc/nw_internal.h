@@ -238,6 +238,20 @@ int        fused_kernel_id(int64_t n, int dtype, int kind);   // NW_K_FUSED or N
 // forward R2C of nsig real rows of length n (fused sizes) into half spectra of row stride nh
 hipError_t fused_forward(int64_t n, int dtype, const void* x, void* X, int64_t nsig, int64_t nh, hipStream_t s);
 hipError_t fused_twiddles(int64_t n, int dtype, void** out);   // exact exp(+2 pi i j / n), cached per device
+// The block shape of an output launch of nw_fused_kernel at length n (its elements per thread,
+// signals per block, XCD tile and padded grid), and the W-support array behind the rows of a
+// table built by build_wtable: what the decimated kernel (nw_decim.hip) shares with it
+struct FusedShape {
+    int e, group, tile_f, tile_g;
+    int64_t nsg_pad, blocks;
+};
+bool       fused_shape(int64_t n, int dtype, int64_t nsig, int nfreq, FusedShape* sh);
+const int* fused_wnz(const void* wtab, int64_t n, int nfreq, int dtype, int kind);
+// decimated one-pass form (nw_decim.hip): every decim-th output sample of a fused length as the
+// (n / decim)-point inverse transform of the folded product; out rows are n / decim long
+bool       decim_supported(int64_t n, int dtype, int decim);
+hipError_t launch_fused_decim(const WDesc& d, int dtype, int out_kind, int decim, const void* X, const void* wtab,
+                              void* out, int64_t nsig, hipStream_t s);
 // epoch reduction partials (fused sizes, fp32 analytic rows; power up to E = 32, phase
 // E <= 16): per block of signals the sum over its signals (fp64, in signal order) of |y|^2,
 // or with phase of y / |y|; one

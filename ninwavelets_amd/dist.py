@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import REDUCTIONS
+from .engine import REDUCTIONS, check_decim
 
 _SUM_OF = {'power_mean': 'power_sum', 'itc': 'phase_sum',
            'power_sum': 'power_sum', 'phase_sum': 'phase_sum'}
@@ -62,13 +62,15 @@ def reduce_partials(partial: np.ndarray, kind: str, nsig: int, dtype, group=None
     return finalize(kind, total, nsig, dtype)
 
 
-def epochs_reduce(wavelet, waves: np.ndarray, freqs, kind: str, group=None) -> np.ndarray:
+def epochs_reduce(wavelet, waves: np.ndarray, freqs, kind: str, group=None, decim: int = 1) -> np.ndarray:
     """EpochsWavelet.power / itc of ``waves`` (epochs, n) over all ranks of ``group``:
-    this rank transforms only its block of epochs on its GPU, then one all_reduce."""
+    this rank transforms only its block of epochs on its GPU, then one all_reduce.  ``decim``
+    keeps every decim-th sample: (F, ceil(n / decim)) values per rank and collective."""
     import torch
     import torch.distributed as dist
     if kind not in REDUCTIONS:
         raise ValueError(f'kind must be one of {REDUCTIONS}')
+    decim = check_decim(decim)
     waves = np.asarray(waves)
     nsig, n = waves.shape[0], waves.shape[-1]
     rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -78,9 +80,9 @@ def epochs_reduce(wavelet, waves: np.ndarray, freqs, kind: str, group=None) -> n
     sum_kind = _SUM_OF[kind]
     nf = len(wavelet._cache.freqs)
     if s1 > s0:
-        part = wavelet.cwt_batch(waves[s0:s1], freqs, reuse=True, out=sum_kind)
+        part = wavelet.cwt_batch(waves[s0:s1], freqs, reuse=True, out=sum_kind, decim=decim)
     else:
-        part = np.zeros((nf, n), dtype=np.complex128 if sum_kind == 'phase_sum' else np.float64)
+        part = np.zeros((nf, -(-n // decim)), dtype=np.complex128 if sum_kind == 'phase_sum' else np.float64)
     dev = None
     if dist.get_backend(group) == 'nccl':
         dev = torch.device('cuda', torch.cuda.current_device())

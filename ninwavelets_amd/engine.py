@@ -34,6 +34,19 @@ def np_dtype(dtype) -> np.dtype:
     return dt
 
 
+def check_decim(decim) -> int:
+    """``decim`` as an int >= 1 (MNE's decim, the reference's MorseMNE.cwt, wavelets.py:170-191);
+    ValueError for anything else, before any device work."""
+    import operator
+    try:
+        d = operator.index(decim)
+    except TypeError:
+        raise ValueError(f'decim must be an integer >= 1, got {decim!r}') from None
+    if isinstance(decim, bool) or d < 1:
+        raise ValueError(f'decim must be an integer >= 1, got {decim!r}')
+    return d
+
+
 def out_dtype(dtype, out_kind: str) -> np.dtype:
     dt = np_dtype(dtype)
     if out_kind == 'power_sum':                 # fp64 partial sums whatever the compute dtype
@@ -235,13 +248,17 @@ def _is_device_tensor(a) -> bool:
 
 
 class Plan:
-    """One nw_plan: signals of length ``n``, ``nfreq`` scales, compute ``dtype``."""
+    """One nw_plan: signals of length ``n``, ``nfreq`` scales, compute ``dtype``.  ``decim`` > 1
+    (nw_plan_set_decim; where L.decim_supported) keeps every decim-th output sample: the rows
+    are ``n_out`` = n // decim long."""
 
     def __init__(self, n: int, nfreq: int, dtype='float32', device: int = 0, max_batch: int = 1,
                  interpolate: bool = False, engine: str | None = None, timing: bool = False,
-                 dedup: bool = True, timing_chain: bool = False):
+                 dedup: bool = True, timing_chain: bool = False, decim: int = 1):
         self.n, self.nfreq, self.device, self.max_batch = int(n), int(nfreq), int(device), int(max_batch)
         self.dtype = np_dtype(dtype)
+        self.decim = check_decim(decim)
+        self.n_out = self.n
         self.interpolate = bool(interpolate)
         flags = L.NW_INTERPOLATE if interpolate else 0
         if engine == 'rocfft':
@@ -261,6 +278,13 @@ class Plan:
                                        self.nfreq, L.NW_F32 if self.dtype == np.float32 else L.NW_F64,
                                        flags))
         self.wavelet_token = None
+        if self.decim > 1:
+            try:
+                L.check(L.lib().nw_plan_set_decim(self._h, self.decim))
+            except Exception:
+                self.close()
+                raise
+            self.n_out = self.n // self.decim
 
     # -- wavelet -----------------------------------------------------------------
     def set_wavelet(self, kind: str, params, freqs, grid: L.nw_grid, table=None, token=None,
@@ -307,7 +331,7 @@ class Plan:
 
     # -- execute -----------------------------------------------------------------
     def execute(self, x, out=None, out_kind: str = 'cwt'):
-        """x: (S, n) numpy array (host) -> returns (S, nfreq, n); or device tensors."""
+        """x: (S, n) numpy array (host) -> returns (S, nfreq, n_out); or device tensors."""
         kind = OUT_KINDS[out_kind]
         reduce = out_kind in REDUCTIONS
         if _is_device_tensor(x):
@@ -325,7 +349,7 @@ class Plan:
         lead = x.shape[:-1]
         nsig = int(np.prod(lead)) if lead else 1
         odt = out_dtype(self.dtype, out_kind)
-        shape = (self.nfreq, self.n) if reduce else lead + (self.nfreq, self.n)
+        shape = (self.nfreq, self.n_out) if reduce else lead + (self.nfreq, self.n_out)
         if out is None:
             out = HOST_POOL.empty(shape, odt)
         elif out.dtype != odt or not out.flags.c_contiguous or out.size != int(np.prod(shape)):
@@ -357,7 +381,8 @@ class Plan:
 
     def execute_ptr(self, x_ptr: int, nsig: int, out_ptr: int, out_kind: str = 'cwt'):
         """Raw device pointers on the plan's device (asynchronous on the plan stream; the
-        caller orders it against its own streams, e.g. with plan.sync())."""
+        caller orders it against its own streams, e.g. with plan.sync()).  The output holds
+        (nsig, nfreq, n_out) values, (nfreq, n_out) for the reductions."""
         L.check(L.lib().nw_execute(self._h, ctypes.c_void_p(x_ptr), int(nsig), ctypes.c_void_p(out_ptr),
                                    OUT_KINDS[out_kind], L.NW_MEM_DEVICE))
 
@@ -382,7 +407,7 @@ class Plan:
     def _check_device_buffers(self, x, out, nsig, out_kind):
         import torch
         if self._check_device_input(x) != nsig:
-            raise ValueError('device buffer sizes do not match (S, n) -> (S, nfreq, n) / (nfreq, n)')
+            raise ValueError('device buffer sizes do not match (S, n) -> (S, nfreq, n_out) / (nfreq, n_out)')
         want_o = {('cwt', np.float32): torch.complex64, ('cwt', np.float64): torch.complex128}.get(
             (out_kind, self.dtype.type), x.dtype)
         if out_kind == 'power_sum':
@@ -394,8 +419,8 @@ class Plan:
         if not out.is_contiguous():
             raise ValueError('device buffers must be contiguous')
         rows = 1 if out_kind in REDUCTIONS else nsig
-        if out.numel() != rows * self.nfreq * self.n:
-            raise ValueError('device buffer sizes do not match (S, n) -> (S, nfreq, n) / (nfreq, n)')
+        if out.numel() != rows * self.nfreq * self.n_out:
+            raise ValueError('device buffer sizes do not match (S, n) -> (S, nfreq, n_out) / (nfreq, n_out)')
         if out.device.index != self.device:
             raise ValueError(f'device buffers must live on device {self.device}')
 
@@ -445,7 +470,9 @@ def execute_multi(plans, x: np.ndarray, out_kind: str = 'cwt', shard: str = 'sig
     lead = x.shape[:-1]
     nsig = int(np.prod(lead)) if lead else 1
     nf = sum(p.nfreq for p in plans) if shard == 'scales' else p0.nfreq
-    shape = (nf, p0.n) if out_kind in REDUCTIONS else lead + (nf, p0.n)
+    if any(p.n_out != p0.n_out for p in plans):
+        raise ValueError('plans must share decim')
+    shape = (nf, p0.n_out) if out_kind in REDUCTIONS else lead + (nf, p0.n_out)
     out = HOST_POOL.empty(shape, out_dtype(p0.dtype, out_kind))
     arr = (ctypes.c_void_p * len(plans))(*[p.handle.value for p in plans])
     fn = L.lib().nw_execute_multi_scales if shard == 'scales' else L.lib().nw_execute_multi

@@ -24,16 +24,17 @@ class EpochsWavelet:
         idx = self.epochs.ch_names.index(ch_name)
         return self.epochs.get_data()[:, idx, :]
 
-    def cwt(self, ch_name: str, freqs) -> np.ndarray:
-        """(epochs, F, N) complex (mneutils.py:26-40)."""
-        return self.wavelet.cwt_batch(self._waves(ch_name), freqs, reuse=True)
+    def cwt(self, ch_name: str, freqs, decim: int = 1) -> np.ndarray:
+        """(epochs, F, N) complex (mneutils.py:26-40); ``decim`` (MNE's, as MorseMNE.cwt passes
+        it, wavelets.py:170-191) keeps every decim-th sample of the last axis, here and below."""
+        return self.wavelet.cwt_batch(self._waves(ch_name), freqs, reuse=True, decim=decim)
 
-    def power(self, ch_name: str, freqs) -> np.ndarray:
+    def power(self, ch_name: str, freqs, decim: int = 1) -> np.ndarray:
         """Epoch-mean of |cwt|^2, (F, N) (mneutils.py:42-55), reduced on the device:
         the (epochs, F, N) CWT is never materialised (fp64 sums in epoch order)."""
-        return self.wavelet.cwt_batch(self._waves(ch_name), freqs, reuse=True, out='power_mean')
+        return self.wavelet.cwt_batch(self._waves(ch_name), freqs, reuse=True, out='power_mean', decim=decim)
 
-    def itc(self, ch_name: str, freqs) -> np.ndarray:
+    def itc(self, ch_name: str, freqs, decim: int = 1) -> np.ndarray:
         """Inter-trial coherence |mean(cwt/|cwt|)|, (F, N) (mneutils.py:57-71), reduced
         on the device; a point where some epoch has |cwt| = 0 is NaN, as in the reference."""
-        return self.wavelet.cwt_batch(self._waves(ch_name), freqs, reuse=True, out='itc')
+        return self.wavelet.cwt_batch(self._waves(ch_name), freqs, reuse=True, out='itc', decim=decim)
