@@ -30,8 +30,7 @@ namespace {
 // fused_psum_groups, i.e. kPsumGroup signals per row
 constexpr int kGroupC = 8;
 static_assert(kGroupC == kPsumGroup, "chirp-z partial rows are counted by fused_psum_groups");
-constexpr int kTileFC = 8;    // scales per XCD tile
-constexpr int kTileGC = 4;    // signal groups per XCD tile
+// (XCD tile kTileFC x kTileGC: nw_shape.h)
 constexpr int kRegOsz = 16;   // PassInfo without last-pass pairing: j = t + q*T everywhere
 
 // The register-DFT form of one kernel instantiation (nw_dft_reg.h): the fp64 phase-sum kernel
@@ -133,15 +132,9 @@ __global__ __launch_bounds__(M / E, (kChirpWps<T, M, E, OUT>)) void nw_chirp_ker
     extern __shared__ __align__(16) unsigned char smem[];
     T* lds = reinterpret_cast<T*>(smem);
     const int t = threadIdx.x;
-    // XCD-aware block -> (scale, signal group), as nw_fused_kernel
-    const int b = blockIdx.x;
-    const int xcd = b & 7;
-    const int local = b >> 3;
-    const int pos = local % (kTileFC * kTileGC);
-    const int round = local / (kTileFC * kTileGC);
-    const int nfr = (nrows + kTileFC - 1) / kTileFC;
-    const int fl = (round % nfr) * kTileFC + pos % kTileFC;   // this launch's rows: rowmap[0 .. nrows)
-    const int sg = ((round / nfr) * kTileGC + pos / kTileFC) * 8 + xcd;
+    // XCD-aware block -> (scale, signal group): block_slot (nw_shape.h)
+    const BlockSlot slot = block_slot(blockIdx.x, nrows, kTileFC, kTileGC);
+    const int fl = slot.row, sg = slot.group;   // fl: this launch's rows, rowmap[0 .. nrows)
     if (fl >= nrows || sg >= nsg_pad || (int64_t)sg * kGroupC >= nsig) return;
     const int fi = rowmap[fl];
     const int64_t s_begin = (int64_t)sg * kGroupC;
@@ -388,19 +381,13 @@ hipError_t launch_m_e(const WDesc& d, int out_kind, const void* X, const void* w
     if (e != hipSuccess) return e;
     const C2<T>* bh = reinterpret_cast<const C2<T>*>(tabs);
     const C2<T>* ct = bh + M;
-    const int64_t nsg = (nsig + kGroupC - 1) / kGroupC;
-    const int64_t nsg_pad = (nsg + 8 * kTileGC - 1) / (8 * kTileGC) * (8 * kTileGC);
-    const int64_t nfr = (nrows + kTileFC - 1) / kTileFC;
-    const int64_t blocks = nsg_pad * nfr * kTileFC;
-    if (blocks > 0x7fffffff || nsg_pad > 0x7fffffff) return hipErrorInvalidConfiguration;
+    const BlockGrid g = block_grid_tile((nsig + kGroupC - 1) / kGroupC, nrows, kTileFC, kTileGC);
+    if (!g.ok) return hipErrorInvalidConfiguration;
     const cplx<T>* Xc = reinterpret_cast<const cplx<T>*>(X);
     const C2<T>* twc = reinterpret_cast<const C2<T>*>(tw);
     auto go = [&](auto kern) {
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return;
-        nw_launch(kern, (unsigned)blocks, threads, lds, s, d, Xc, wtab, out, twc, bh, ct, nsig, (int)nsg_pad, rowmap, nrows,
-                                                    ksup);
-        e = hipGetLastError();
+        e = nw_launch_lds(kern, (unsigned)g.blocks, threads, lds, s, d, Xc, wtab, out, twc, bh, ct, nsig,
+                          (int)g.groups_pad, rowmap, nrows, ksup);
     };
     if (out_kind == NW_OUT_CWT) go(nw_chirp_kernel<T, M, E, NW_OUT_CWT, REALW>);
     else if (out_kind == NW_OUT_POWER) go(nw_chirp_kernel<T, M, E, NW_OUT_POWER, REALW>);

@@ -56,15 +56,9 @@ __global__ __launch_bounds__(ND / E, (kWpsDecim<T>)) void nw_fused_decim_kernel(
     const int t = threadIdx.x;
     const int n = __builtin_amdgcn_readfirstlane((int)d.n);
 
-    // XCD-aware block -> (scale, signal group): as nw_fused_kernel
-    const int b = blockIdx.x;
-    const int xcd = b & 7;
-    const int local = b >> 3;
-    const int pos = local % (tf * tg);
-    const int round = local / (tf * tg);
-    const int nfr = (d.nfreq + tf - 1) / tf;
-    const int fi = (round % nfr) * tf + pos % tf;
-    const int sg = ((round / nfr) * tg + pos / tf) * 8 + xcd;
+    // XCD-aware block -> (scale, signal group): block_slot (nw_shape.h)
+    const BlockSlot slot = block_slot(blockIdx.x, d.nfreq, tf, tg);
+    const int fi = slot.row, sg = slot.group;
     if (fi >= d.nfreq || sg >= nsg_pad || (int64_t)sg * group >= nsig) return;
     const int64_t s_begin = (int64_t)sg * group;
     // the block's signal count pinned in an SGPR (as nw_fused_pair_kernel: an int64 bound in
@@ -133,69 +127,41 @@ __global__ __launch_bounds__(ND / E, (kWpsDecim<T>)) void nw_fused_decim_kernel(
     }
 }
 
-template <typename T, int ND, int E, int OUT, bool REALW>
-hipError_t launch_one(const WDesc& d, const FusedShape& sh, int decim, int wtt, const void* X, const void* wtab,
-                      void* out, const void* tw, const int* wnz, int64_t nsig, hipStream_t s) {
-    const int lds = kLdsBytes<T, ND, E>;
-    auto* kernel = nw_fused_decim_kernel<T, ND, E, OUT, REALW>;
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    nw_launch(kernel, (unsigned)sh.blocks, ND / E, lds, s, d, reinterpret_cast<const cplx<T>*>(X), wtab, out,
-              reinterpret_cast<const C2<T>*>(tw), nsig, sh.group, (int)sh.nsg_pad, wnz, sh.tile_f, sh.tile_g, decim,
-              wtt);
-    return hipGetLastError();
-}
-
 template <typename T, int ND, int E>
 hipError_t launch_nd(const WDesc& d, int dtype, int out_kind, int decim, const void* X, const void* wtab, void* out,
                      int64_t nsig, hipStream_t s) {
-    // the block shape of an undecimated launch of length ND, and the E the support table was built for
-    FusedShape sh{}, full{};
-    if (!fused_shape(ND, dtype, nsig, d.nfreq, &sh) || sh.e != E || !fused_shape(d.n, dtype, 1, 1, &full))
-        return hipErrorNotSupported;
+    if (out_kind != NW_OUT_CWT && out_kind != NW_OUT_POWER && out_kind != NW_OUT_ABS) return hipErrorInvalidValue;
+    // the block shape of an undecimated launch of length ND
+    FusedShape sh{};
+    if (!fused_shape(ND, dtype, nsig, d.nfreq, &sh)) return hipErrorNotSupported;
     void* tw = nullptr;
     hipError_t e = fused_twiddles(ND, dtype, &tw);
     if (e != hipSuccess) return e;
-    const int wtt = (int)(d.n / full.e);
-    const int* wnz = fused_wnz(wtab, d.n, d.nfreq, dtype, d.kind);
+    const int wtt = (int)(d.n / fused_e(d.n, dtype));   // the support table was built for the full length's E
     const bool realw = d.kind != NW_TABLE;
-#define NW_DECIM_OUT(OUTK)                                                                                         \
-    return realw ? launch_one<T, ND, E, OUTK, true>(d, sh, decim, wtt, X, wtab, out, tw, wnz, nsig, s)             \
-                 : launch_one<T, ND, E, OUTK, false>(d, sh, decim, wtt, X, wtab, out, tw, wnz, nsig, s)
-    if (out_kind == NW_OUT_CWT) NW_DECIM_OUT(NW_OUT_CWT);
-    if (out_kind == NW_OUT_POWER) NW_DECIM_OUT(NW_OUT_POWER);
-    if (out_kind == NW_OUT_ABS) NW_DECIM_OUT(NW_OUT_ABS);
-#undef NW_DECIM_OUT
-    return hipErrorInvalidValue;
+    const int* wnz = wtab_wnz(wtab, d.n, d.nfreq, sizeof(T), realw);
+    return for_out_kind(out_kind, [&](auto o) {
+        auto go = [&](auto kernel) {
+            return nw_launch_lds(kernel, (unsigned)sh.blocks, ND / E, kLdsBytes<T, ND, E>, s, d,
+                                 reinterpret_cast<const cplx<T>*>(X), wtab, out, reinterpret_cast<const C2<T>*>(tw),
+                                 nsig, sh.group, (int)sh.nsg_pad, wnz, sh.tile_f, sh.tile_g, decim, wtt);
+        };
+        constexpr int OUT = decltype(o)::value;
+        return realw ? go(nw_fused_decim_kernel<T, ND, E, OUT, true>) : go(nw_fused_decim_kernel<T, ND, E, OUT, false>);
+    });
 }
 
 }  // namespace
 
-// Transform lengths ND = n / decim of the decimated kernel and their elements per thread: the
-// rows of NW_FUSED_TABLE (nw_fused.hip) for 1024 <= ND <= 8192 (launch_nd checks E against it)
-#define NW_DECIM_TABLE(X)                                                  \
-    X(float, 1024, 16) X(float, 2048, 16) X(float, 4096, 16) X(float, 8192, 32) \
-    X(double, 1024, 16) X(double, 2048, 16) X(double, 4096, 16) X(double, 8192, 32)
-
-// power-of-two n = 2048 .. 16384 and decim >= 2 with n / decim >= 1024, fp32 and fp64: ten
-// (n, decim) pairs per dtype
-bool decim_supported(int64_t n, int dtype, int decim) {
-    if (dtype != NW_F32 && dtype != NW_F64) return false;
-    if (n < 2048 || n > 16384 || (n & (n - 1))) return false;
-    if (decim < 2 || (decim & (decim - 1))) return false;
-    return n / decim >= 1024;
-}
-
+// the transform length ND = n / decim is a row of the one-pass size table up to kDecimMaxND
+// (decim_supported, nw_shape.h), run at that row's E
 hipError_t launch_fused_decim(const WDesc& d, int dtype, int out_kind, int decim, const void* X, const void* wtab,
                               void* out, int64_t nsig, hipStream_t s) {
     if (!decim_supported(d.n, dtype, decim)) return hipErrorNotSupported;
-    const int64_t nd = d.n / decim;
-#define NW_DECIM_LAUNCH(TY, NN, EE)                                \
-    if (nd == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64)) \
-        return launch_nd<TY, NN, EE>(d, dtype, out_kind, decim, X, wtab, out, nsig, s);
-    NW_DECIM_TABLE(NW_DECIM_LAUNCH)
-#undef NW_DECIM_LAUNCH
-    return hipErrorNotSupported;
+    return for_fused_size(d.n / decim, dtype, hipErrorNotSupported, [&]<typename T, int ND, int E>(FusedSize<T, ND, E>) {
+        if constexpr (ND <= kDecimMaxND) return launch_nd<T, ND, E>(d, dtype, out_kind, decim, X, wtab, out, nsig, s);
+        else return hipErrorNotSupported;
+    });
 }
 
 }  // namespace nw

@@ -10,6 +10,7 @@
 #include "nw_dcheck.h"
 #include "nw_dft_reg.h"
 #include "nw_internal.h"
+#include "nw_shape.h"
 
 // Tuning constants; each was measured against its alternatives (numbers in DESIGN.md §4).
 // unpaired last pass: lane-pair transposes (DPP) regroup outputs of <= 8 B into 16-B stores
@@ -27,7 +28,6 @@ constexpr int kPruneMin = 4;
 constexpr int kXdmaMinE = 32;
 // W held in registers for the whole block when E <= this
 constexpr int kWregMaxE = 16;
-
 
 namespace nw {
 namespace {

@@ -84,80 +84,9 @@ constexpr int kPairWKeepRed = 10;
 // (W elements beyond kWKeep32 evaluated in registers for Morse rows instead of re-read:
 // C4 3.360-3.368 -> 3.420-3.430 ms per launch; removing those loads altogether (diagnostic)
 // 3.367-3.369: the re-read costs nothing, the evaluation's VALU does)
-// E = 32: a pass-0 variant for rows whose support ends below 3/4 of n (NZ = 24: C4's rows
-// above 186 Hz), between the power-of-two variants: C4 3.360-3.368 -> 3.346-3.351 ms
-constexpr bool kNz24 = true;
 // signal-pair kernel: the next pair's X by LDS-DMA before the stores (cwt output only, below)
 constexpr bool kPairXD = true;
-template <typename T, int N, int E> constexpr bool kNz24Of = kNz24 && E > 16;
-// NZ = 12 and 20 between them (fp32 only: fp64 n = 16384 |y| spills 20 B with them)
-template <typename T, int N, int E> constexpr bool kNzFineOf = kNz24Of<T, N, E> && sizeof(T) == 4;
-// ... and for the fp64 cwt output (round 6: C4 shape fp64 -0.7 to -0.9 %; its |y| spills with
-// them; -DNW_F64_FINE=0 for the A/B)
-#ifndef NW_F64_FINE
-#define NW_F64_FINE 1
-#endif
-#if NW_F64_FINE
-template <typename T, int N, int E, int OUT> constexpr bool kNzFineOut = kNzFineOf<T, N, E> ||
-    (kNz24Of<T, N, E> && OUT == NW_OUT_CWT);
-#else
-template <typename T, int N, int E, int OUT> constexpr bool kNzFineOut = kNzFineOf<T, N, E>;
-#endif
-// The pass-0 variant (elements read and multiplied per thread) that runs a row of support nz:
-// the smallest instantiated NZ >= nz.  The X LDS-DMA copies what THAT variant reads (a row
-// of support 12 on a kernel without the NZ = 12 variant runs NZ = 16, which reads 16 elements)
-template <typename T, int N, int E, int OUT>
-__device__ __forceinline__ int pass0_variant(int nz) {
-    if (nz <= 4) return 4;
-    if (nz <= 8) return 8;
-    if (kNzFineOut<T, N, E, OUT> && nz <= 12) return 12;
-    if (E > 16 && nz <= 16) return 16;
-    if (kNzFineOut<T, N, E, OUT> && nz <= 20) return 20;
-    if (kNz24Of<T, N, E> && nz <= 24) return 24;
-    return E;
-}
-// signals per block: C3 0.354 -> 0.348 ms, C4 1.774 -> 1.770 vs 4 (2 and 16 slower or equal).
-// fp64 (one block per CU): 8 since round 6 (C4 shape fp64 7.31-7.32 -> 7.25-7.28 ms per launch,
-// with the fine pass-0 variants below 7.21-7.24; 2 signals +2.6 %, tiles 4 x 8 +1.5 %, 8 x 2
-// +0.3 %; profiles/r06_f64_group_ab.txt).  Round 3 had taken 4 (then 10.04 -> 9.66 ms against
-// 8 signals, when X was re-read from L2 per scale without the LDS-DMA)
-constexpr int kGroup = 8;
-static_assert(kGroup == kPsumGroup, "fused partial rows are counted by fused_psum_groups");
-// (-DNW_GROUP64 / NW_TILE64_F / NW_TILE64_G: diagnostic A/B of the fp64 block and tile shape)
-#ifndef NW_GROUP64
-#define NW_GROUP64 8
-#endif
-constexpr int kGroup64 = NW_GROUP64;
-// XCD tile: kTileF scales x kTileG signal groups per XCD round (fp64 tiles 16 x 2, 4 x 8,
-// 32 x 1, 2 x 16 measured -2.4 / -0.2 / -4.8 / -3.5 % against 8 x 4)
-constexpr int kTileF = 8, kTileG = 4;
-#ifndef NW_TILE64_F
-#define NW_TILE64_F kTileF
-#endif
-#ifndef NW_TILE64_G
-#define NW_TILE64_G kTileG
-#endif
-template <typename T> constexpr int kTileFT = sizeof(T) == 8 ? NW_TILE64_F : kTileF;
-template <typename T> constexpr int kTileGT = sizeof(T) == 8 ? NW_TILE64_G : kTileG;
-// fp64 output kernels at n = 16384 (one block per CU): 16-signal blocks in XCD tiles of 8 scales
-// x 2 groups -- the same X + W working set per XCD round as 8 x 4 of 8 signals, half the blocks
-// (C4 shape fp64 7.175 -> 7.12-7.13 and 7.246 -> 7.212 ms per launch on two boxes, -0.5 %;
-// 32 x 1 -0.3 %, 16 signals in 8 x 4 tiles -0.4 %, 16 in 8 x 1 +-0; profiles/r06_f64_g16_ab.txt).
-// Smaller n (two blocks per CU) and the partial-sum kernels keep kGroup64 / kTileGT.
-#ifndef NW_GROUP64_16K
-#define NW_GROUP64_16K 16
-#endif
-#ifndef NW_TILE64_G_16K
-#define NW_TILE64_G_16K 2
-#endif
-template <typename T, int N> constexpr int kGroupOut = sizeof(T) == 8 ? (N == 16384 ? NW_GROUP64_16K : kGroup64) : kGroup;
-template <typename T, int N> constexpr int kTileGOut = sizeof(T) == 8 && N == 16384 ? NW_TILE64_G_16K : kTileGT<T>;
-// ... and at most as many groups as a launch has (in units of 8 XCD slots): C2 (64 signals =
-// 8 groups) with 4-group tiles padded its grid to 4x its real blocks
-__host__ __device__ constexpr int tile_g_of(int64_t nsg, int tg_max) {
-    const int64_t per = (nsg + 7) / 8;
-    return per < tg_max ? (int)(per < 1 ? 1 : per) : tg_max;
-}
+// (block shapes, XCD tiles, the pass-0 ladder and its fine variants: nw_shape.h)
 // Occupancy: 4 waves/SIMD (128 VGPRs) for fp32 -- the half image is <= 74 KiB, so two
 // 512-thread blocks share a CU at n = 16384 (more at smaller n) and one block's barriers,
 // memory waits and store bursts overlap another's arithmetic -- and 2 for fp64 (twice the
@@ -200,20 +129,9 @@ __global__ __launch_bounds__(N / E, (kWpsOf<T, E, OUT>)) void nw_fused_kernel(WD
     const int t = threadIdx.x;
     if constexpr (kPrioHalf<T> && XD) prio_half(t, N / E);   // the measured case: E = 32 output kernels
 
-    // XCD-aware block -> (scale, signal group).  Blocks b, b+8, b+16, ... share an XCD
-    // (and its 4 MiB L2); the ~64 of them resident at a time cover a tile of
-    // kTileF scales x kTileG signal groups, so each W row is read by kTileG blocks
-    // and each X group by kTileF blocks from L2 (W + X of a tile ~2.5 MiB), and
-    // the XCD sweeps all scales of its groups before moving on.
-    const int b = blockIdx.x;
-    const int xcd = b & 7;
-    const int local = b >> 3;
-    constexpr int TF = kTileFT<T>;
-    const int pos = local % (TF * tg);
-    const int round = local / (TF * tg);
-    const int nfr = (d.nfreq + TF - 1) / TF;
-    const int fi = (round % nfr) * TF + pos % TF;
-    const int sg = ((round / nfr) * tg + pos / TF) * 8 + xcd;
+    // XCD-aware block -> (scale, signal group): block_slot (nw_shape.h)
+    const BlockSlot slot = block_slot(blockIdx.x, d.nfreq, kTileFT<T>, tg);
+    const int fi = slot.row, sg = slot.group;
     if (fi >= d.nfreq || sg >= nsg_pad || (int64_t)sg * group >= nsig) return;
     const int64_t s_begin = (int64_t)sg * group;
     const int64_t s_end = min(nsig, s_begin + group);
@@ -267,7 +185,7 @@ __global__ __launch_bounds__(N / E, (kWpsOf<T, E, OUT>)) void nw_fused_kernel(WD
     C2<T> nyq{T(0), T(0)};
     if constexpr (XD) {
         nyq = reinterpret_cast<const C2<T>*>(X + s_begin * d.nh)[N / 2];
-        const int nzv0 = pass0_variant<T, N, E, OUT>(max(1, wnz[fi] >> WSH));
+        const int nzv0 = pass0_variant<E, kNzFineOut<T, N, E, OUT>, kNz24Of<T, N, E>>(max(1, wnz[fi] >> WSH));
         dma_x<T, N, G::T>(reinterpret_cast<const C2<T>*>(X + s_begin * d.nh),
                           lds, t, nzv0 <= E / 2 ? dma_rounds_for<T>(nzv0) : 1 << 30);
     }
@@ -279,7 +197,7 @@ __global__ __launch_bounds__(N / E, (kWpsOf<T, E, OUT>)) void nw_fused_kernel(WD
     // LDS-DMA only the X bins the pruned pass 0 reads: variant NZ (>= 4) reads bins < NZ*T,
     // i.e. NZ/2 rounds of 2*T bins (fp32; NZ rounds of T bins in fp64), when it reads no
     // mirrored bin (NZ <= E/2)
-    const int nzv = pass0_variant<T, N, E, OUT>(nz);
+    const int nzv = pass0_variant<E, kNzFineOut<T, N, E, OUT>, kNz24Of<T, N, E>>(nz);
     static_assert(kPruneMin == 4, "the smallest pass-0 variant");
     const int dma_rounds = nzv <= E / 2 ? dma_rounds_for<T>(nzv) : 1 << 30;
     // power partial sums (kOutPSum): sum over the block's signals of |y|^2 per output point
@@ -392,15 +310,9 @@ __global__ __launch_bounds__(N / E, OUT == kOutPSum ? 3 : 4) void nw_fused_pair_
     extern __shared__ __align__(16) unsigned char smem[];
     f2* lds = reinterpret_cast<f2*>(smem);
     const int t = threadIdx.x;
-    // XCD-aware block -> (scale, signal group): as nw_fused_kernel
-    const int b = blockIdx.x;
-    const int xcd = b & 7;
-    const int local = b >> 3;
-    const int pos = local % (kTileF * tg);
-    const int round = local / (kTileF * tg);
-    const int nfr = (d.nfreq + kTileF - 1) / kTileF;
-    const int fi = (round % nfr) * kTileF + pos % kTileF;
-    const int sg = ((round / nfr) * tg + pos / kTileF) * 8 + xcd;
+    // XCD-aware block -> (scale, signal group): block_slot (nw_shape.h)
+    const BlockSlot slot = block_slot(blockIdx.x, d.nfreq, kTileF, tg);
+    const int fi = slot.row, sg = slot.group;
     if (fi >= d.nfreq || sg >= nsg_pad || (int64_t)sg * group >= nsig) return;
     const int64_t s_begin = (int64_t)sg * group;
     // the block's signal count, pinned in an SGPR: as an int64 min it sat in a VGPR pair that
@@ -580,11 +492,8 @@ __global__ __launch_bounds__(256) void wtable_kernel(WDesc d, void* wtab) {
 
 // Support of each W row for pass-0 pruning: wnz[f] >= the number of pass-0 elements r
 // (bins k = t + r*T, t < T) reaching the row's last bin above kTailRel x its max, i.e. elements
-// r >= wnz[f] see only the row's negligible tail for every thread (they run as zeros): the
-// next power of two up to 4, then the next multiple
-// of 4 (the pass-0 variants: NZ = 4, 8, 12, 16 at E = 16; 4, 8, 12, 16, 20, 24, 32 at E = 32
-// fp32; a multiple of 2^WSH, so nz >> WSH is exact for the partial-sum kernels' smaller E).
-// Rows pruned in steps of 4 elements: C3 1.205 -> 1.186 ms per launch (NZ = 12 at E = 16).
+// r >= wnz[f] see only the row's negligible tail for every thread (they run as zeros), rounded
+// up by wnz_round (nw_shape.h).
 // The support ends at the last bin above kTailRel x the row's max |W| (nw_internal.h).
 template <typename T, bool REALW>
 __global__ __launch_bounds__(256) void wsupport_kernel(const void* wtab, int64_t n, int tt, int e, int* wnz) {
@@ -616,10 +525,7 @@ __global__ __launch_bounds__(256) void wsupport_kernel(const void* wtab, int64_t
     }
     if (threadIdx.x == 0) {
         const int need = kmax[0] < 0 ? 1 : kmax[0] / tt + 1;   // elements 0 .. need-1 can be nonzero
-        int p2 = 1;
-        while (p2 < need && p2 < 8) p2 <<= 1;
-        if (p2 < need) p2 = (need + 3) / 4 * 4;
-        wnz[fi] = p2 < e ? p2 : e;
+        wnz[fi] = wnz_round(need, e);
     }
 }
 
@@ -675,117 +581,74 @@ hipError_t twiddles_for(int64_t n, int dtype, void** out) {
 template <typename T, int N, int E>
 hipError_t launch_forward(const void* x, void* X, int64_t nsig, int64_t nh, hipStream_t s) {
     void* tw = nullptr;
-    hipError_t e = twiddles_for(N, sizeof(T) == 4 ? NW_F32 : NW_F64, &tw);
-    if (e != hipSuccess) return e;
-    const int lds = kLdsBytes<T, N, E>;
-    e = hipFuncSetAttribute((const void*)fwd_r2c_kernel<T, N, E>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipError_t e = twiddles_for(N, kDtypeOf<T>, &tw);
     if (e != hipSuccess) return e;
     if (nsig > 0x7fffffff) return hipErrorInvalidConfiguration;
-    nw_launch(fwd_r2c_kernel<T, N, E>, (unsigned)nsig, N / E, lds, s, reinterpret_cast<const T*>(x), reinterpret_cast<C2<T>*>(X),
-                                                             reinterpret_cast<const C2<T>*>(tw), nh);
-    return hipGetLastError();
+    return nw_launch_lds(fwd_r2c_kernel<T, N, E>, (unsigned)nsig, N / E, kLdsBytes<T, N, E>, s,
+                         reinterpret_cast<const T*>(x), reinterpret_cast<C2<T>*>(X), reinterpret_cast<const C2<T>*>(tw), nh);
 }
 
-// bytes of the W rows in the table buffer (the wnz[nfreq] support array follows them)
-size_t wtab_row_bytes(int64_t n, int nfreq, size_t esz, bool realw) {
-    const size_t b = (size_t)n * nfreq * esz * (realw ? 1 : 2);
-    return (b + 15) / 16 * 16;
-}
-
-template <typename T, int E, bool REALW>
-constexpr bool kPairMode = std::is_same<T, float>::value && E <= 16 && REALW;
-
-// Signals per block of the output kernels: `base`, halved (to 2) while a launch would fill the
-// chip fewer than kMinRounds times over (512 resident 512-thread blocks): a small launch (C2:
-// 64 signals x 128 scales = 1024 blocks of 8, two rounds) otherwise ends on a tail of long
-// blocks.  NW_FUSED_GROUP=<g> fixes it (diagnostic A/B).
-constexpr int64_t kMinRounds = 4, kResidentBlocks = 512;
+// NW_FUSED_GROUP=<g> fixes the signals per block of the output kernels (diagnostic A/B)
 int group_for(int base, int64_t nsig, int nfreq) {
     static const int fixed = [] {
         const char* v = std::getenv("NW_FUSED_GROUP");
         return v ? std::atoi(v) : 0;
     }();
-    if (fixed > 0) return fixed;
-    int g = base;
-    while (g > 2 && (nsig + g - 1) / g * (int64_t)nfreq < kMinRounds * kResidentBlocks) g /= 2;
-    return g;
+    return fixed > 0 ? fixed : group_filling(base, nsig, nfreq);
 }
 
+// the grid of nsig signals in blocks of `group` x nfreq scales, in XCD tiles of tile_f x (up to) tg_max
+bool shape_for(int e, int group, int tile_f, int tg_max, int64_t nsig, int nfreq, FusedShape* sh) {
+    const BlockGrid g = block_grid((nsig + group - 1) / group, nfreq, tile_f, tg_max);
+    *sh = FusedShape{e, group, tile_f, g.tile_g, g.groups_pad, g.blocks};
+    return g.ok;
+}
+// ... of an output launch: the signal-pair kernel keeps kGroup signals per block
+template <typename T, int N, int E>
+bool output_shape(bool pair, int64_t nsig, int nfreq, FusedShape* sh) {
+    return shape_for(E, pair ? kGroup : group_for(kGroupOut<T, N>, nsig, nfreq), kTileFT<T>, kTileGOut<T, N>, nsig,
+                     nfreq, sh);
+}
+
+// (no hipFuncSetAttribute here: the output kernels' LDS sizes are set with the plan, prepare_one)
 template <typename T, int N, int E, bool REALW>
 hipError_t launch_n(const WDesc& d, int out_kind, const void* X, const void* wtab, void* out, int64_t nsig,
                     hipStream_t s) {
-    constexpr int threads = N / E;
-    const size_t lds = (size_t)kLdsBytes<T, N, E>;
+    constexpr bool PAIR = kPairMode<T, E, REALW>;
     void* tw = nullptr;
-    hipError_t e = twiddles_for(N, sizeof(T) == 4 ? NW_F32 : NW_F64, &tw);
+    hipError_t e = twiddles_for(N, kDtypeOf<T>, &tw);
     if (e != hipSuccess) return e;
-    const int grp = kPairMode<T, E, REALW> ? kGroup : group_for(kGroupOut<T, N>, nsig, d.nfreq);
-    const int64_t nsg = (nsig + grp - 1) / grp;
-    constexpr int TF = kTileFT<T>;
-    const int TG = tile_g_of(nsg, kTileGOut<T, N>);
-    const int64_t nsg_pad = (nsg + 8 * TG - 1) / (8 * TG) * (8 * TG);
-    const int64_t nfr = (d.nfreq + TF - 1) / TF;
-    const int64_t blocks = nsg_pad * nfr * TF;
-    if (blocks > 0x7fffffff || nsg_pad > 0x7fffffff) return hipErrorInvalidConfiguration;
-    const cplx<T>* Xc = reinterpret_cast<const cplx<T>*>(X);
-    const C2<T>* twc_ = reinterpret_cast<const C2<T>*>(tw);
-    const int* wnz = reinterpret_cast<const int*>(reinterpret_cast<const char*>(wtab) +
-                                                  wtab_row_bytes(N, d.nfreq, sizeof(T), REALW));
-    if constexpr (kPairMode<T, E, REALW>) {
-        const size_t lp = (size_t)kLdsBytes<f2, N, E>;
-        const C2<float>* twf = reinterpret_cast<const C2<float>*>(tw);
-        const cplx<float>* Xf = reinterpret_cast<const cplx<float>*>(X);
-        if (out_kind == NW_OUT_CWT)
-            nw_launch(nw_fused_pair_kernel<N, E, NW_OUT_CWT>, blocks, threads, lp, s, d, Xf, wtab, out, twf, nsig, kGroup, (int)nsg_pad, wnz, TG);
-        else if (out_kind == NW_OUT_POWER)
-            nw_launch(nw_fused_pair_kernel<N, E, NW_OUT_POWER>, blocks, threads, lp, s, d, Xf, wtab, out, twf, nsig, kGroup, (int)nsg_pad, wnz, TG);
-        else
-            nw_launch(nw_fused_pair_kernel<N, E, NW_OUT_ABS>, blocks, threads, lp, s, d, Xf, wtab, out, twf, nsig, kGroup, (int)nsg_pad, wnz, TG);
-        return hipGetLastError();
-    }
-    if (out_kind == NW_OUT_CWT)
-        nw_launch(nw_fused_kernel<T, N, E, NW_OUT_CWT, REALW>, blocks, threads, lds, s, d, Xc, wtab, out, twc_, nsig, grp, (int)nsg_pad, wnz, TG);
-    else if (out_kind == NW_OUT_POWER)
-        nw_launch(nw_fused_kernel<T, N, E, NW_OUT_POWER, REALW>, blocks, threads, lds, s, d, Xc, wtab, out, twc_, nsig, grp, (int)nsg_pad, wnz, TG);
-    else
-        nw_launch(nw_fused_kernel<T, N, E, NW_OUT_ABS, REALW>, blocks, threads, lds, s, d, Xc, wtab, out, twc_, nsig, grp, (int)nsg_pad, wnz, TG);
-    return hipGetLastError();
+    FusedShape sh{};
+    if (!output_shape<T, N, E>(PAIR, nsig, d.nfreq, &sh)) return hipErrorInvalidConfiguration;
+    const int* wnz = wtab_wnz(wtab, N, d.nfreq, sizeof(T), REALW);
+    return for_out_kind(out_kind, [&](auto o) {
+        constexpr int OUT = decltype(o)::value;
+        auto go = [&](auto kernel, size_t lds) {
+            nw_launch(kernel, (unsigned)sh.blocks, N / E, lds, s, d, reinterpret_cast<const cplx<T>*>(X), wtab, out,
+                      reinterpret_cast<const C2<T>*>(tw), nsig, sh.group, (int)sh.nsg_pad, wnz, sh.tile_g);
+            return hipGetLastError();
+        };
+        if constexpr (PAIR) return go(nw_fused_pair_kernel<N, E, OUT>, (size_t)kLdsBytes<f2, N, E>);
+        else return go(nw_fused_kernel<T, N, E, OUT, REALW>, (size_t)kLdsBytes<T, N, E>);
+    });
 }
 
 template <typename T, int N, int E, int OUT, int WSH>
 hipError_t launch_psum(const WDesc& d, const void* X, const void* wtab, void* partials, int64_t nsig, hipStream_t s) {
-    constexpr int threads = N / E;
-    const int lds = kLdsBytes<T, N, E>;
     void* tw = nullptr;
-    hipError_t e = twiddles_for(N, sizeof(T) == 4 ? NW_F32 : NW_F64, &tw);
+    hipError_t e = twiddles_for(N, kDtypeOf<T>, &tw);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)nw_fused_kernel<T, N, E, OUT, true, WSH>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    const int64_t nsg = (nsig + kGroup - 1) / kGroup;
-    constexpr int TF = kTileFT<T>;
-    const int TG = tile_g_of(nsg, kTileGT<T>);
-    const int64_t nsg_pad = (nsg + 8 * TG - 1) / (8 * TG) * (8 * TG);
-    const int64_t nfr = (d.nfreq + TF - 1) / TF;
-    const int64_t blocks = nsg_pad * nfr * TF;
-    if (blocks > 0x7fffffff || nsg_pad > 0x7fffffff) return hipErrorInvalidConfiguration;
-    const int* wnz = reinterpret_cast<const int*>(reinterpret_cast<const char*>(wtab) +
-                                                  wtab_row_bytes(N, d.nfreq, sizeof(T), true));
-    if constexpr (OUT == kOutPSum && kPairMode<T, E, true>) {
-        // power partials on the signal-pair kernel: the same values as its power output
-        const int lp = kLdsBytes<f2, N, E>;
-        e = hipFuncSetAttribute((const void*)nw_fused_pair_kernel<N, E, kOutPSum>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lp);
-        if (e != hipSuccess) return e;
-        nw_launch(nw_fused_pair_kernel<N, E, kOutPSum>, blocks, threads, lp, s, 
-            d, reinterpret_cast<const cplx<float>*>(X), wtab, partials, reinterpret_cast<const C2<float>*>(tw), nsig,
-            kGroup, (int)nsg_pad, wnz, TG);
-        return hipGetLastError();
-    }
-    nw_launch(nw_fused_kernel<T, N, E, OUT, true, WSH>, blocks, threads, lds, s, 
-        d, reinterpret_cast<const cplx<T>*>(X), wtab, partials, reinterpret_cast<const C2<T>*>(tw), nsig, kGroup,
-        (int)nsg_pad, wnz, TG);
-    return hipGetLastError();
+    FusedShape sh{};
+    if (!shape_for(E, kGroup, kTileFT<T>, kTileGT<T>, nsig, d.nfreq, &sh)) return hipErrorInvalidConfiguration;
+    const int* wnz = wtab_wnz(wtab, N, d.nfreq, sizeof(T), true);
+    auto go = [&](auto kernel, int lds) {
+        return nw_launch_lds(kernel, (unsigned)sh.blocks, N / E, lds, s, d, reinterpret_cast<const cplx<T>*>(X), wtab,
+                             partials, reinterpret_cast<const C2<T>*>(tw), nsig, kGroup, (int)sh.nsg_pad, wnz,
+                             sh.tile_g);
+    };
+    // power partials on the signal-pair kernel: the same values as its power output
+    if constexpr (OUT == kOutPSum && kPairMode<T, E, true>) return go(nw_fused_pair_kernel<N, E, kOutPSum>, kLdsBytes<f2, N, E>);
+    else return go(nw_fused_kernel<T, N, E, OUT, true, WSH>, kLdsBytes<T, N, E>);
 }
 
 template <typename T, int N, int E, bool REALW>
@@ -819,36 +682,20 @@ hipError_t prepare_n() {
     hipError_t e = prepare_one<T, N, E, true>();
     if (e == hipSuccess) e = prepare_one<T, N, E, false>();
     void* tw = nullptr;
-    if (e == hipSuccess) e = twiddles_for(N, sizeof(T) == 4 ? NW_F32 : NW_F64, &tw);
+    if (e == hipSuccess) e = twiddles_for(N, kDtypeOf<T>, &tw);
     return e;
 }
 
 }  // namespace
 
+// The public entry points take (n, dtype) at run time: for_fused_size (nw_shape.h) finds the
+// table's row and hands its <T, N, E> to the lambda.
+
 hipError_t fused_twiddles(int64_t n, int dtype, void** out) { return twiddles_for(n, dtype, out); }
 
-// power-of-two n: 2^10..2^14 in fp32 and fp64 (fp64 at 8192 / 16384: E = 32 with 256 VGPRs,
-// W re-read per signal)
-bool fused_supported(int64_t n, int dtype) {
-    if (n < 1024 || (n & (n - 1))) return false;
-    return (dtype == NW_F32 || dtype == NW_F64) && n <= 16384;
-}
-
-// Elements per thread E of each fused size (threads = n / E).  Measured: fp32 n = 4096 at
-// E = 32 slower (0.350 -> 0.404 ms power); n = 8192 at E = 32 vs 16: power 0.887 -> 0.768 ms,
-// cwt 1.034 -> 0.926; fp64 at n >= 8192: E = 32 (3 passes, 256 VGPRs, 2 waves/SIMD) vs E = 16
-// (4 passes): 8192 cwt 2.907 -> 2.573 ms, power 2.397 -> 1.991; 16384 cwt 3.447 -> 3.124,
-// power 2.615 -> 2.312 (256 x 256 rows; 128 x 256 at 16384).
-#define NW_FUSED_TABLE(X)                                                               \
-    X(float, 1024, 16) X(float, 2048, 16) X(float, 4096, 16) X(float, 8192, 32) X(float, 16384, 32) \
-    X(double, 1024, 16) X(double, 2048, 16) X(double, 4096, 16) X(double, 8192, 32) X(double, 16384, 32)
-
 hipError_t fused_prepare(int64_t n, int dtype) {
-#define NW_PREP(TY, NN, EE) \
-    if (n == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64)) return prepare_n<TY, NN, EE>();
-    NW_FUSED_TABLE(NW_PREP)
-#undef NW_PREP
-    return hipErrorNotSupported;
+    return for_fused_size(n, dtype, hipErrorNotSupported,
+                          []<typename T, int N, int E>(FusedSize<T, N, E>) { return prepare_n<T, N, E>(); });
 }
 
 size_t fused_wtable_bytes(int64_t n, int nfreq, int dtype, int kind) {
@@ -860,12 +707,8 @@ hipError_t build_wtable(const WDesc& d, int dtype, void* wtab, hipStream_t s) {
     dim3 grid((unsigned)((d.n + 255) / 256), (unsigned)d.nfreq);
     const bool realw = d.kind != NW_TABLE;
     const size_t esz = dtype == NW_F32 ? sizeof(float) : sizeof(double);
-    int* wnz = reinterpret_cast<int*>(reinterpret_cast<char*>(wtab) + wtab_row_bytes(d.n, d.nfreq, esz, realw));
-    int e = 0;
-#define NW_E_OF(TY, NN, EE) \
-    if (d.n == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64)) e = EE;
-    NW_FUSED_TABLE(NW_E_OF)
-#undef NW_E_OF
+    int* wnz = const_cast<int*>(wtab_wnz(wtab, d.n, d.nfreq, esz, realw));
+    const int e = fused_e(d.n, dtype);
     if (e == 0) return hipErrorNotSupported;
     const int tt = (int)(d.n / e);
     if (dtype == NW_F32) {
@@ -882,114 +725,63 @@ hipError_t build_wtable(const WDesc& d, int dtype, void* wtab, hipStream_t s) {
     return hipGetLastError();
 }
 
-// epoch power / phase partials: analytic rows; fp32 power to E = 32, fp32 phases and fp64 at E = 16
-// Elements per thread of the partial-sum kernels (EO: the output kernels'): fp32 power keeps
-// EO (E = 32 at n = 8192 / 16384: E fp64 accumulators at 2 waves/SIMD); fp32 phases (2E fp64
-// accumulators) and fp64 (the drop-in's default dtype, 2 waves/SIMD already at 256 VGPRs)
-// run at E = 16 -- n = 8192 / 16384 then take 512 / 1024 threads, the W-support table
-// shifted by log2(EO / 16) (nw_fused_kernel's WSH)
-template <typename T, int EO, bool PHASE>
-constexpr int kPsE = (EO >= 32 && (PHASE || sizeof(T) == 8)) ? 16 : EO;
-template <int EO, int E> constexpr int kPsShift = EO == E ? 0 : EO == 2 * E ? 1 : 2;
-// combinations whose accumulators fit without spilling (tools/regs.py): at 1024 threads
-// (n = 16384, E = 16) a wave has 128 VGPRs, and neither fp64 power (228 B of scratch) nor
-// phases (fp32: 84 B) fit there -- n = 16384 keeps the chunk path for those
-template <typename T, int N, int EO>
-constexpr bool kPSumOK = !(sizeof(T) == 8 && N / kPsE<T, EO, false> > 512);
-template <typename T, int N, int EO>
-constexpr bool kPhSumOK = N / kPsE<T, EO, true> <= 512;
-
 bool fused_psum_supported(int64_t n, int dtype, int kind, bool phase) {
     if (kind == NW_TABLE) return false;
-#define NW_PS(TY, NN, EE) \
-    if (n == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64)) return phase ? kPhSumOK<TY, NN, EE> : kPSumOK<TY, NN, EE>;
-    NW_FUSED_TABLE(NW_PS)
-#undef NW_PS
-    return false;
+    return for_fused_size(n, dtype, false, [&]<typename T, int N, int E>(FusedSize<T, N, E>) {
+        return phase ? kPhSumOK<T, N, E> : kPSumOK<T, N, E>;
+    });
 }
 
 int64_t fused_psum_groups(int64_t nsig) { return (nsig + kGroup - 1) / kGroup; }
 
 int fused_psum_kernel_id(int64_t n, int dtype, bool phase) {
-#define NW_PK_ID(TY, NN, EE) \
-    if (n == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64)) \
-        return (!phase && kPairMode<TY, EE, true>) ? NW_K_FUSED_PAIR : NW_K_FUSED;
-    NW_FUSED_TABLE(NW_PK_ID)
-#undef NW_PK_ID
-    return NW_K_NONE;
+    return for_fused_size(n, dtype, NW_K_NONE, [&]<typename T, int N, int E>(FusedSize<T, N, E>) {
+        return (!phase && kPairMode<T, E, true>) ? NW_K_FUSED_PAIR : NW_K_FUSED;
+    });
 }
 
 hipError_t fused_power_partials(const WDesc& d, int dtype, bool phase, const void* X, const void* wtab,
                                 void* partials, int64_t nsig, hipStream_t s) {
-#define NW_PSL(TY, NN, EE)                                                                                    \
-    if (d.n == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64)) {                                          \
-        if constexpr (kPhSumOK<TY, NN, EE>) {                                                                 \
-            constexpr int PE = kPsE<TY, EE, true>;                                                            \
-            if (phase) return launch_psum<TY, NN, PE, kOutPhSum, kPsShift<EE, PE>>(d, X, wtab, partials, nsig, s); \
-        }                                                                                                     \
-        if constexpr (kPSumOK<TY, NN, EE>) {                                                                  \
-            constexpr int PE = kPsE<TY, EE, false>;                                                           \
-            if (!phase) return launch_psum<TY, NN, PE, kOutPSum, kPsShift<EE, PE>>(d, X, wtab, partials, nsig, s); \
-        }                                                                                                     \
-        return hipErrorNotSupported;                                                                          \
-    }
-    NW_FUSED_TABLE(NW_PSL)
-#undef NW_PSL
-    return hipErrorNotSupported;
+    return for_fused_size(d.n, dtype, hipErrorNotSupported, [&]<typename T, int N, int E>(FusedSize<T, N, E>) {
+        if constexpr (kPhSumOK<T, N, E>) {
+            constexpr int PE = kPsE<T, E, true>;
+            if (phase) return launch_psum<T, N, PE, kOutPhSum, kPsShift<E, PE>>(d, X, wtab, partials, nsig, s);
+        }
+        if constexpr (kPSumOK<T, N, E>) {
+            constexpr int PE = kPsE<T, E, false>;
+            if (!phase) return launch_psum<T, N, PE, kOutPSum, kPsShift<E, PE>>(d, X, wtab, partials, nsig, s);
+        }
+        return hipErrorNotSupported;
+    });
 }
 
 hipError_t fused_forward(int64_t n, int dtype, const void* x, void* X, int64_t nsig, int64_t nh, hipStream_t s) {
-#define NW_FWD(TY, NN, EE) \
-    if (n == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64)) return launch_forward<TY, NN, EE>(x, X, nsig, nh, s);
-    NW_FUSED_TABLE(NW_FWD)
-#undef NW_FWD
-    return hipErrorNotSupported;
+    return for_fused_size(n, dtype, hipErrorNotSupported, [&]<typename T, int N, int E>(FusedSize<T, N, E>) {
+        return launch_forward<T, N, E>(x, X, nsig, nh, s);
+    });
 }
 
 int fused_kernel_id(int64_t n, int dtype, int kind) {
     const bool realw = kind != NW_TABLE;
-#define NW_KID(TY, NN, EE)                                                                      \
-    if (n == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64))                                \
-        return (realw ? kPairMode<TY, EE, true> : kPairMode<TY, EE, false>) ? NW_K_FUSED_PAIR : NW_K_FUSED;
-    NW_FUSED_TABLE(NW_KID)
-#undef NW_KID
-    return NW_K_NONE;
+    return for_fused_size(n, dtype, NW_K_NONE, [&]<typename T, int N, int E>(FusedSize<T, N, E>) {
+        return (realw ? kPairMode<T, E, true> : kPairMode<T, E, false>) ? NW_K_FUSED_PAIR : NW_K_FUSED;
+    });
 }
 
 // launch_n's grid for the single-signal output kernel (the decimated kernel maps its blocks alike)
 bool fused_shape(int64_t n, int dtype, int64_t nsig, int nfreq, FusedShape* sh) {
-#define NW_SHAPE(TY, NN, EE)                                                   \
-    if (n == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64)) {             \
-        sh->e = EE;                                                            \
-        sh->group = group_for(kGroupOut<TY, NN>, nsig, nfreq);                 \
-        sh->tile_f = kTileFT<TY>;                                              \
-        const int64_t nsg = (nsig + sh->group - 1) / sh->group;                \
-        sh->tile_g = tile_g_of(nsg, kTileGOut<TY, NN>);                        \
-        sh->nsg_pad = (nsg + 8 * sh->tile_g - 1) / (8 * sh->tile_g) * (8 * sh->tile_g); \
-        sh->blocks = sh->nsg_pad * ((nfreq + sh->tile_f - 1) / sh->tile_f) * sh->tile_f; \
-        return sh->blocks <= 0x7fffffff && sh->nsg_pad <= 0x7fffffff;          \
-    }
-    NW_FUSED_TABLE(NW_SHAPE)
-#undef NW_SHAPE
-    return false;
-}
-
-const int* fused_wnz(const void* wtab, int64_t n, int nfreq, int dtype, int kind) {
-    const size_t esz = dtype == NW_F32 ? sizeof(float) : sizeof(double);
-    return reinterpret_cast<const int*>(reinterpret_cast<const char*>(wtab) +
-                                        wtab_row_bytes(n, nfreq, esz, kind != NW_TABLE));
+    return for_fused_size(n, dtype, false, [&]<typename T, int N, int E>(FusedSize<T, N, E>) {
+        return output_shape<T, N, E>(false, nsig, nfreq, sh);
+    });
 }
 
 hipError_t launch_fused(const WDesc& d, int dtype, int out_kind, const void* X, const void* wtab, void* out,
                         int64_t nsig, hipStream_t s) {
     const bool realw = d.kind != NW_TABLE;
-#define NW_LAUNCH(TY, NN, EE)                                                                 \
-    if (d.n == NN && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64))                            \
-        return realw ? launch_n<TY, NN, EE, true>(d, out_kind, X, wtab, out, nsig, s)         \
-                     : launch_n<TY, NN, EE, false>(d, out_kind, X, wtab, out, nsig, s);
-    NW_FUSED_TABLE(NW_LAUNCH)
-#undef NW_LAUNCH
-    return hipErrorNotSupported;
+    return for_fused_size(d.n, dtype, hipErrorNotSupported, [&]<typename T, int N, int E>(FusedSize<T, N, E>) {
+        return realw ? launch_n<T, N, E, true>(d, out_kind, X, wtab, out, nsig, s)
+                     : launch_n<T, N, E, false>(d, out_kind, X, wtab, out, nsig, s);
+    });
 }
 
 }  // namespace nw

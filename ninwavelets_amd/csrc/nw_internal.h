@@ -9,6 +9,7 @@
 
 #include "../../include/ninwave.h"
 #include "nw_host.h"
+#include "nw_shape.h"
 
 namespace nw {
 
@@ -70,6 +71,22 @@ inline void nw_launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s
     } else {
         hipLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, s, args...);
     }
+}
+// ... of a kernel whose dynamic LDS size is set at every launch (the attribute is per device;
+// the one-pass output kernels have it set with the plan instead, fused_prepare)
+template <typename K, typename... Args>
+inline hipError_t nw_launch_lds(K kernel, dim3 grid, dim3 block, int lds, hipStream_t s, Args... args) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+    nw_launch(kernel, grid, block, (size_t)lds, s, args...);
+    return hipGetLastError();
+}
+// f(std::integral_constant<int, OUT>) for the output kind of a launch (|y| for any other value)
+template <typename F>
+inline hipError_t for_out_kind(int out_kind, F f) {
+    if (out_kind == NW_OUT_CWT) return f(std::integral_constant<int, NW_OUT_CWT>{});
+    if (out_kind == NW_OUT_POWER) return f(std::integral_constant<int, NW_OUT_POWER>{});
+    return f(std::integral_constant<int, NW_OUT_ABS>{});
 }
 
 // ---------------------------------------------------------------------------
@@ -227,8 +244,7 @@ hipError_t launch_wavelet_time(const WaveRow* rows, int nrows, int64_t maxlen, W
 constexpr int BL_WORK_DOUBLES = 1024 + 2;   // k_bl_partial blocks + (mean, std)
 hipError_t launch_baseline(int dtype, const void* x, int64_t count, int64_t b0, int64_t b1, int op, void* out,
                            double* work, hipStream_t s);
-// fused engine (nw_fused.hip)
-bool       fused_supported(int64_t n, int dtype);
+// fused engine (nw_fused.hip; fused_supported and the rest of its launch geometry: nw_shape.h)
 hipError_t fused_prepare(int64_t n, int dtype);
 size_t     fused_wtable_bytes(int64_t n, int nfreq, int dtype, int kind);
 hipError_t build_wtable(const WDesc& d, int dtype, void* wtab, hipStream_t s);
@@ -239,17 +255,16 @@ int        fused_kernel_id(int64_t n, int dtype, int kind);   // NW_K_FUSED or N
 hipError_t fused_forward(int64_t n, int dtype, const void* x, void* X, int64_t nsig, int64_t nh, hipStream_t s);
 hipError_t fused_twiddles(int64_t n, int dtype, void** out);   // exact exp(+2 pi i j / n), cached per device
 // The block shape of an output launch of nw_fused_kernel at length n (its elements per thread,
-// signals per block, XCD tile and padded grid), and the W-support array behind the rows of a
-// table built by build_wtable: what the decimated kernel (nw_decim.hip) shares with it
+// signals per block, XCD tile and padded grid): what the decimated kernel (nw_decim.hip) shares
+// with it
 struct FusedShape {
     int e, group, tile_f, tile_g;
     int64_t nsg_pad, blocks;
 };
 bool       fused_shape(int64_t n, int dtype, int64_t nsig, int nfreq, FusedShape* sh);
-const int* fused_wnz(const void* wtab, int64_t n, int nfreq, int dtype, int kind);
-// decimated one-pass form (nw_decim.hip): every decim-th output sample of a fused length as the
-// (n / decim)-point inverse transform of the folded product; out rows are n / decim long
-bool       decim_supported(int64_t n, int dtype, int decim);
+// decimated one-pass form (nw_decim.hip; decim_supported: nw_shape.h): every decim-th output
+// sample of a fused length as the (n / decim)-point inverse transform of the folded product; out
+// rows are n / decim long
 hipError_t launch_fused_decim(const WDesc& d, int dtype, int out_kind, int decim, const void* X, const void* wtab,
                               void* out, int64_t nsig, hipStream_t s);
 // epoch reduction partials (fused sizes, fp32 analytic rows; power up to E = 32, phase
@@ -257,10 +272,7 @@ hipError_t launch_fused_decim(const WDesc& d, int dtype, int out_kind, int decim
 // or with phase of y / |y|; one
 // (groups, F, n) row of fp64 (phase: complex fp64) per (group, scale);
 // groups = fused_psum_groups(nsig)
-// Signals per partial-sum row: the block size of both the fused kernels (kGroup) and the
-// chirp-z kernel (kGroupC), each static_assert'ed equal to it, so one fused_psum_groups sizes
-// and accumulates the partial rows of either form
-constexpr int kPsumGroup = 8;
+// (kPsumGroup signals per row, nw_shape.h)
 
 // W support for the pruned pass 0 / row pass (wsupport_kernel, kmax_kernel): the last bin
 // whose |W| exceeds kTailRel x the row's max |W|.  The bins past it (the far tail of a Morse

@@ -51,8 +51,7 @@ namespace nw {
 namespace {
 
 constexpr int kRowGroup = 4;      // rows (k1) per rows_kernel workgroup (1 when a launch holds few scales)
-constexpr int kRowTileF = 8;      // scales per XCD tile
-constexpr int kRowTileG = 8;      // row groups per XCD tile
+// (XCD tile kRowTileF x kRowTileG: nw_shape.h)
 // cols_kernel workgroups of 1024 threads: C = 32 columns at N1 = 1024, 256-B runs (C5 cols
 // 1.039 -> 0.978 ms per launch against 512 threads)
 // cols_kernel workgroup size (C * N1 / E)
@@ -595,17 +594,11 @@ __global__ __launch_bounds__(N2 / E, sizeof(T) == 8 ? 2 : 4) void rows_kernel(
     T* lds = reinterpret_cast<T*>(smem);
     const int t = threadIdx.x;
 
-    // XCD-aware block -> (scale, row group), as nw_fused_kernel: blocks b, b+8, ... share
+    // XCD-aware block -> (scale, row group), block_slot (nw_shape.h): blocks b, b+8, ... share
     // an XCD, whose resident blocks cover kRowTileF scales x kRowTileG row groups, so each
     // Xt row group is read from HBM once per tile and then from that XCD's L2
-    const int b = blockIdx.x;
-    const int xcd = b & 7;
-    const int local = b >> 3;
-    const int pos = local % (kRowTileF * kRowTileG);
-    const int round = local / (kRowTileF * kRowTileG);
-    const int nfr = (nf + kRowTileF - 1) / kRowTileF;
-    const int fl = (round % nfr) * kRowTileF + pos % kRowTileF;
-    const int rg = ((round / nfr) * kRowTileG + pos / kRowTileF) * 8 + xcd;
+    const BlockSlot slot = block_slot(blockIdx.x, nf, kRowTileF, kRowTileG);
+    const int fl = slot.row, rg = slot.group;
     const int ngroups = n1 / rgs;
     if (fl >= nf || rg >= ngroups) return;
     const int fi = f0 + fl;
@@ -1091,17 +1084,11 @@ hipError_t launch_row_pass(const WDesc& d, int f0, int nf, int n1, const C2<T>* 
     void* tw = nullptr;
     hipError_t e = fused_twiddles(N2, sizeof(T) == 4 ? NW_F32 : NW_F64, &tw);
     if (e != hipSuccess) return e;
-    const int lds = kLdsBytes<T, N2, E>;
-    e = hipFuncSetAttribute((const void*)rows_kernel<T, N2, E, KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
     const int rgs = nf < kRowTileF ? 1 : kRowGroup;   // few scales: one row per block, more blocks
-    const int ngroups = n1 / rgs;
-    const int gpad = (ngroups + 8 * kRowTileG - 1) / (8 * kRowTileG) * (8 * kRowTileG);
-    const int nfr = (nf + kRowTileF - 1) / kRowTileF;
-    const int64_t blocks = (int64_t)gpad * nfr * kRowTileF;
-    nw_launch(rows_kernel<T, N2, E, KIND>, (unsigned)blocks, N2 / E, lds, s, d, f0, nf, n1, rgs, Xt, B, kmax,
-                                                                       reinterpret_cast<const C2<T>*>(tw));
-    return hipGetLastError();
+    const BlockGrid g = block_grid_tile(n1 / rgs, nf, kRowTileF, kRowTileG);
+    if (!g.ok) return hipErrorInvalidConfiguration;
+    return nw_launch_lds(rows_kernel<T, N2, E, KIND>, (unsigned)g.blocks, N2 / E, kLdsBytes<T, N2, E>, s, d, f0, nf, n1,
+                         rgs, Xt, B, kmax, reinterpret_cast<const C2<T>*>(tw));
 }
 
 // fp32: the column-pair kernel (C5 cols 4.02 -> 3.86 ms per 64-scale launch against the

@@ -1,9 +1,14 @@
 // CPU driver for the sanitizer build of the engine's host-only logic (nw_host.cpp):
 // built with -fsanitize=address,undefined by tests/test_host_asan.py.
 //   host_asan self      : invariant checks of group_rows / block_of / parallel_copy / advise_output /
-//                         normal_rows / row_view_layout / stock_params
+//                         normal_rows / row_view_layout / stock_params, and of the kernels' launch
+//                         geometry (nw_shape.h): grid <-> block mapping, size table, limits
 //   host_asan grid      : stdin "real_length sfreq interpolate" -> "len_valid len_full delta"
+//   host_asan shapes    : the size table's rules (E, pass-0 ladders, support rounding, partial
+//                         sums, decimated lengths), one line each
+#include <algorithm>
 #include <cmath>
+#include <iterator>
 #include <cstdio>
 #include <functional>
 #include <cstdlib>
@@ -14,6 +19,7 @@
 
 #include "../../include/ninwave.h"
 #include "../../ninwavelets_amd/csrc/nw_host.h"
+#include "../../ninwavelets_amd/csrc/nw_shape.h"
 
 using namespace nw::host;
 
@@ -188,8 +194,128 @@ static void self_checks() {
     }
 }
 
+// ---- the launch geometry (nw_shape.h): what the kernels and their launchers compile
+
+// block_slot restricted to the valid slots of grid g is a bijection onto nrows x groups_pad (so
+// onto nrows x groups): every (row, group) is computed by exactly one block
+static void check_grid(const nw::BlockGrid& g, int64_t groups, int nrows, int tile_f) {
+    CHECK(g.ok && g.tile_g >= 1 && g.groups_pad >= groups && g.groups_pad < groups + 8 * g.tile_g);
+    CHECK(g.blocks % (8 * tile_f * g.tile_g) == 0);
+    std::vector<int> hit((size_t)nrows * (size_t)g.groups_pad, 0);
+    for (int64_t b = 0; b < g.blocks; ++b) {
+        const nw::BlockSlot sl = nw::block_slot((int)b, nrows, tile_f, g.tile_g);
+        CHECK(sl.row >= 0 && sl.group >= 0 && sl.group < g.groups_pad);
+        if (sl.row >= 0 && sl.row < nrows && sl.group >= 0 && sl.group < g.groups_pad)
+            hit[(size_t)sl.row * (size_t)g.groups_pad + (size_t)sl.group]++;
+    }
+    for (int h : hit) CHECK(h == 1);
+}
+
+static void shape_checks() {
+    using namespace nw;
+    for (int nrows : {1, 2, 7, 8, 9, 64, 129})
+        for (int64_t groups : {1, 2, 7, 8, 9, 31, 32, 33, 65}) {
+            for (int tg_max : {1, 2, 4}) {
+                const BlockGrid g = block_grid(groups, nrows, kTileF, tg_max);
+                CHECK(g.tile_g == std::min<int64_t>(tg_max, (groups + 7) / 8) && g.tile_g == tile_g_of(groups, tg_max));
+                check_grid(g, groups, nrows, kTileF);
+            }
+            check_grid(block_grid_tile(groups, nrows, kTileFC, kTileGC), groups, nrows, kTileFC);       // chirp-z
+            check_grid(block_grid_tile(groups, nrows, kRowTileF, kRowTileG), groups, nrows, kRowTileF);  // two-pass rows
+        }
+    // the 2^31 refusal at the first size that needs it: 8 rows x 2^28 padded groups = 2^31 blocks
+    CHECK(block_grid(0, 1, 8, 4).ok && block_grid(0, 1, 8, 4).blocks == 0);
+    for (int tg_max : {1, 2, 4}) {
+        const int64_t last = (int64_t(1) << 28) - 8 * tg_max;   // the last whole tile below 2^28 groups
+        const BlockGrid fits = block_grid(last, 8, 8, tg_max), over = block_grid(last + 1, 8, 8, tg_max);
+        CHECK(fits.ok && fits.blocks == (int64_t(1) << 31) - 64 * tg_max);
+        CHECK(!over.ok && over.blocks == int64_t(1) << 31);
+        CHECK(block_grid(last, 9, 8, tg_max).ok == false);     // one more row tile
+        CHECK(!block_grid_tile(int64_t(1) << 31, 1, 1, 1).ok && block_grid_tile((int64_t(1) << 31) - 8, 1, 1, 1).ok);
+    }
+    // the size table: powers of two 2^10 .. 2^14, both compute dtypes, and nothing else
+    for (int dtype : {NW_F32, NW_F64, 7})
+        for (int64_t n = 1; n <= 40000; ++n) {
+            const bool in = dtype != 7 && n >= 1024 && n <= 16384 && (n & (n - 1)) == 0;
+            CHECK(fused_supported(n, dtype) == in && fused_e(n, dtype) == (in ? (n <= 4096 ? 16 : 32) : 0));
+            const int seen = for_fused_size(n, dtype, -1, []<typename T, int N, int E>(FusedSize<T, N, E>) {
+                return (int)sizeof(T) * 100000 + N / E;
+            });
+            CHECK(seen == (in ? (dtype == NW_F32 ? 4 : 8) * 100000 + (int)n / fused_e(n, dtype) : -1));
+        }
+    // group_filling halves down to 2 and never below; the W-support array follows 16-byte padded rows
+    for (int base : {8, 16})
+        for (int64_t nsig : {1, 7, 64, 256, 4096}) {
+            const int g = group_filling(base, nsig, 128);
+            CHECK(g >= 2 && g <= base && base % g == 0);
+            CHECK(g == base || (nsig + g - 1) / g * 128 >= kMinRounds * kResidentBlocks || g == 2);
+        }
+    alignas(16) static char buf[64];
+    CHECK(reinterpret_cast<const char*>(wtab_wnz(buf, 3, 1, 4, true)) == buf + 16);
+    CHECK(reinterpret_cast<const char*>(wtab_wnz(buf, 3, 1, 4, false)) == buf + 32);
+}
+
+static const char* out_name(int out) { return out == NW_OUT_CWT ? "cwt" : out == NW_OUT_POWER ? "power" : "abs"; }
+
+template <typename T, int N, int E, int OUT>
+static void print_ladder() {
+    const char* dt = sizeof(T) == 4 ? "float32" : "float64";
+    std::printf("variants %s %d %s single", dt, N, out_name(OUT));
+    for (int nz = 1, prev = 0; nz <= E; ++nz) {
+        const int v = nw::pass0_variant<E, nw::kNzFineOut<T, N, E, OUT>, nw::kNz24Of<T, N, E>>(nz);
+        if (v != prev) std::printf(" %d", v);
+        prev = v;
+    }
+    std::printf("\n");
+    if constexpr (nw::kPairMode<T, E, true>) {
+        std::printf("variants %s %d %s pair", dt, N, out_name(OUT));
+        for (int nz = 1, prev = 0; nz <= E; ++nz) {
+            const int v = nw::pair_pass0_variant(nz, E);
+            if (v != prev) std::printf(" %d", v);
+            prev = v;
+        }
+        std::printf("\n");
+    }
+}
+
+// every rule of the table, one line each, for tests/test_host_asan.py to compare with the
+// tests' Python restatement (tests/fused_variants.py, tests/test_decim_cpu.py)
+static void print_shapes() {
+    using namespace nw;
+    for (int dtype : {NW_F32, NW_F64})
+        for (int64_t n = 512; n <= 32768; n *= 2)
+            for_fused_size(n, dtype, 0, []<typename T, int N, int E>(FusedSize<T, N, E>) {
+                const char* dt = sizeof(T) == 4 ? "float32" : "float64";
+                std::printf("size %s %d E %d pair %d\n", dt, N, E, (int)kPairMode<T, E, true>);
+                print_ladder<T, N, E, NW_OUT_CWT>();
+                print_ladder<T, N, E, NW_OUT_ABS>();
+                print_ladder<T, N, E, NW_OUT_POWER>();
+                std::printf("wnz %s %d", dt, N);
+                for (int need = 1; need <= E; ++need) std::printf(" %d", wnz_round(need, E));
+                std::printf("\n");
+                constexpr int PE = kPsE<T, E, false>, HE = kPsE<T, E, true>;
+                std::printf("psum %s %d power E %d shift %d ok %d\n", dt, N, PE, kPsShift<E, PE>, (int)kPSumOK<T, N, E>);
+                std::printf("psum %s %d phase E %d shift %d ok %d\n", dt, N, HE, kPsShift<E, HE>, (int)kPhSumOK<T, N, E>);
+                return 1;
+            });
+    const int64_t extra[] = {1000, 3000, 4097, 6144, 12288, 16383, 16385};
+    for (int dtype : {NW_F32, NW_F64}) {
+        std::vector<int64_t> sizes;
+        for (int64_t n = 512; n <= 32768; n *= 2) sizes.push_back(n);
+        sizes.insert(sizes.end(), std::begin(extra), std::end(extra));
+        for (int64_t n : sizes)
+            for (int decim = -2; decim <= 32; ++decim)
+                if (decim_supported(n, dtype, decim))
+                    std::printf("decim %s %lld %d\n", dtype == NW_F32 ? "float32" : "float64", (long long)n, decim);
+    }
+}
+
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "self";
+    if (mode == "shapes") {
+        print_shapes();
+        return 0;
+    }
     if (mode == "grid") {
         double rl, sf;
         int interp;
@@ -202,6 +328,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     self_checks();
+    shape_checks();
     std::printf("%s\n", g_fail ? "FAIL" : "ok");
     return g_fail ? 1 : 0;
 }

@@ -1,6 +1,8 @@
 """Which pass-0 variant (pruned idft_br<T, E, NZ>) of the one-pass fused kernels a W row runs,
-restated from nw_fused.hip for the tests that steer rows into every instantiated variant
-(tests/test_gpu_dft_forms.py: analytic rows, tests/test_gpu_table_rows.py: table rows).
+restated from ninwavelets_amd/csrc/nw_shape.h for the tests that steer rows into every
+instantiated variant (tests/test_gpu_dft_forms.py: analytic rows, tests/test_gpu_table_rows.py:
+table rows).  tests/test_host_asan.py compares this restatement, line by line, with what the
+header itself gives for every row of the size table (tests/asan/host_asan.cpp, mode `shapes`).
 
 A row's support ends at its last bin above kTailRel x the row's max |W| (nw_internal.h);
 wsupport_kernel rounds the pass-0 elements reaching it to wnz, pass0_variant picks the smallest
@@ -12,13 +14,13 @@ TAIL_REL = {'float64': 2.0 ** -72, 'float32': 2.0 ** -56}      # kTailRel (nw_in
 
 
 def elems_per_thread(n):
-    """E of the fused kernels (nw_fused.hip, NW_FUSED_SIZES): 16 up to n = 4096, 32 above."""
+    """E of the fused kernels (fused_e, nw_shape.h): 16 up to n = 4096, 32 above."""
     return 16 if n <= 4096 else 32
 
 
 def instantiated_variants(n, dtype, out, pair):
     """The pass-0 variants NZ of the kernel that runs (n, dtype, out): pass0_variant
-    (nw_fused.hip) for the single-signal kernel, the pair kernel's own ladder."""
+    (nw_shape.h) for the single-signal kernel, the pair kernel's own ladder (pair_pass0_variant)."""
     e = elems_per_thread(n)
     if pair:
         return {4, 8, 12, e}
@@ -32,7 +34,7 @@ def instantiated_variants(n, dtype, out, pair):
 
 def row_wnz(row, n, dtype):
     """wnz of one W row as wsupport_kernel builds it: pass-0 elements reaching the support,
-    rounded up to 1, 2, 4, 8, then to a multiple of 4, capped at E."""
+    rounded up (wnz_round, nw_shape.h) to 1, 2, 4, 8, then to a multiple of 4, capped at E."""
     e = elems_per_thread(n)
     mag = np.abs(np.asarray(row))
     mag = np.where(np.isfinite(mag), mag, 0.0)

@@ -36,9 +36,9 @@ TAIL = 37
 
 
 def fused_constants(f64=False):
-    """Signals per block and XCD-tile groups as the kernel source defines them for the
+    """Signals per block and XCD-tile groups as the kernels' geometry header defines them for the
     n = 16384 output kernels (kGroup / kTileG; fp64: NW_GROUP64_16K / NW_TILE64_G_16K)."""
-    src = open(os.path.join(ROOT, 'ninwavelets_amd', 'csrc', 'nw_fused.hip')).read()
+    src = open(os.path.join(ROOT, 'ninwavelets_amd', 'csrc', 'nw_shape.h')).read()
     if f64:
         return (int(re.search(r'#define NW_GROUP64_16K (\d+)', src).group(1)),
                 int(re.search(r'#define NW_TILE64_G_16K (\d+)', src).group(1)))

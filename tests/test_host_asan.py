@@ -2,7 +2,10 @@
 CPU path").  ninwavelets_amd/csrc/nw_host.cpp -- numpy-exact grid lengths, Normal-mode
 row timelines, distinct-row grouping with row hashing, balanced signal blocks and the
 threaded copy-out -- is compiled with g++ -fsanitize=address,undefined together with the
-driver tests/asan/host_asan.cpp; any out-of-bounds access, leak or UB aborts the run."""
+driver tests/asan/host_asan.cpp; any out-of-bounds access, leak or UB aborts the run.  The driver
+also includes ninwavelets_amd/csrc/nw_shape.h, the launch geometry the kernels and their
+launchers compile: its grids are checked exhaustively and its rules compared with the tests'
+Python restatement."""
 import os
 import shutil
 import subprocess
@@ -33,6 +36,52 @@ def test_host_logic_under_asan(host_asan):
     r = subprocess.run([host_asan, 'self'], capture_output=True, text=True, env=ENV, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.strip() == 'ok'
+
+
+def test_python_restatement_matches_the_shape_header(host_asan):
+    """tests/fused_variants.py (the rules the GPU tests use to steer rows into every pass-0
+    variant) and tests/test_decim_cpu.py's rule, line by line against what nw_shape.h -- the
+    header the kernels and launchers compile -- gives for every row of the size table."""
+    import fused_variants as V
+    from test_decim_cpu import rule
+    r = subprocess.run([host_asan, 'shapes'], capture_output=True, text=True, env=ENV, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = r.stdout.splitlines()
+    sizes = [512 << i for i in range(7)]
+    want, psum = [], 0
+    for dtype in ('float32', 'float64'):
+        for n in sizes[1:6]:                                  # the table: 1024 .. 16384
+            e = V.elems_per_thread(n)
+            pair = dtype == 'float32' and e <= 16             # analytic rows of these sizes run signal pairs
+            want.append(f'size {dtype} {n} E {e} pair {int(pair)}')
+            for out in ('cwt', 'abs', 'power'):
+                for p in ([False, True] if pair else [False]):
+                    ladder = ' '.join(map(str, sorted(V.instantiated_variants(n, dtype, out, p))))
+                    want.append(f'variants {dtype} {n} {out} {"pair" if p else "single"} {ladder}')
+            wnz = []
+            for need in range(1, e + 1):                      # a row whose last bin is in element need - 1
+                row = np.zeros(n)
+                row[(need - 1) * (n // e)] = 1.0
+                w, nd = V.row_wnz(row, n, dtype)
+                assert nd == need
+                wnz.append(w)
+            want.append(f'wnz {dtype} {n} ' + ' '.join(map(str, wnz)))
+            want += [None, None]                              # the two partial-sum lines (no Python restatement)
+    for dtype in ('float32', 'float64'):
+        for n in sizes + [1000, 3000, 4097, 6144, 12288, 16383, 16385]:
+            want += [f'decim {dtype} {n} {d}' for d in range(-2, 33) if d > 0 and rule(n, d)]
+    assert len(got) == len(want), (len(got), len(want))
+    for g, w in zip(got, want):
+        if w is not None:
+            assert g == w
+            continue
+        # partial sums: E is the output kernels' or 16, the support table shifted by their ratio
+        tag, dtype, n, kind, _, pe, _, shift, _, ok = g.split()
+        e = V.elems_per_thread(int(n))
+        assert tag == 'psum' and kind in ('power', 'phase') and int(pe) in (16, e) and int(pe) << int(shift) == e
+        assert ok in ('0', '1')
+        psum += 1
+    assert psum == 20 and sum(w is not None and w.startswith('decim') for w in want) == 20
 
 
 def test_trans_grid_under_asan_matches_numpy(host_asan):
