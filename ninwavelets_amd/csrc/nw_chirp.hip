@@ -329,13 +329,6 @@ struct ChirpKey {
 std::mutex g_chirp_mu;
 std::map<ChirpKey, void*> g_chirp;   // per device, length and M: Bh[M] then (fp64) c[n]
 
-constexpr int kChirpClasses = 5;      // M = 1024 << c, c < 5
-int64_t chirp_m(int64_t n) {
-    int64_t m = 1024;
-    while (m < 2 * n - 1) m <<= 1;
-    return m;
-}
-
 hipError_t chirp_tables(int64_t n, int64_t m, int dtype, void** out) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -386,30 +379,25 @@ hipError_t launch_m_e(const WDesc& d, int out_kind, const void* X, const void* w
     const cplx<T>* Xc = reinterpret_cast<const cplx<T>*>(X);
     const C2<T>* twc = reinterpret_cast<const C2<T>*>(tw);
     auto go = [&](auto kern) {
-        e = nw_launch_lds(kern, (unsigned)g.blocks, threads, lds, s, d, Xc, wtab, out, twc, bh, ct, nsig,
-                          (int)g.groups_pad, rowmap, nrows, ksup);
+        return nw_launch_lds(kern, (unsigned)g.blocks, threads, lds, s, d, Xc, wtab, out, twc, bh, ct, nsig,
+                             (int)g.groups_pad, rowmap, nrows, ksup);
     };
-    if (out_kind == NW_OUT_CWT) go(nw_chirp_kernel<T, M, E, NW_OUT_CWT, REALW>);
-    else if (out_kind == NW_OUT_POWER) go(nw_chirp_kernel<T, M, E, NW_OUT_POWER, REALW>);
-    else if (out_kind == kOutPSum || out_kind == kOutPhSum) {
+    if (out_kind == kOutPSum || out_kind == kOutPhSum) {
         // partial sums at E = 16 only (chirp_psum_ok: the classes whose kernels do not spill)
-        if constexpr (E == 16) {
-            if (out_kind == kOutPSum) go(nw_chirp_kernel<T, M, E, kOutPSum, REALW>);
-            else go(nw_chirp_kernel<T, M, E, kOutPhSum, REALW>);
-        } else {
-            e = hipErrorNotSupported;
-        }
-    } else go(nw_chirp_kernel<T, M, E, NW_OUT_ABS, REALW>);
-    return e;
+        if constexpr (E == 16)
+            return out_kind == kOutPSum ? go(nw_chirp_kernel<T, M, E, kOutPSum, REALW>)
+                                        : go(nw_chirp_kernel<T, M, E, kOutPhSum, REALW>);
+        else
+            return hipErrorNotSupported;
+    }
+    return for_out_kind(out_kind, [&](auto o) { return go(nw_chirp_kernel<T, M, E, decltype(o)::value, REALW>); });
 }
 
-// fp32 M = 8192: |y| and |y|^2 at E = 32 (256 threads, two blocks per CU, 3 passes, no
-// scratch): measured N = 4097 power 10.60 -> 8.75 ms, N = 3001 6.60 -> 5.82 ms per launch;
-// the complex output spills at E = 32 (108-128 B) and keeps E = 16
+// |y| and |y|^2 at kChirpAbsE (nw_shape.h: E = 32 at fp32 M = 8192), the other kinds at E
 template <typename T, int M, int E, bool REALW>
 hipError_t launch_m(const WDesc& d, int out_kind, const void* X, const void* wtab, void* out, int64_t nsig,
                     const int* rowmap, int nrows, const int* ksup, hipStream_t s) {
-    constexpr int EP = (sizeof(T) == 4 && M == 8192) ? 32 : E;
+    constexpr int EP = kChirpAbsE<T, M, E>;
     if constexpr (EP != E) {
         if (out_kind == NW_OUT_POWER || out_kind == NW_OUT_ABS)
             return launch_m_e<T, M, EP, REALW>(d, out_kind, X, wtab, out, nsig, rowmap, nrows, ksup, s);
@@ -418,24 +406,6 @@ hipError_t launch_m(const WDesc& d, int out_kind, const void* X, const void* wta
 }
 
 }  // namespace
-
-// (dtype, M, E) of the chirp engine: fp32 M <= 16384 (E = 32 at 16384), fp64 M <= 8192
-#define NW_CHIRP_TABLE(X)                                                                        \
-    X(float, 1024, 16) X(float, 2048, 16) X(float, 4096, 16) X(float, 8192, 16) X(float, 16384, 32) \
-    X(double, 1024, 16) X(double, 2048, 16) X(double, 4096, 16) X(double, 8192, 16)
-
-int64_t chirp_mmax(int dtype) { return dtype == NW_F32 ? 16384 : 8192; }
-
-bool chirp_supported(int64_t n, int dtype) {
-    if (n < 1 || fused_supported(n, dtype)) return false;
-    return (dtype == NW_F32 || dtype == NW_F64) && 2 * n - 1 <= chirp_mmax(dtype);
-}
-
-// longer lengths (up to M_max - 1) fit when every row's support does (M >= n + K - 1)
-bool chirp_possible(int64_t n, int dtype) {
-    if (n < 1 || fused_supported(n, dtype) || (dtype != NW_F32 && dtype != NW_F64)) return false;
-    return n < chirp_mmax(dtype);
-}
 
 // table buffer: W rows, then ksup[nfreq], then the row map (rows grouped by M class)
 size_t chirp_w_bytes(int64_t n, int nfreq, int dtype, int kind) {
@@ -449,47 +419,35 @@ size_t chirp_wtable_bytes(int64_t n, int nfreq, int dtype, int kind) {
 hipError_t build_chirp_wtable(const WDesc& d, int dtype, void* wtab, hipStream_t s, int64_t* counts, bool* fits,
                               std::vector<int>* overflow) {
     dim3 grid((unsigned)((d.n + 255) / 256), (unsigned)d.nfreq);
-    const bool realw = d.kind != NW_TABLE;
     int* ksup = reinterpret_cast<int*>(reinterpret_cast<char*>(wtab) + chirp_w_bytes(d.n, d.nfreq, dtype, d.kind));
     int* rowmap = ksup + d.nfreq;
-    if (dtype == NW_F32) {
-        if (realw) nw_launch(chirp_wtable_kernel<float, true>, grid, 256, 0, s, d, wtab);
-        else nw_launch(chirp_wtable_kernel<float, false>, grid, 256, 0, s, d, wtab);
-        if (realw) nw_launch(chirp_support_kernel<float, true>, d.nfreq, 256, 0, s, wtab, d.n, ksup);
-        else nw_launch(chirp_support_kernel<float, false>, d.nfreq, 256, 0, s, wtab, d.n, ksup);
-    } else {
-        if (realw) nw_launch(chirp_wtable_kernel<double, true>, grid, 256, 0, s, d, wtab);
-        else nw_launch(chirp_wtable_kernel<double, false>, grid, 256, 0, s, d, wtab);
-        if (realw) nw_launch(chirp_support_kernel<double, true>, d.nfreq, 256, 0, s, wtab, d.n, ksup);
-        else nw_launch(chirp_support_kernel<double, false>, d.nfreq, 256, 0, s, wtab, d.n, ksup);
-    }
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const bool realw = d.kind != NW_TABLE;
+        for_bool(realw, [&](auto rw) { nw_launch(chirp_wtable_kernel<T, decltype(rw)::value>, grid, 256, 0, s, d, wtab); });
+        for_bool(realw, [&](auto rw) {
+            nw_launch(chirp_support_kernel<T, decltype(rw)::value>, d.nfreq, 256, 0, s, wtab, d.n, ksup);
+        });
+    });
     hipError_t e = hipGetLastError();
-    // once per wavelet: the rows' M classes on the host (M >= n + K - 1 wrap-free, >= 2K for
-    // the pruned first pass 0, >= 1024, <= the full 2^ceil(log2(2n - 1)))
+    // once per wavelet: the rows' M classes on the host (chirp_class, nw_shape.h)
     std::vector<int> ks(d.nfreq);
     if (e == hipSuccess) e = hipMemcpyAsync(ks.data(), ksup, d.nfreq * sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
-    const int64_t mfull = std::min<int64_t>(chirp_m(d.n), chirp_mmax(dtype));
     std::vector<int> cls(d.nfreq);
     for (int c = 0; c < kChirpClasses; ++c) counts[c] = 0;
     *fits = true;
     if (overflow) overflow->clear();
     for (int f = 0; f < d.nfreq; ++f) {
-        const int64_t need = std::max<int64_t>(d.n + std::max(ks[f], 1) - 1, 2 * (int64_t)ks[f]);
-        if (need > mfull) {
+        cls[f] = chirp_class(d.n, ks[f], dtype);
+        if (cls[f] < 0) {
             // wider than the largest on-chip transform: listed for the caller (rocFFT rows)
             *fits = false;
             if (overflow) overflow->push_back(f);
-            cls[f] = -1;
-            continue;
+        } else {
+            counts[cls[f]]++;
         }
-        int64_t m = 1024;
-        while (m < need && m < mfull) m <<= 1;
-        int c = 0;
-        while ((1024ll << c) < m) ++c;
-        cls[f] = c;
-        counts[c]++;
     }
     std::vector<int> map;
     for (int c = 0; c < kChirpClasses; ++c)
@@ -500,22 +458,9 @@ hipError_t build_chirp_wtable(const WDesc& d, int dtype, void* wtab, hipStream_t
     return e;
 }
 
-// Epoch partial sums on the chirp-z form: every M class of the wavelet needs a partial-sum
-// kernel without scratch (tools/regs.py): fp32 M <= 8192 (E = 16), fp64 power every M, fp64
-// phases M <= 2048 (44-60 B of scratch above)
-bool chirp_psum_ok(int dtype, bool phase, const int64_t* counts) {
-    for (int c = 0; c < kChirpClasses; ++c) {
-        if (counts[c] == 0) continue;
-        const int64_t m = 1024ll << c;
-        if (dtype == NW_F32 ? m > 8192 : (phase && m > 2048)) return false;
-    }
-    return true;
-}
-
 hipError_t launch_chirp(const WDesc& d, int dtype, int out_kind, const void* X, const void* wtab, void* out,
                         int64_t nsig, const int64_t* counts, hipStream_t s) {
     if (!chirp_possible(d.n, dtype)) return hipErrorNotSupported;
-    const bool realw = d.kind != NW_TABLE;
     const int* ksup = reinterpret_cast<const int*>(reinterpret_cast<const char*>(wtab) +
                                                    chirp_w_bytes(d.n, d.nfreq, dtype, d.kind));
     const int* rowmap = ksup + d.nfreq;
@@ -523,14 +468,13 @@ hipError_t launch_chirp(const WDesc& d, int dtype, int out_kind, const void* X, 
     for (int c = 0; c < kChirpClasses; ++c) {
         const int64_t cnt = counts[c];
         if (cnt == 0) continue;
-        const int64_t m = 1024ll << c;
-        hipError_t e = hipErrorNotSupported;
-#define NW_CHIRP_LAUNCH(TY, MM, EE)                                                                             \
-        if (m == MM && dtype == (sizeof(TY) == 4 ? NW_F32 : NW_F64))                                            \
-            e = realw ? launch_m<TY, MM, EE, true>(d, out_kind, X, wtab, out, nsig, rowmap + off, (int)cnt, ksup, s) \
-                      : launch_m<TY, MM, EE, false>(d, out_kind, X, wtab, out, nsig, rowmap + off, (int)cnt, ksup, s);
-        NW_CHIRP_TABLE(NW_CHIRP_LAUNCH)
-#undef NW_CHIRP_LAUNCH
+        const hipError_t e = for_chirp_size(int64_t(1024) << c, dtype, hipErrorNotSupported,
+                                            [&]<typename T, int M, int E>(ChirpSize<T, M, E>) {
+            return for_bool(d.kind != NW_TABLE, [&](auto rw) {
+                return launch_m<T, M, E, decltype(rw)::value>(d, out_kind, X, wtab, out, nsig, rowmap + off, (int)cnt,
+                                                               ksup, s);
+            });
+        });
         if (e != hipSuccess) return e;
         off += cnt;
     }

@@ -711,17 +711,13 @@ hipError_t build_wtable(const WDesc& d, int dtype, void* wtab, hipStream_t s) {
     const int e = fused_e(d.n, dtype);
     if (e == 0) return hipErrorNotSupported;
     const int tt = (int)(d.n / e);
-    if (dtype == NW_F32) {
-        if (realw) nw_launch(wtable_kernel<float, true>, grid, 256, 0, s, d, wtab);
-        else nw_launch(wtable_kernel<float, false>, grid, 256, 0, s, d, wtab);
-        if (realw) nw_launch(wsupport_kernel<float, true>, d.nfreq, 256, 0, s, wtab, d.n, tt, e, wnz);
-        else nw_launch(wsupport_kernel<float, false>, d.nfreq, 256, 0, s, wtab, d.n, tt, e, wnz);
-    } else {
-        if (realw) nw_launch(wtable_kernel<double, true>, grid, 256, 0, s, d, wtab);
-        else nw_launch(wtable_kernel<double, false>, grid, 256, 0, s, d, wtab);
-        if (realw) nw_launch(wsupport_kernel<double, true>, d.nfreq, 256, 0, s, wtab, d.n, tt, e, wnz);
-        else nw_launch(wsupport_kernel<double, false>, d.nfreq, 256, 0, s, wtab, d.n, tt, e, wnz);
-    }
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        for_bool(realw, [&](auto rw) { nw_launch(wtable_kernel<T, decltype(rw)::value>, grid, 256, 0, s, d, wtab); });
+        for_bool(realw, [&](auto rw) {
+            nw_launch(wsupport_kernel<T, decltype(rw)::value>, d.nfreq, 256, 0, s, wtab, d.n, tt, e, wnz);
+        });
+    });
     return hipGetLastError();
 }
 

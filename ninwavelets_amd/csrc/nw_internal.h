@@ -88,6 +88,16 @@ inline hipError_t for_out_kind(int out_kind, F f) {
     if (out_kind == NW_OUT_POWER) return f(std::integral_constant<int, NW_OUT_POWER>{});
     return f(std::integral_constant<int, NW_OUT_ABS>{});
 }
+// f(T{}) for the compute type of a plan dtype (double for any value but NW_F32)
+template <typename F>
+inline auto for_dtype(int dtype, F f) {
+    return dtype == NW_F32 ? f(float{}) : f(double{});
+}
+// f(std::bool_constant<B>) for a launch's two-way template switch (real or complex W rows, ...)
+template <typename F>
+inline auto for_bool(bool b, F f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // ---------------------------------------------------------------------------
 // Analytic spectra.  fp64 follows the reference expression order exactly;
@@ -296,8 +306,8 @@ hipError_t fused_power_partials(const WDesc& d, int dtype, bool phase, const voi
 
 // chirp-z engine (nw_chirp.hip): n not taken by the power-of-two kernels, 2n - 1 <= 16384
 // (fp32) / 8192 (fp64); one (scale, signal) row = two on-chip FFTs of M = 2^ceil(log2(2n-1))
-bool       chirp_supported(int64_t n, int dtype);
-bool       chirp_possible(int64_t n, int dtype);   // also n < M_max when every row's support fits
+// (chirp_supported, chirp_possible -- also n < M_max when every row's support fits --,
+// chirp_class and chirp_psum_ok: nw_shape.h)
 size_t     chirp_wtable_bytes(int64_t n, int nfreq, int dtype, int kind);
 // builds W, each row's support and the rows grouped by M class (M = 1024 << c, c < 5:
 // counts[c] rows each; synchronises s once); launch_chirp runs one kernel per class
@@ -307,14 +317,12 @@ hipError_t build_chirp_wtable(const WDesc& d, int dtype, void* wtab, hipStream_t
                               std::vector<int>* overflow);
 hipError_t launch_chirp(const WDesc& d, int dtype, int out_kind, const void* X, const void* wtab, void* out,
                         int64_t nsig, const int64_t* counts, hipStream_t s);
-bool chirp_psum_ok(int dtype, bool phase, const int64_t* counts);
 
 // two-pass engine for long signals (nw_large.hip): power-of-two 2^15 <= n <= 2^24, fp32 or
 // fp64.  scratch = Xt (n complex) + B (large_fchunk scales x n complex); support = kmax[nfreq]
 // + the fp64 column-pass twiddle tables.
-bool       large_supported(int64_t n, int dtype);
+// (large_supported, large_support_bytes: nw_shape.h)
 size_t     large_scratch_bytes(int64_t n, int nfreq, int dtype);
-size_t     large_support_bytes(int nfreq);
 int64_t    large_fchunk(int64_t n, int nfreq, int dtype);
 hipError_t build_large_support(const WDesc& d, int dtype, void* support, hipStream_t s);
 // kmax[] / wmax[] of the rows into support (its first nfreq ints are kmax): the analytic kinds

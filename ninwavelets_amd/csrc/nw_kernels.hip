@@ -66,14 +66,17 @@ hipError_t launch_multiply(const WDesc& d, int dtype, const void* X, void* Y, in
     const int V = dtype == NW_F32 ? 2 : 1;
     dim3 grid((unsigned)((d.n + (int64_t)K1_THREADS * V - 1) / ((int64_t)K1_THREADS * V)), (unsigned)d.nfreq,
               (unsigned)((nsig + K1_GROUP - 1) / K1_GROUP));
-    if (dtype == NW_F32) {
-        if (d.n % 2 == 0)
-            nw_launch(k1_multiply<float, 2, true>, grid, K1_THREADS, 0, s, d, (const cplx<float>*)X, (cplx<float>*)Y, nsig);
-        else
-            nw_launch(k1_multiply<float, 2, false>, grid, K1_THREADS, 0, s, d, (const cplx<float>*)X, (cplx<float>*)Y, nsig);
-    } else {
-        nw_launch(k1_multiply<double, 1, true>, grid, K1_THREADS, 0, s, d, (const cplx<double>*)X, (cplx<double>*)Y, nsig);
-    }
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        constexpr int VT = sizeof(T) == 4 ? 2 : 1;
+        auto go = [&](auto kernel) {
+            nw_launch(kernel, grid, K1_THREADS, 0, s, d, (const cplx<T>*)X, (cplx<T>*)Y, nsig);
+        };
+        if constexpr (VT > 1) {
+            if (d.n % VT != 0) return go(k1_multiply<T, VT, false>);
+        }
+        go(k1_multiply<T, VT, true>);
+    });
     return hipGetLastError();
 }
 
@@ -92,17 +95,12 @@ __global__ __launch_bounds__(256) void k2_epilogue(const cplx<T>* __restrict__ Y
 
 hipError_t launch_epilogue(int dtype, int out_kind, const void* Y, void* out, int64_t count, hipStream_t s) {
     const int64_t blocks = std::min<int64_t>((count + 255) / 256, 256 * 16);
-    if (dtype == NW_F32) {
-        if (out_kind == NW_OUT_POWER)
-            nw_launch(k2_epilogue<float, true>, blocks, 256, 0, s, (const cplx<float>*)Y, (float*)out, count);
-        else
-            nw_launch(k2_epilogue<float, false>, blocks, 256, 0, s, (const cplx<float>*)Y, (float*)out, count);
-    } else {
-        if (out_kind == NW_OUT_POWER)
-            nw_launch(k2_epilogue<double, true>, blocks, 256, 0, s, (const cplx<double>*)Y, (double*)out, count);
-        else
-            nw_launch(k2_epilogue<double, false>, blocks, 256, 0, s, (const cplx<double>*)Y, (double*)out, count);
-    }
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        for_bool(out_kind == NW_OUT_POWER, [&](auto power) {
+            nw_launch(k2_epilogue<T, decltype(power)::value>, blocks, 256, 0, s, (const cplx<T>*)Y, (T*)out, count);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -125,10 +123,7 @@ __global__ __launch_bounds__(256) void k_rows(WDesc d, T* __restrict__ rows) {
 
 hipError_t launch_rows(const WDesc& d, int dtype, void* rows, hipStream_t s) {
     dim3 grid((unsigned)((d.len_full + 255) / 256), (unsigned)d.nfreq);
-    if (dtype == NW_F32)
-        nw_launch(k_rows<float>, grid, 256, 0, s, d, (float*)rows);
-    else
-        nw_launch(k_rows<double>, grid, 256, 0, s, d, (double*)rows);
+    for_dtype(dtype, [&](auto t) { nw_launch(k_rows<decltype(t)>, grid, 256, 0, s, d, (decltype(t)*)rows); });
     return hipGetLastError();
 }
 
@@ -175,18 +170,15 @@ __global__ __launch_bounds__(256) void k_accumulate(const void* __restrict__ src
 hipError_t launch_accumulate(int dtype, int src_kind, const void* src, double* acc, int64_t fn, int64_t c,
                              hipStream_t s) {
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((fn + 255) / 256, 256 * 32));
-#define NW_ACC(T)                                                                                         \
-    switch (src_kind) {                                                                                   \
-        case ACC_POWER_REAL: nw_launch(k_accumulate<T, ACC_POWER_REAL>, blocks, 256, 0, s, src, acc, fn, c); break; \
-        case ACC_POWER_Y: nw_launch(k_accumulate<T, ACC_POWER_Y>, blocks, 256, 0, s, src, acc, fn, c); break;       \
-        default: nw_launch(k_accumulate<T, ACC_PHASE_Y>, blocks, 256, 0, s, src, acc, fn, c); break;               \
-    }
-    if (dtype == NW_F32) {
-        NW_ACC(float)
-    } else {
-        NW_ACC(double)
-    }
-#undef NW_ACC
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        auto go = [&](auto kernel) { nw_launch(kernel, blocks, 256, 0, s, src, acc, fn, c); };
+        switch (src_kind) {
+            case ACC_POWER_REAL: return go(k_accumulate<T, ACC_POWER_REAL>);
+            case ACC_POWER_Y: return go(k_accumulate<T, ACC_POWER_Y>);
+            default: return go(k_accumulate<T, ACC_PHASE_Y>);
+        }
+    });
     return hipGetLastError();
 }
 
@@ -207,13 +199,10 @@ hipError_t launch_finalize(int dtype, bool itc, const double* acc, void* out, in
                            hipStream_t s) {
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((fn + 255) / 256, 256 * 32));
     const double d = (double)nsig;
-    if (dtype == NW_F32) {
-        if (itc) nw_launch(k_finalize<float, true>, blocks, 256, 0, s, acc, (float*)out, fn, d);
-        else nw_launch(k_finalize<float, false>, blocks, 256, 0, s, acc, (float*)out, fn, d);
-    } else {
-        if (itc) nw_launch(k_finalize<double, true>, blocks, 256, 0, s, acc, (double*)out, fn, d);
-        else nw_launch(k_finalize<double, false>, blocks, 256, 0, s, acc, (double*)out, fn, d);
-    }
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        for_bool(itc, [&](auto i) { nw_launch(k_finalize<T, decltype(i)::value>, blocks, 256, 0, s, acc, (T*)out, fn, d); });
+    });
     return hipGetLastError();
 }
 
@@ -287,12 +276,11 @@ __global__ __launch_bounds__(256) void k_normal_finish(const NormalRow* __restri
 
 hipError_t launch_normal_finish(const NormalRow* rows, int nrows, int64_t lmax, bool interp, const void* buf,
                                 int dtype, void* table, hipStream_t s) {
-    if (nrows > 0) {
-        if (dtype == NW_F32)
-            nw_launch(k_normal_finish<float>, nrows, 256, 0, s, rows, lmax, interp, (const double2*)buf, (cplx<float>*)table);
-        else
-            nw_launch(k_normal_finish<double>, nrows, 256, 0, s, rows, lmax, interp, (const double2*)buf, (cplx<double>*)table);
-    }
+    if (nrows > 0)
+        for_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            nw_launch(k_normal_finish<T>, nrows, 256, 0, s, rows, lmax, interp, (const double2*)buf, (cplx<T>*)table);
+        });
     return hipGetLastError();
 }
 
@@ -460,19 +448,14 @@ hipError_t launch_baseline(int dtype, const void* x, int64_t count, int64_t b0, 
     const int64_t n = std::max<int64_t>(0, b1 - b0);
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(BL_BLOCKS, (n + BL_THREADS - 1) / BL_THREADS));
     const int64_t ab = std::max<int64_t>(1, std::min<int64_t>((count + 255) / 256, 256 * 32));
-    if (dtype == NW_F32) {
-        nw_launch(k_bl_partial<float, 0>, nb, BL_THREADS, 0, s, (const float*)x, b0, b1, stats, part);
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        nw_launch(k_bl_partial<T, 0>, nb, BL_THREADS, 0, s, (const T*)x, b0, b1, stats, part);
         nw_launch(k_bl_final<0>, 1, BL_THREADS, 0, s, part, nb, n, stats);
-        nw_launch(k_bl_partial<float, 1>, nb, BL_THREADS, 0, s, (const float*)x, b0, b1, stats, part);
+        nw_launch(k_bl_partial<T, 1>, nb, BL_THREADS, 0, s, (const T*)x, b0, b1, stats, part);
         nw_launch(k_bl_final<1>, 1, BL_THREADS, 0, s, part, nb, n, stats);
-        if (count > 0) nw_launch(k_bl_apply<float>, ab, 256, 0, s, (const float*)x, (float*)out, count, op, stats);
-    } else {
-        nw_launch(k_bl_partial<double, 0>, nb, BL_THREADS, 0, s, (const double*)x, b0, b1, stats, part);
-        nw_launch(k_bl_final<0>, 1, BL_THREADS, 0, s, part, nb, n, stats);
-        nw_launch(k_bl_partial<double, 1>, nb, BL_THREADS, 0, s, (const double*)x, b0, b1, stats, part);
-        nw_launch(k_bl_final<1>, 1, BL_THREADS, 0, s, part, nb, n, stats);
-        if (count > 0) nw_launch(k_bl_apply<double>, ab, 256, 0, s, (const double*)x, (double*)out, count, op, stats);
-    }
+        if (count > 0) nw_launch(k_bl_apply<T>, ab, 256, 0, s, (const T*)x, (T*)out, count, op, stats);
+    });
     return hipGetLastError();
 }
 

@@ -18,8 +18,8 @@
 //                complex row stored to B[f][k1][0 .. N2)
 //   cols_kernel  per (scale f, C consecutive n2): v[k1] = B[f][k1][n2] * w_n^(n2 k1), C
 //                length-N1 inverse FFTs side by side (C * N1 = 32768 fp32 / 16384 fp64 points
-//                per 1024-thread workgroup, C * 2e B contiguous per k1 read), epilogue y / |y|
-//                / |y|^2 stored to out[f][n2 + N2 n1] (256-B contiguous runs at N1 = 1024)
+//                per workgroup, C complex values contiguous per k1 read: 256 B at N1 = 1024),
+//                epilogue y / |y| / |y|^2 stored to out[f][n2 + N2 n1] (256-B runs at N1 = 1024)
 //
 // fp64: rows of E = 32 at N2 >= 8192 and 16 below, as fp32 (its complex table rows: always
 // 16), 32 elements per thread in the column pass, the
@@ -50,41 +50,8 @@ namespace nw {
 
 namespace {
 
-constexpr int kRowGroup = 4;      // rows (k1) per rows_kernel workgroup (1 when a launch holds few scales)
-// (XCD tile kRowTileF x kRowTileG: nw_shape.h)
-// cols_kernel workgroups of 1024 threads: C = 32 columns at N1 = 1024, 256-B runs (C5 cols
-// 1.039 -> 0.978 ms per launch against 512 threads)
-// cols_kernel workgroup size (C * N1 / E)
-// fp64: 512 threads x 32 elements (N1 = 1024 in 2 passes, one exchange; 16 columns, 256-B runs
-// as before) against 1024 x 16 (3 passes, two exchanges): C5 fp64 cols 3.97-4.11 -> 3.90-3.91
-// ms per 32-scale launch (profiles/r05_c5f64_cols_e32_ab.txt; -DNW_COLS64_E16: the old form)
-#ifdef NW_COLS64_E16
-template <typename T> constexpr int kColThreads = 1024;
-#else
-template <typename T> constexpr int kColThreads = sizeof(T) == 8 ? 512 : 1024;
-#endif
-// bytes of B per launch pair (scales chunked to fit): 8 GiB = 64 scales of fp32 / 32 of fp64 at
-// C5.  Against 2 GiB (16 / 8 scales): C5 fp32 47.49 -> 46.15 ms per step, fp64 118.19 -> 113.15
-// (fewer, longer launches: the row pass's XCD tiles of 8 scales fill, fewer tails;
-// profiles/r04_c5_fchunk.txt)
-constexpr size_t kBBudget = size_t(8) << 30;
-
-// N2 (on-chip rows) and its elements per thread E, both dtypes: 32 from N2 = 8192 up, 16 below
-template <typename T, int N2> constexpr int kRowE = N2 >= 8192 ? 32 : 16;
-// complex table rows (wavelet_bin loads) spill at fp64 E = 32: E = 16 there
-template <typename T, int N2> constexpr int kRowETab = sizeof(T) == 8 ? 16 : kRowE<T, N2>;
-// elements per thread in cols_kernel: 32 complex fp32 (64 VGPRs) or fp64 (128 VGPRs, 2 waves/SIMD)
-#ifdef NW_COLS64_E16
-template <typename T> constexpr int kColE = sizeof(T) == 4 ? 32 : 16;
-#else
-template <typename T> constexpr int kColE = 32;
-#endif
-// rows of at most 16384 on chip, fp64 too (N2 = 8192 with N1 = 2048, 8-column blocks and
-// 128-B runs: C5 fp64 150.0 ms/step; 16384, 16 columns, 256-B runs: 129.9)
-// (fp32 rows of 32768 -- N1 = 512, 64-column workgroups writing 512-B output pieces -- measured
-// in round 6: the row pass at one 1024-thread block per CU +37-43 %, the column pass 0-3 %
-// faster, C5 step +10 %; profiles/r06_c5_rows32k_ab.txt)
-template <typename T> constexpr int kMaxN2 = 16384;
+// (the split, the row and column block shapes, the scale chunk and the support buffer's layout:
+// nw_shape.h)
 
 // ---- X (R2C half spectrum) -> Xt[k1][k2], mirrored + masked (spectrum_bin)
 template <typename T>
@@ -567,13 +534,7 @@ template <int KIND> struct RowW<double, KIND> {
 template <typename T, int KIND> struct RowRec { struct type {}; };
 template <> struct RowRec<double, kMorseRec> { using type = RowW<double, kMorseRec>::Rec; };
 
-// ---- pass 1: rows
-// fp32 E = 32 rows: pruned Xt rows by LDS-DMA ahead of the stores (C5 50.6 -> 48.5 ms per step);
-// analytic kinds only (table rows' wavelet_bin loads would exceed 128 VGPRs, as in nw_fused);
-// fp64 rows with the same DMA measured no faster (0.94 -> 0.98 ms per launch; round 5, after the
-// W-evaluator changes: rows -0.5 %, step +1.4 %, profiles/r05_c5f64_rows_xd_ab.txt)
-// (fp64 rows with the DMA, re-measured in round 4 beside the fast Morse form: no gain either,
-// profiles/r04_c5f64_rows_ab.txt)
+// ---- pass 1: rows (which rows take their Xt by LDS-DMA: kRowXD, nw_shape.h)
 // NW_ABL_ROWS_STREAM (diagnostic, wrong results): the row pass as a pure stream -- the pass-0
 // Xt loads (global, no LDS-DMA) and the last pass's B stores at the product's addresses and
 // widths, without W, FFT arithmetic or exchanges: the floor of its write stream
@@ -583,7 +544,7 @@ constexpr bool kRowsStream = true;
 constexpr bool kRowsStream = false;
 #endif
 template <typename T, int E, int KIND>
-constexpr bool kRowsXD = sizeof(T) == 4 && E >= 32 && KIND != NW_TABLE && !kRowsStream;
+constexpr bool kRowsXD = kRowXD<T, E, KIND == NW_TABLE> && !kRowsStream;
 // 4 waves/SIMD; fp64: 2 (twice the registers per element, as nw_fused)
 template <typename T, int N2, int E, int KIND>
 __global__ __launch_bounds__(N2 / E, sizeof(T) == 8 ? 2 : 4) void rows_kernel(
@@ -613,14 +574,20 @@ __global__ __launch_bounds__(N2 / E, sizeof(T) == 8 ? 2 : 4) void rows_kernel(
     if constexpr (TwSplit<T, N2, E>::ON) lds_barrier();   // read before the first exchange
     C2<T> x[E];
     // bins k = k1 + n1*k2 with k2 = t + r*T: elements r >= need are zero for every thread;
-    // pass 0 runs the variant NZ = nzv(need) elements
-    auto need_of = [&](int k1) { return km < k1 ? 1 : (km - k1) / n1 / G::T + 1; };
-    // pass-0 variants in steps of 4 elements at fp32 E = 32 (fp64: 4, 8, 16, 24, E)
-    constexpr bool FINE = E > 16 && sizeof(T) == 4 && KIND != NW_TABLE;   // table rows: more scratch
+    // pass 0 runs the variant NZ = nzv(need) elements (row_need, kRowFine: nw_shape.h)
+    auto need_of = [&](int k1) { return row_need(km, k1, n1, G::T); };
+    constexpr bool FINE = kRowFine<T, E, KIND == NW_TABLE>;
+    // pass0_variant<E, FINE, (E > 16)>, written out: a call of it gives the LDS-DMA kernels
+    // another scalar sequence for the ladder (profiles/r10_cols_isa.txt)
     auto nzv_of = [](int need) {
         return need <= 4 ? 4 : need <= 8 ? 8 : (FINE && need <= 12) ? 12 : (E > 16 && need <= 16) ? 16
              : (FINE && need <= 20) ? 20 : (E > 16 && need <= 24) ? 24 : E;
     };
+    static_assert([=] {
+        for (int need = 1; need <= E; ++need)
+            if (nzv_of(need) != pass0_variant<E, FINE, (E > 16)>(need)) return false;
+        return true;
+    }(), "nzv_of restates pass0_variant");
     // XD: a row whose pass 0 reads only Xt[k1][0 .. N2/2) (NZ <= E/2) gets those bins by
     // LDS-DMA into the idle image, issued BEFORE the previous row's stores (as nw_fused's
     // next-signal X): global loads issued after the stores would wait for all of them in
@@ -630,7 +597,7 @@ __global__ __launch_bounds__(N2 / E, sizeof(T) == 8 ? 2 : 4) void rows_kernel(
     bool in_lds = false;
     if constexpr (XD) {
         const int nz0 = nzv_of(need_of(k1_begin));
-        if (nz0 <= E / 2) {
+        if (nz0 <= kRowLdsNz<E>) {
             dma_x<T, N2, G::T>(Xt + (int64_t)k1_begin * N2, lds, t, dma_rounds_for<T>(nz0));
             in_lds = true;
         }
@@ -710,7 +677,7 @@ __global__ __launch_bounds__(N2 / E, sizeof(T) == 8 ? 2 : 4) void rows_kernel(
         if constexpr (XD) {
             if (k1 + 1 < k1_end) {
                 const int nzn = nzv_of(need_of(k1 + 1));
-                if (nzn <= E / 2) {
+                if (nzn <= kRowLdsNz<E>) {
                     xs_next = Xt + (int64_t)(k1 + 1) * N2;
                     rounds_next = dma_rounds_for<T>(nzn);
                 }
@@ -731,12 +698,18 @@ __global__ __launch_bounds__(N2 / E, sizeof(T) == 8 ? 2 : 4) void rows_kernel(
     }
 }
 
-// ---- pass 2: columns.  Thread t owns column c = t % C of the workgroup's C columns and
-// butterflies u + q*U (U = N1/E threads per column).  The exchange image is
-// [position][column] (position-major, C reals per position), one real component at a
-// time: 32-lane groups cover >= 16 consecutive columns (fp32), so reads are conflict-free
+// ---- pass 2: columns.  Thread t owns slot c = t % SLOTS of the workgroup's slots (one column,
+// or the adjacent columns 2c, 2c + 1 of the fp32 pair form) and butterflies u + q*U (U = N1/E
+// threads per slot).  The exchange image is
+// [position][slot] (position-major, SLOTS lane values per position), one real component at a
+// time: 32-lane groups cover >= 16 consecutive slots (fp32), so reads are conflict-free
 // and writes at most 2-way (free for ds_write_b32, MI355X_MICROARCH.md §LDS); fp64 lanes
 // read 8 B each, so C >= 8 columns keep a 32-lane group on consecutive positions.
+// fp32 on column PAIRS: every lane value a C2<f2> holding the two columns
+// (signal-pair technique of nw_fused_pair_kernel): B is read and y written 16 B per lane
+// (two complex64) instead of 8, every butterfly / twiddle / LDS access serves both columns
+// (v_pk_* math, 8-B image slots [position][pair]), the same C = 2 SLOTS columns per 1024-thread
+// workgroup and 256-B runs.  (The block shape of either form: ColShape, nw_shape.h.)
 // NW_ABL_COLS_STREAM (diagnostic, wrong results): the column kernels as a pure stream -- the
 // pass-0 B loads and the last pass's y stores at exactly the product's addresses and widths,
 // with no twiddles, FFT arithmetic or LDS exchanges between them: the floor the column pass's
@@ -749,49 +722,99 @@ __global__ __launch_bounds__(N2 / E, sizeof(T) == 8 ? 2 : 4) void rows_kernel(
 #define NW_ABL_COLS_NOTW
 #endif
 #endif
-template <typename T, int N1> struct Cols {
-    static constexpr int E = kColE<T>;
-    static constexpr int U = N1 / E;                 // threads per column
-    static constexpr int C = kColThreads<T> / U;     // columns per workgroup
-    using G = Geometry<N1, E>;
-    static_assert(N1 >= 32 && C >= (sizeof(T) == 4 ? 16 : 4), "cols geometry");
+// V: the lane value type -- float or double (one column per slot) or f2 (two)
+template <typename V, int N1> struct Cols : ColShape<Sc<V>, kIsPair<V>, N1> {
+    using G = Geometry<N1, ColShape<Sc<V>, kIsPair<V>, N1>::E>;
 };
 
-template <typename T, int N1, int P, int COMP>
-__device__ __forceinline__ void col_write(C2<T>* v, T* lds, int u, int c) {
-    using CL = Cols<T, N1>;
+template <typename V, int N1, int P, int COMP>
+__device__ __forceinline__ void col_write(C2<V>* v, V* lds, int u, int c) {
+    using CL = Cols<V, N1>;
     using G = typename CL::G;
-    constexpr int C = CL::C, U = CL::U;
+    constexpr int C = CL::SLOTS, U = CL::U;
     constexpr int R = G::radix(P), NS = G::ns(P), Q = CL::E / R;
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
         const int j = u + q * U;
-        T* dst = lds + ((j / NS) * NS * R + j % NS) * C + c;
+        V* dst = lds + ((j / NS) * NS * R + j % NS) * C + c;
 #pragma unroll
         for (int i = 0; i < R; ++i) dst[bitrev<R>(i) * NS * C] = comp<COMP>(v[q * R + i]);
     }
 }
 
-template <typename T, int N1, int P, int COMP>
-__device__ __forceinline__ void col_read(C2<T>* v, const T* lds, int u, int c) {
-    using CL = Cols<T, N1>;
+template <typename V, int N1, int P, int COMP>
+__device__ __forceinline__ void col_read(C2<V>* v, const V* lds, int u, int c) {
+    using CL = Cols<V, N1>;
     using G = typename CL::G;
-    constexpr int C = CL::C, U = CL::U;
+    constexpr int C = CL::SLOTS, U = CL::U;
     constexpr int R = G::radix(P), Q = CL::E / R, STRIDE = N1 / R;
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-        const T* src = lds + (u + q * U) * C + c;
+        const V* src = lds + (u + q * U) * C + c;
 #pragma unroll
         for (int r = 0; r < R; ++r) comp<COMP>(v[q * R + r]) = src[r * STRIDE * C];
     }
 }
 
+// B[k1][n2] as a slot's lane loads it -- one complex value, or the pair's two in 16 B -- and as
+// its lane value: the pair's (re, re), (im, im)
+template <typename V> struct ColLane { using type = C2<V>; };
+template <> struct ColLane<f2> { using type = float __attribute__((ext_vector_type(4))); };
+template <typename V>
+__device__ __forceinline__ C2<V> col_value(typename ColLane<V>::type b) {
+    if constexpr (kIsPair<V>) return C2<f2>{f2{b.x, b.z}, f2{b.y, b.w}};
+    else return b;
+}
+
+// y of a slot, or its |y| / |y|^2, stored nt at orow + lane_off + coff: C2<T> / O per column,
+// V4 / f2 per column pair
+template <int OUT, typename V>
+__device__ __forceinline__ void col_store(C2<V> y, void* orow, uint32_t lane_off, uint32_t coff) {
+    using T = Sc<V>;
+    using O = typename OutT<OUT, T>::type;
+    if constexpr (kIsPair<V>) {
+        O* dst = at(reinterpret_cast<O*>(orow), lane_off, coff);
+        if constexpr (OUT == NW_OUT_CWT) {
+            using V4 = float __attribute__((ext_vector_type(4)));
+            const V4 o{y.re.x, y.im.x, y.re.y, y.im.y};
+#ifdef NW_ABL_COLS_NOSTORE
+            asm volatile("" ::"v"(o), "v"(dst));
+#else
+            __builtin_nontemporal_store(o, reinterpret_cast<V4*>(dst));
+#endif
+        } else {
+            const f2 o{out_value<OUT, float>(C2<float>{y.re.x, y.im.x}),
+                       out_value<OUT, float>(C2<float>{y.re.y, y.im.y})};
+#ifdef NW_ABL_COLS_NOSTORE
+            asm volatile("" ::"v"(o), "v"(dst));
+#else
+            __builtin_nontemporal_store(o, reinterpret_cast<f2*>(dst));
+#endif
+        }
+    } else {
+        const O val = out_value<OUT, T>(y);
+        O* dst = at(reinterpret_cast<O*>(orow), lane_off, coff);
+#ifdef NW_ABL_COLS_NOSTORE
+        if constexpr (OUT == NW_OUT_CWT) asm volatile("" ::"v"(val.re), "v"(val.im), "v"(dst));
+        else asm volatile("" ::"v"(val), "v"(dst));
+#else
+        if constexpr (OUT == NW_OUT_CWT) {
+            using V2 = T __attribute__((ext_vector_type(2)));
+            __builtin_nontemporal_store(__builtin_bit_cast(V2, val), reinterpret_cast<V2*>(dst));
+        } else {
+            __builtin_nontemporal_store(val, dst);
+        }
+#endif
+    }
+}
+
 // tw1: fp64 only, the exact length-N1 table exp(+2 pi i j / N1) (fp32 twiddles come from
-// v_sin / v_cos)
-template <typename T, int N1, int N2, int OUT, int P>
-__device__ __forceinline__ void col_passes(C2<T>* v, T* lds, int u, int c, void* orow, uint32_t lane_off,
-                                           const C2<T>* __restrict__ tw1) {
-    using CL = Cols<T, N1>;
+// v_sin / v_cos, shared by the two columns of a pair)
+template <typename V, int N1, int N2, int OUT, int P>
+__device__ __forceinline__ void col_passes(C2<V>* v, V* lds, int u, int c, void* orow, uint32_t lane_off,
+                                           const C2<Sc<V>>* __restrict__ tw1) {
+    using T = Sc<V>;
+    using CL = Cols<V, N1>;
     using G = typename CL::G;
     constexpr int U = CL::U;
     constexpr int R = G::radix(P), NS = G::ns(P), Q = CL::E / R;
@@ -802,24 +825,24 @@ __device__ __forceinline__ void col_passes(C2<T>* v, T* lds, int u, int c, void*
 #endif
         constexpr int LR = ilog2<R>();
         lds_barrier();
-        col_write<T, N1, P - 1, 0>(v, lds, u, c);
+        col_write<V, N1, P - 1, 0>(v, lds, u, c);
         lds_barrier();
-        col_read<T, N1, P, 0>(v, lds, u, c);
+        col_read<V, N1, P, 0>(v, lds, u, c);
         lds_barrier();
-        col_write<T, N1, P - 1, 1>(v, lds, u, c);
+        col_write<V, N1, P - 1, 1>(v, lds, u, c);
         lds_barrier();
-        col_read<T, N1, P, 1>(v, lds, u, c);
+        col_read<V, N1, P, 1>(v, lds, u, c);
         // twiddles after the exchange (no stores are in flight here): bases of one
         // butterfly at a time, so they never sit live across the exchange
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
             C2<T> pb[LR > 0 ? LR : 1];
             twiddle_bases<T, R, N1, NS * R>(pb, (u + q * U) % NS, tw1);
-            twiddle_dft<T, R>(v + q * R, pb);
+            twiddle_dft<V, R>(v + q * R, pb);
         }
     }
     if constexpr (P + 1 < G::npass()) {
-        col_passes<T, N1, N2, OUT, P + 1>(v, lds, u, c, orow, lane_off, tw1);
+        col_passes<V, N1, N2, OUT, P + 1>(v, lds, u, c, orow, lane_off, tw1);
     } else {
         // v[q*R + i] is y at n1 = (j / NS) * NS * R + j % NS + bitrev(i) * NS, j = u + q*U.
         // The last pass has N1 / R = NS butterflies, so j < NS and n1 = u + q*U + bitrev(i)*NS:
@@ -830,62 +853,56 @@ __device__ __forceinline__ void col_passes(C2<T>* v, T* lds, int u, int c, void*
 #pragma unroll
             for (int i = 0; i < R; ++i) {
                 const uint32_t cn1 = (uint32_t)(q * U + bitrev<R>(i) * NS);
-                const O val = out_value<OUT, T>(v[q * R + i]);
-                O* dst = at(reinterpret_cast<O*>(orow), lane_off, cn1 * (uint32_t)N2 * (uint32_t)sizeof(O));
-#ifdef NW_ABL_COLS_NOSTORE
-                if constexpr (OUT == NW_OUT_CWT) asm volatile("" ::"v"(val.re), "v"(val.im), "v"(dst));
-                else asm volatile("" ::"v"(val), "v"(dst));
-                continue;
-#endif
-                if constexpr (OUT == NW_OUT_CWT) {
-                    using V2 = T __attribute__((ext_vector_type(2)));
-                    __builtin_nontemporal_store(__builtin_bit_cast(V2, val), reinterpret_cast<V2*>(dst));
-                } else {
-                    __builtin_nontemporal_store(val, dst);
-                }
+                col_store<OUT, V>(v[q * R + i], orow, lane_off, cn1 * (uint32_t)N2 * (uint32_t)sizeof(O));
             }
         }
     }
 }
 
-// fp64 pass-0 twiddles w_n^m (m = n2 k1 < n) as the product of two exact entries:
-// tsplit[m & 4095] = w_n^(m mod 4096) and tsplit[4096 + (m >> 12)] = w_n^(4096 (m >> 12))
-constexpr int kSplitLo = 4096;
-constexpr int kSplitEntries = 2 * kSplitLo;   // n <= 2^24: m >> 12 < 4096
-
-template <typename T, int N1, int N2, int OUT>
+// TW: fp64's two tables, (tw1, tsplit) -- tw1: col_passes; tsplit: the split pass-0 table,
+// kSplitLo -- and nothing in fp32: the kernel's argument list is part of its descriptor, so the
+// forms that read no table take none (col_tab: table I of the pack, null without one)
+template <typename T> using ColTab = const C2<T>* __restrict__;
+template <int I, typename T> __device__ __forceinline__ const C2<T>* col_tab() { return nullptr; }
+template <int I, typename T> __device__ __forceinline__ const C2<T>* col_tab(const C2<T>* tw1, const C2<T>* tsplit) {
+    return I == 0 ? tw1 : tsplit;
+}
+// workgroups per CU of the launch bounds
 #ifdef NW_COLS64_E16
-__global__ __launch_bounds__(kColThreads<T>, sizeof(T) == 8 ? 2 : 4) void cols_kernel(
+template <typename T> constexpr int kColBlocks = sizeof(T) == 8 ? 2 : 4;
 #else
-__global__ __launch_bounds__(kColThreads<T>, sizeof(T) == 8 ? 1 : 4) void cols_kernel(
+template <typename T> constexpr int kColBlocks = sizeof(T) == 8 ? 1 : 4;
 #endif
-    int f0, int nf, const C2<T>* __restrict__ B, void* __restrict__ out, const C2<T>* __restrict__ tw1,
-    const C2<T>* __restrict__ tsplit) {
-    using CL = Cols<T, N1>;
-    constexpr int C = CL::C, U = CL::U, E = CL::E;
+
+template <typename V, int N1, int N2, int OUT, typename... TW>
+__global__ __launch_bounds__((Cols<V, N1>::THREADS), (kColBlocks<Sc<V>>)) void cols_kernel(
+    int f0, int nf, const C2<Sc<V>>* __restrict__ B, void* __restrict__ out, TW... tw) {
+    using T = Sc<V>;
+    using CL = Cols<V, N1>;
+    constexpr int SLOTS = CL::SLOTS, C = CL::C, U = CL::U, E = CL::E;
     constexpr int64_t n = (int64_t)N1 * N2;
     extern __shared__ __align__(16) unsigned char smem[];
-    T* lds = reinterpret_cast<T*>(smem);
+    V* lds = reinterpret_cast<V*>(smem);
     const int t = threadIdx.x;
-    const int c = t % C, u = t / C;
+    const int c = t % SLOTS, u = t / SLOTS;
     constexpr int ngroups = N2 / C;
     const int fl = blockIdx.x / ngroups;
     const int cg = blockIdx.x % ngroups;
     if (fl >= nf) return;
-    const int col = cg * C + c;                      // n2
+    const int col = cg * C + CL::CPS * c;            // n2 (of the pair's first column)
     // B[fl] (uniform base) + 32-bit lane offsets: (k1 * N2 + col) * 16 < n * 16 <= 2^28
     const C2<T>* bf = B + (int64_t)fl * n;
     const uint32_t boff = ((uint32_t)u * N2 + (uint32_t)col) * (uint32_t)sizeof(C2<T>);
 
-    // pass 0: v[r] = B[k1][n2] * w_n^(n2 k1), k1 = u + U r (radix E, Ns = 1)
-    C2<T> v[E];
+    // pass 0: v[r] = B[k1][n2 (, n2 + 1)] * w_n^(n2 k1), k1 = u + U r (radix E, Ns = 1)
+    C2<V> v[E];
     // fp64: w_n^(n2 u) and w_n^(n2 U) from the exact split tables (4 loads per thread), the
     // E powers by repeated multiplication (<= E ulp of drift, far inside 1e-12)
-    C2<T> wr{T(1), T(0)}, wstep{T(1), T(0)};
+    [[maybe_unused]] C2<T> wr{T(1), T(0)}, wstep{T(1), T(0)};
     if constexpr (sizeof(T) == 8) {
         auto wpow = [&](uint32_t m) {
-            const C2<T> wl = *at(tsplit, (m & (kSplitLo - 1)) * (uint32_t)sizeof(C2<T>));
-            const C2<T> wh = *at(tsplit, (kSplitLo + (m >> 12)) * (uint32_t)sizeof(C2<T>));
+            const C2<T> wl = *at(col_tab<1, T>(tw...), (m & (kSplitLo - 1)) * (uint32_t)sizeof(C2<T>));
+            const C2<T> wh = *at(col_tab<1, T>(tw...), (kSplitLo + (m >> 12)) * (uint32_t)sizeof(C2<T>));
             return cmul(wh, wl);
         };
         wr = wpow((uint32_t)col * (uint32_t)u);
@@ -894,20 +911,26 @@ __global__ __launch_bounds__(kColThreads<T>, sizeof(T) == 8 ? 1 : 4) void cols_k
 #pragma unroll
     for (int r = 0; r < E; ++r) {
         const int k1 = u + U * r;
-        const C2<T> bv = *at(bf, boff, (uint32_t)(U * r * N2 * sizeof(C2<T>)));
+        using L = typename ColLane<V>::type;
+        const L bv = *reinterpret_cast<const L*>(at(bf, boff, (uint32_t)(U * r * N2 * sizeof(C2<T>))));
         const uint32_t m = (uint32_t)col * (uint32_t)k1;                      // n2 k1 < n <= 2^24
 #ifdef NW_ABL_COLS_NOTW
         (void)m;
-        v[r] = bv;
+        v[r] = col_value<V>(bv);
 #else
-        if constexpr (sizeof(T) == 4) {
-            constexpr float inv_n = 1.0f / (float)n;                          // exact: power of two
+        constexpr float inv_n = 1.0f / (float)n;                              // exact: power of two
+        if constexpr (kIsPair<V>) {                                           // the pair's two angles
+            const float r0 = (float)m * inv_n, r1 = (float)(m + (uint32_t)k1) * inv_n;
+            const C2<f2> w{f2{__builtin_amdgcn_cosf(r0), __builtin_amdgcn_cosf(r1)},
+                           f2{__builtin_amdgcn_sinf(r0), __builtin_amdgcn_sinf(r1)}};
+            v[r] = cmul(col_value<V>(bv), w);
+        } else if constexpr (sizeof(T) == 4) {
             const float rev = (float)m * inv_n;                               // exact: m < 2^24
             const C2<float> w{__builtin_amdgcn_cosf(rev), __builtin_amdgcn_sinf(rev)};
-            v[r] = cmul(bv, w);
+            v[r] = cmul(col_value<V>(bv), w);
         } else {
             (void)m;
-            v[r] = cmul(bv, wr);
+            v[r] = cmul(col_value<V>(bv), wr);
             if (r + 1 < E) wr = cmul(wr, wstep);
         }
 #endif
@@ -916,156 +939,12 @@ __global__ __launch_bounds__(kColThreads<T>, sizeof(T) == 8 ? 1 : 4) void cols_k
 #pragma unroll
     for (int i = 0; i < E; ++i) asm volatile("" : "+v"(v[i].re), "+v"(v[i].im));
 #else
-    idft_br<T, E>(v);
+    idft_br<V, E>(v);
 #endif
     using O = typename OutT<OUT, T>::type;
     void* orow = reinterpret_cast<char*>(out) + (int64_t)(f0 + fl) * n * (int64_t)sizeof(O);
     const uint32_t ooff = ((uint32_t)col + (uint32_t)u * N2) * (uint32_t)sizeof(O);
-    col_passes<T, N1, N2, OUT, 0>(v, lds, u, c, orow, ooff, tw1);
-}
-
-// ---- fp32 column pass on column PAIRS: thread (cp, u) owns the adjacent columns 2cp, 2cp+1
-// and E2 = 16 elements k1 = u + U2 r of each, every lane value a C2<f2> holding the two columns
-// (signal-pair technique of nw_fused_pair_kernel): B is read and y written 16 B per lane
-// (two complex64) instead of 8, every butterfly / twiddle / LDS access serves both columns
-// (v_pk_* math, 8-B image slots [position][pair]), the same C = 2 CP columns per 1024-thread
-// workgroup and 256-B runs.  Length-N1 transforms at E = 16 take one exchange more than E = 32.
-// (E = 32 with 512-thread workgroups: one exchange instead of two, 198 VGPRs at 2 waves/SIMD:
-// C5 cols 3.92 -> 3.95 ms per launch, not kept; profiles/r04_c5_colpairs_ab.txt)
-template <int N1> struct ColsP {
-    static constexpr int E = 16;
-    static constexpr int THREADS = 1024;
-    static constexpr int U = N1 / E;                 // threads per column pair
-    static constexpr int CP = THREADS / U;           // column pairs per workgroup
-    static constexpr int C = 2 * CP;
-    using G = Geometry<N1, E>;
-    static_assert(N1 >= 32 && CP >= 16, "column-pair geometry");
-};
-
-template <int N1, int P, int COMP>
-__device__ __forceinline__ void colp_write(C2<f2>* v, f2* lds, int u, int cp) {
-    using CL = ColsP<N1>;
-    using G = typename CL::G;
-    constexpr int CP = CL::CP, U = CL::U;
-    constexpr int R = G::radix(P), NS = G::ns(P), Q = CL::E / R;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int j = u + q * U;
-        f2* dst = lds + ((j / NS) * NS * R + j % NS) * CP + cp;
-#pragma unroll
-        for (int i = 0; i < R; ++i) dst[bitrev<R>(i) * NS * CP] = comp<COMP>(v[q * R + i]);
-    }
-}
-
-template <int N1, int P, int COMP>
-__device__ __forceinline__ void colp_read(C2<f2>* v, const f2* lds, int u, int cp) {
-    using CL = ColsP<N1>;
-    using G = typename CL::G;
-    constexpr int CP = CL::CP, U = CL::U;
-    constexpr int R = G::radix(P), Q = CL::E / R, STRIDE = N1 / R;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const f2* src = lds + (u + q * U) * CP + cp;
-#pragma unroll
-        for (int r = 0; r < R; ++r) comp<COMP>(v[q * R + r]) = src[r * STRIDE * CP];
-    }
-}
-
-template <int N1, int N2, int OUT, int P>
-__device__ __forceinline__ void colp_passes(C2<f2>* v, f2* lds, int u, int cp, void* orow, uint32_t lane_off) {
-    using CL = ColsP<N1>;
-    using G = typename CL::G;
-    constexpr int U = CL::U;
-    constexpr int R = G::radix(P), NS = G::ns(P), Q = CL::E / R;
-#ifdef NW_ABL_COLS_STREAM
-    if constexpr (false) {
-#else
-    if constexpr (P > 0) {
-#endif
-        constexpr int LR = ilog2<R>();
-        lds_barrier();
-        colp_write<N1, P - 1, 0>(v, lds, u, cp);
-        lds_barrier();
-        colp_read<N1, P, 0>(v, lds, u, cp);
-        lds_barrier();
-        colp_write<N1, P - 1, 1>(v, lds, u, cp);
-        lds_barrier();
-        colp_read<N1, P, 1>(v, lds, u, cp);
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            C2<float> pb[LR > 0 ? LR : 1];                  // shared by the two columns
-            twiddle_bases<float, R, N1, NS * R>(pb, (u + q * U) % NS, nullptr);
-            twiddle_dft<f2, R>(v + q * R, pb);
-        }
-    }
-    if constexpr (P + 1 < G::npass()) {
-        colp_passes<N1, N2, OUT, P + 1>(v, lds, u, cp, orow, lane_off);
-    } else {
-        // v[q*R + i] is y at n1 = u + q*U + bitrev(i)*NS (the last pass has NS butterflies)
-        using O = typename OutT<OUT, float>::type;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-#pragma unroll
-            for (int i = 0; i < R; ++i) {
-                const uint32_t cn1 = (uint32_t)(q * U + bitrev<R>(i) * NS);
-                const C2<f2> y = v[q * R + i];
-                O* dst = at(reinterpret_cast<O*>(orow), lane_off, cn1 * (uint32_t)N2 * (uint32_t)sizeof(O));
-                if constexpr (OUT == NW_OUT_CWT) {
-                    using V4 = float __attribute__((ext_vector_type(4)));
-                    __builtin_nontemporal_store(V4{y.re.x, y.im.x, y.re.y, y.im.y}, reinterpret_cast<V4*>(dst));
-                } else {
-                    const f2 o{out_value<OUT, float>(C2<float>{y.re.x, y.im.x}),
-                               out_value<OUT, float>(C2<float>{y.re.y, y.im.y})};
-                    __builtin_nontemporal_store(o, reinterpret_cast<f2*>(dst));
-                }
-            }
-        }
-    }
-}
-
-template <int N1, int N2, int OUT>
-__global__ __launch_bounds__(ColsP<N1>::THREADS, ColsP<N1>::THREADS / 256) void cols_kernel(int f0, int nf, const C2<float>* __restrict__ B,
-                                                       void* __restrict__ out) {
-    using CL = ColsP<N1>;
-    constexpr int CP = CL::CP, C = CL::C, U = CL::U, E = CL::E;
-    constexpr int64_t n = (int64_t)N1 * N2;
-    extern __shared__ __align__(16) unsigned char smem[];
-    f2* lds = reinterpret_cast<f2*>(smem);
-    const int t = threadIdx.x;
-    const int cp = t % CP, u = t / CP;
-    constexpr int ngroups = N2 / C;
-    const int fl = blockIdx.x / ngroups;
-    const int cg = blockIdx.x % ngroups;
-    if (fl >= nf) return;
-    const int col = cg * C + 2 * cp;                 // n2 of the pair's first column
-    const C2<float>* bf = B + (int64_t)fl * n;
-    const uint32_t boff = ((uint32_t)u * N2 + (uint32_t)col) * (uint32_t)sizeof(C2<float>);
-    // pass 0: v[r] = B[k1][n2 .. n2+1] * w_n^(n2 k1), k1 = u + U r
-    C2<f2> v[E];
-#pragma unroll
-    for (int r = 0; r < E; ++r) {
-        const int k1 = u + U * r;
-        using V4 = float __attribute__((ext_vector_type(4)));
-        const V4 b4 = *reinterpret_cast<const V4*>(at(bf, boff, (uint32_t)(U * r * N2 * sizeof(C2<float>))));
-#ifdef NW_ABL_COLS_STREAM
-        (void)k1;
-        v[r] = C2<f2>{f2{b4.x, b4.z}, f2{b4.y, b4.w}};
-#else
-        const uint32_t m0 = (uint32_t)col * (uint32_t)k1;                 // n2 k1 < n <= 2^24
-        constexpr float inv_n = 1.0f / (float)n;                          // exact: power of two
-        const float r0 = (float)m0 * inv_n, r1 = (float)(m0 + (uint32_t)k1) * inv_n;
-        const C2<f2> w{f2{__builtin_amdgcn_cosf(r0), __builtin_amdgcn_cosf(r1)},
-                       f2{__builtin_amdgcn_sinf(r0), __builtin_amdgcn_sinf(r1)}};
-        v[r] = cmul(C2<f2>{f2{b4.x, b4.z}, f2{b4.y, b4.w}}, w);
-#endif
-    }
-#ifndef NW_ABL_COLS_STREAM
-    idft_br<f2, E>(v);
-#endif
-    using O = typename OutT<OUT, float>::type;
-    void* orow = reinterpret_cast<char*>(out) + (int64_t)(f0 + fl) * n * (int64_t)sizeof(O);
-    const uint32_t ooff = ((uint32_t)col + (uint32_t)u * N2) * (uint32_t)sizeof(O);
-    colp_passes<N1, N2, OUT, 0>(v, lds, u, cp, orow, ooff);
+    col_passes<V, N1, N2, OUT, 0>(v, lds, u, c, orow, ooff, col_tab<0, T>(tw...));
 }
 
 // tsplit for one n (fp64 column pass), from sincospi in fp64
@@ -1082,40 +961,20 @@ template <typename T, int N2, int E, int KIND>
 hipError_t launch_row_pass(const WDesc& d, int f0, int nf, int n1, const C2<T>* Xt, C2<T>* B, const int* kmax,
                            hipStream_t s) {
     void* tw = nullptr;
-    hipError_t e = fused_twiddles(N2, sizeof(T) == 4 ? NW_F32 : NW_F64, &tw);
+    hipError_t e = fused_twiddles(N2, kDtypeOf<T>, &tw);
     if (e != hipSuccess) return e;
-    const int rgs = nf < kRowTileF ? 1 : kRowGroup;   // few scales: one row per block, more blocks
+    const int rgs = row_group_of(nf);
     const BlockGrid g = block_grid_tile(n1 / rgs, nf, kRowTileF, kRowTileG);
     if (!g.ok) return hipErrorInvalidConfiguration;
     return nw_launch_lds(rows_kernel<T, N2, E, KIND>, (unsigned)g.blocks, N2 / E, kLdsBytes<T, N2, E>, s, d, f0, nf, n1,
                          rgs, Xt, B, kmax, reinterpret_cast<const C2<T>*>(tw));
 }
 
-// fp32: the column-pair kernel (C5 cols 4.02 -> 3.86 ms per 64-scale launch against the
-// single-column kernel, which fp64 keeps: its lanes already read and write 16 B)
-constexpr bool kColsPair = true;
+// V: fp32 on column pairs (kColPair, nw_shape.h)
 template <typename T, int N1, int N2>
 hipError_t launch_cols(int out_kind, int f0, int nf, const C2<T>* B, void* out, const C2<T>* tsplit, hipStream_t s) {
-    if constexpr (sizeof(T) == 4 && kColsPair && ColsP<N1>::CP >= 16 && N2 % ColsP<N1>::C == 0) {
-        using CL = ColsP<N1>;
-        const int lds = N1 * CL::C * (int)sizeof(float);
-        const int64_t blocks = (int64_t)nf * (N2 / CL::C);
-        const void* fn = out_kind == NW_OUT_CWT     ? (const void*)cols_kernel<N1, N2, NW_OUT_CWT>
-                         : out_kind == NW_OUT_POWER ? (const void*)cols_kernel<N1, N2, NW_OUT_POWER>
-                                                    : (const void*)cols_kernel<N1, N2, NW_OUT_ABS>;
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        if (out_kind == NW_OUT_CWT)
-            nw_launch(cols_kernel<N1, N2, NW_OUT_CWT>, (unsigned)blocks, CL::THREADS, lds, s, f0, nf, B, out);
-        else if (out_kind == NW_OUT_POWER)
-            nw_launch(cols_kernel<N1, N2, NW_OUT_POWER>, (unsigned)blocks, CL::THREADS, lds, s, f0, nf, B, out);
-        else
-            nw_launch(cols_kernel<N1, N2, NW_OUT_ABS>, (unsigned)blocks, CL::THREADS, lds, s, f0, nf, B, out);
-        return hipGetLastError();
-    }
-    using CL = Cols<T, N1>;
-    const int lds = N1 * CL::C * (int)sizeof(T);
-    const int64_t blocks = (int64_t)nf * (N2 / CL::C);
+    using V = std::conditional_t<kColPair<T>, f2, T>;
+    using CL = Cols<V, N1>;
     static_assert(N2 % CL::C == 0, "column groups");
     const C2<T>* tw1 = nullptr;
     if constexpr (sizeof(T) == 8) {
@@ -1124,58 +983,23 @@ hipError_t launch_cols(int out_kind, int f0, int nf, const C2<T>* B, void* out, 
         if (e != hipSuccess) return e;
         tw1 = reinterpret_cast<const C2<T>*>(tw);
     }
-    const void* fn = out_kind == NW_OUT_CWT     ? (const void*)cols_kernel<T, N1, N2, NW_OUT_CWT>
-                     : out_kind == NW_OUT_POWER ? (const void*)cols_kernel<T, N1, N2, NW_OUT_POWER>
-                                                : (const void*)cols_kernel<T, N1, N2, NW_OUT_ABS>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    if (out_kind == NW_OUT_CWT)
-        nw_launch(cols_kernel<T, N1, N2, NW_OUT_CWT>, (unsigned)blocks, kColThreads<T>, lds, s, f0, nf, B, out, tw1, tsplit);
-    else if (out_kind == NW_OUT_POWER)
-        nw_launch(cols_kernel<T, N1, N2, NW_OUT_POWER>, (unsigned)blocks, kColThreads<T>, lds, s, f0, nf, B, out, tw1, tsplit);
-    else
-        nw_launch(cols_kernel<T, N1, N2, NW_OUT_ABS>, (unsigned)blocks, kColThreads<T>, lds, s, f0, nf, B, out, tw1, tsplit);
-    return hipGetLastError();
+    return for_out_kind(out_kind, [&](auto o) {
+        constexpr int OUT = decltype(o)::value;
+        auto go = [&](auto kernel, auto... tables) {
+            return nw_launch_lds(kernel, (unsigned)((int64_t)nf * (N2 / CL::C)), CL::THREADS, CL::LDS, s, f0, nf, B, out,
+                                 tables...);
+        };
+        if constexpr (sizeof(T) == 8) return go(cols_kernel<V, N1, N2, OUT, ColTab<T>, ColTab<T>>, tw1, tsplit);
+        else return go(cols_kernel<V, N1, N2, OUT>);
+    });
 }
-
-// n = N1 * N2: N2 = min(n / 32, 16384) in both dtypes (kMaxN2), N1 = n / N2 >= 32
-struct Split {
-    int n1, n2;
-};
-Split split_of(int64_t n, int dtype) {
-    const int64_t maxn2 = dtype == NW_F32 ? kMaxN2<float> : kMaxN2<double>;
-    const int64_t n1 = n / maxn2 > 32 ? n / maxn2 : 32;
-    return {(int)n1, (int)(n / n1)};
-}
-
-size_t cplx_bytes(int dtype) { return dtype == NW_F32 ? sizeof(C2<float>) : sizeof(C2<double>); }
-
-int64_t fchunk_of(int64_t n, int nfreq, int dtype) {
-    const int64_t per = n * (int64_t)cplx_bytes(dtype);
-    int64_t fc = (int64_t)(kBBudget / (size_t)per);
-    if (const char* e = std::getenv("NW_LARGE_FCHUNK")) fc = std::atoll(e);   // diagnostics
-    if (fc < 1) fc = 1;
-    return fc < nfreq ? fc : nfreq;
-}
-
-// support buffer: kmax[nfreq] (padded to 256 B), then the fp64 split twiddles
-// support buffer: kmax (int) | row maxima (u64) | tsplit (fp64)
-size_t wmax_offset(int nfreq) { return ((size_t)nfreq * sizeof(int) + 255) / 256 * 256; }
-size_t tsplit_offset(int nfreq) { return wmax_offset(nfreq) + ((size_t)nfreq * sizeof(uint64_t) + 255) / 256 * 256; }
 
 }  // namespace
 
-bool large_supported(int64_t n, int dtype) {
-    return (dtype == NW_F32 || dtype == NW_F64) && n >= (int64_t(1) << 15) && n <= (int64_t(1) << 24) &&
-           !(n & (n - 1));
-}
-
 size_t large_scratch_bytes(int64_t n, int nfreq, int dtype) {
-    const size_t per = (size_t)n * cplx_bytes(dtype);
-    return per + (size_t)fchunk_of(n, nfreq, dtype) * per;   // Xt + B
+    const size_t per = (size_t)n * large_cplx_bytes(dtype);
+    return per + (size_t)large_fchunk(n, nfreq, dtype) * per;   // Xt + B
 }
-
-size_t large_support_bytes(int nfreq) { return tsplit_offset(nfreq) + kSplitEntries * sizeof(C2<double>); }
 
 // kmax[] and wmax[] of every row into `support`: the analytic kinds by support_fast_kernel,
 // the others (or scan = true: the full-scan reference the tests compare it with) by
@@ -1187,25 +1011,20 @@ hipError_t large_row_support(const WDesc& d, int dtype, void* support, bool scan
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(wmax, 0, (size_t)d.nfreq * sizeof(uint64_t), s);            // +0.0
     if (e != hipSuccess) return e;
+    const int64_t per_block = 256 * kSupBins;
+    const dim3 grid((unsigned)((d.n + per_block - 1) / per_block), (unsigned)d.nfreq);
     if (!scan && support_fast_ok(d, dtype)) {
-        if (dtype == NW_F32) nw_launch(support_fast_kernel<float>, d.nfreq, kFastThreads, 0, s, d, kmax, wmax);
-        else nw_launch(support_fast_kernel<double>, d.nfreq, kFastThreads, 0, s, d, kmax, wmax);
+        for_dtype(dtype, [&](auto t) {
+            nw_launch(support_fast_kernel<decltype(t)>, d.nfreq, kFastThreads, 0, s, d, kmax, wmax);
+        });
         return hipGetLastError();
     }
-    const int64_t per_block = 256 * kSupBins;
-    dim3 grid((unsigned)((d.n + per_block - 1) / per_block), (unsigned)d.nfreq);
-    const bool realw = d.kind != NW_TABLE;
-    if (dtype == NW_F32) {
-        if (realw) nw_launch(wmax_kernel<float, true>, grid, 256, 0, s, d, wmax);
-        else nw_launch(wmax_kernel<float, false>, grid, 256, 0, s, d, wmax);
-        if (realw) nw_launch(kmax_kernel<float, true>, grid, 256, 0, s, d, kmax, wmax);
-        else nw_launch(kmax_kernel<float, false>, grid, 256, 0, s, d, kmax, wmax);
-    } else {
-        if (realw) nw_launch(wmax_kernel<double, true>, grid, 256, 0, s, d, wmax);
-        else nw_launch(wmax_kernel<double, false>, grid, 256, 0, s, d, wmax);
-        if (realw) nw_launch(kmax_kernel<double, true>, grid, 256, 0, s, d, kmax, wmax);
-        else nw_launch(kmax_kernel<double, false>, grid, 256, 0, s, d, kmax, wmax);
-    }
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const bool realw = d.kind != NW_TABLE;
+        for_bool(realw, [&](auto rw) { nw_launch(wmax_kernel<T, decltype(rw)::value>, grid, 256, 0, s, d, wmax); });
+        for_bool(realw, [&](auto rw) { nw_launch(kmax_kernel<T, decltype(rw)::value>, grid, 256, 0, s, d, kmax, wmax); });
+    });
     return hipGetLastError();
 }
 
@@ -1218,24 +1037,27 @@ hipError_t build_large_support(const WDesc& d, int dtype, void* support, hipStre
     hipError_t e = large_row_support(d, dtype, support, force_scan, s);
     if (e != hipSuccess) return e;
     if (dtype == NW_F64) {
-        nw_launch(tsplit_kernel, kSplitEntries / 256, 256, 0, s, 
+        nw_launch(tsplit_kernel, kSplitEntries / 256, 256, 0, s,
             reinterpret_cast<C2<double>*>(reinterpret_cast<char*>(support) + tsplit_offset(d.nfreq)), d.n);
     }
     return hipGetLastError();
 }
 
-int64_t large_fchunk(int64_t n, int nfreq, int dtype) { return fchunk_of(n, nfreq, dtype); }
+// fchunk_of (nw_shape.h), or NW_LARGE_FCHUNK scales per launch pair (diagnostics)
+int64_t large_fchunk(int64_t n, int nfreq, int dtype) {
+    if (const char* e = std::getenv("NW_LARGE_FCHUNK")) return fchunk_clamp(std::atoll(e), nfreq);
+    return fchunk_of(n, nfreq, dtype);
+}
 
 // Xt of one signal (X: its R2C half spectrum) into the scratch's first n complex
 hipError_t large_transpose(const WDesc& d, int dtype, const void* X, void* scratch, hipStream_t s) {
-    const Split sp = split_of(d.n, dtype);
+    const Split sp = large_split(d.n);
     const dim3 grid((unsigned)(sp.n1 / 32), (unsigned)(sp.n2 / 32));
-    if (dtype == NW_F32)
-        nw_launch(xt_kernel<float>, grid, 256, 0, s, d, reinterpret_cast<const cplx<float>*>(X),
-                                              reinterpret_cast<C2<float>*>(scratch), sp.n1, sp.n2);
-    else
-        nw_launch(xt_kernel<double>, grid, 256, 0, s, d, reinterpret_cast<const cplx<double>*>(X),
-                                               reinterpret_cast<C2<double>*>(scratch), sp.n1, sp.n2);
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        nw_launch(xt_kernel<T>, grid, 256, 0, s, d, reinterpret_cast<const cplx<T>*>(X),
+                  reinterpret_cast<C2<T>*>(scratch), sp.n1, sp.n2);
+    });
     return hipGetLastError();
 }
 
@@ -1246,72 +1068,49 @@ bool morse_fast_of(const WDesc& d) {
     return d.kind == NW_MORSE && !d.morse_ovf && d.r == 3.0 && b2 >= 0.0 && b2 < 128.0 && b2 == (double)(int)b2;
 }
 
-template <typename T>
-hipError_t rows_t(const WDesc& d, int f0, int nf, const int* km, void* scratch, hipStream_t s) {
-    const Split sp = split_of(d.n, sizeof(T) == 4 ? NW_F32 : NW_F64);
-    C2<T>* Xt = reinterpret_cast<C2<T>*>(scratch);
-    C2<T>* B = Xt + d.n;
-#define NW_ROWS(NN)                                                                                          \
-    case NN:                                                                                                 \
-        if constexpr (NN <= kMaxN2<T>) {                                                                     \
-            constexpr int EE = kRowE<T, NN>;                                                                 \
-            switch (d.kind) {                                                                                \
-                case NW_MORSE:                                                                               \
-                    if constexpr (sizeof(T) == 8)                                                            \
-                        if (morse_fast_of(d))                                                                \
-                            return d.b == 17.5 ? (kRowsRec && d.off == 0 ? launch_row_pass<T, NN, EE, kMorseRec>(d, f0, nf, sp.n1, Xt, B, km, s) \
-                                                             : launch_row_pass<T, NN, EE, kMorseFast35>(d, f0, nf, sp.n1, Xt, B, km, s)) \
-                                               : launch_row_pass<T, NN, EE, kMorseFast>(d, f0, nf, sp.n1, Xt, B, km, s);  \
-                    if constexpr (sizeof(T) == 4)                                                            \
-                        if (d.morse_ovf) return launch_row_pass<T, NN, EE, kMorseOvf>(d, f0, nf, sp.n1, Xt, B, km, s); \
-                    return launch_row_pass<T, NN, EE, NW_MORSE>(d, f0, nf, sp.n1, Xt, B, km, s);             \
-                case NW_MORLET: return launch_row_pass<T, NN, EE, NW_MORLET>(d, f0, nf, sp.n1, Xt, B, km, s);   \
-                case NW_SHANNON: return launch_row_pass<T, NN, EE, NW_SHANNON>(d, f0, nf, sp.n1, Xt, B, km, s); \
-                case NW_TABLE: return launch_row_pass<T, NN, kRowETab<T, NN>, NW_TABLE>(d, f0, nf, sp.n1, Xt, B, km, s); \
-                default: return hipErrorNotSupported;                                                        \
-            }                                                                                                \
-        }                                                                                                    \
-        return hipErrorNotSupported;
-    switch (sp.n2) {
-        NW_ROWS(1024) NW_ROWS(2048) NW_ROWS(4096) NW_ROWS(8192) NW_ROWS(16384)
+// f(std::integral_constant<int, KIND>) for the row evaluator (RowW<T, KIND>) of a plan's wavelet
+template <typename T, typename F>
+hipError_t for_row_kind(const WDesc& d, F f) {
+    using std::integral_constant;
+    switch (d.kind) {
+        case NW_MORSE:
+            if constexpr (sizeof(T) == 8) {
+                if (morse_fast_of(d))
+                    return d.b == 17.5 ? (kRowsRec && d.off == 0 ? f(integral_constant<int, kMorseRec>{})
+                                                                 : f(integral_constant<int, kMorseFast35>{}))
+                                       : f(integral_constant<int, kMorseFast>{});
+            } else {
+                if (d.morse_ovf) return f(integral_constant<int, kMorseOvf>{});
+            }
+            return f(integral_constant<int, NW_MORSE>{});
+        case NW_MORLET: return f(integral_constant<int, NW_MORLET>{});
+        case NW_SHANNON: return f(integral_constant<int, NW_SHANNON>{});
+        case NW_TABLE: return f(integral_constant<int, NW_TABLE>{});
         default: return hipErrorNotSupported;
     }
-#undef NW_ROWS
-}
-
-template <typename T>
-hipError_t cols_t(const WDesc& d, int out_kind, int f0, int nf, const void* support, const void* scratch, void* out,
-                  hipStream_t s) {
-    const Split sp = split_of(d.n, sizeof(T) == 4 ? NW_F32 : NW_F64);
-    const C2<T>* B = reinterpret_cast<const C2<T>*>(scratch) + d.n;
-    const C2<T>* ts = sizeof(T) == 8 ? reinterpret_cast<const C2<T>*>(reinterpret_cast<const char*>(support) +
-                                                                      tsplit_offset(d.nfreq))
-                                     : nullptr;
-#define NW_COLS(A, BB) \
-    if (sp.n1 == A && sp.n2 == BB) return launch_cols<T, A, BB>(out_kind, f0, nf, B, out, ts, s);
-    if constexpr (sizeof(T) == 4) {
-        NW_COLS(32, 1024) NW_COLS(32, 2048) NW_COLS(32, 4096) NW_COLS(32, 8192) NW_COLS(32, 16384)
-        NW_COLS(64, 16384) NW_COLS(128, 16384) NW_COLS(256, 16384) NW_COLS(512, 16384) NW_COLS(1024, 16384)
-    } else {
-        NW_COLS(32, 1024) NW_COLS(32, 2048) NW_COLS(32, 4096) NW_COLS(32, 8192) NW_COLS(32, 16384)
-        NW_COLS(64, 16384) NW_COLS(128, 16384) NW_COLS(256, 16384) NW_COLS(512, 16384) NW_COLS(1024, 16384)
-    }
-    return hipErrorNotSupported;
-#undef NW_COLS
 }
 }  // namespace
 
 // pass 1 for scales [f0, f0 + nf): Xt -> B (both in the scratch)
 hipError_t large_rows(const WDesc& d, int dtype, int f0, int nf, const void* support, void* scratch, hipStream_t s) {
     const int* km = reinterpret_cast<const int*>(support);
-    return dtype == NW_F32 ? rows_t<float>(d, f0, nf, km, scratch, s) : rows_t<double>(d, f0, nf, km, scratch, s);
+    return for_large_split(d.n, dtype, hipErrorNotSupported, [&]<typename T, int N1, int N2>(LargeSplit<T, N1, N2>) {
+        C2<T>* Xt = reinterpret_cast<C2<T>*>(scratch);
+        return for_row_kind<T>(d, [&](auto kind) {
+            constexpr int KIND = decltype(kind)::value;
+            constexpr int E = KIND == NW_TABLE ? kRowETab<T, N2> : kRowE<T, N2>;
+            return launch_row_pass<T, N2, E, KIND>(d, f0, nf, N1, Xt, Xt + d.n, km, s);
+        });
+    });
 }
 
 // pass 2 for scales [f0, f0 + nf): B -> out rows (f, n) of one signal (out: its row 0)
 hipError_t large_cols(const WDesc& d, int dtype, int out_kind, int f0, int nf, const void* support,
                       const void* scratch, void* out, hipStream_t s) {
-    return dtype == NW_F32 ? cols_t<float>(d, out_kind, f0, nf, support, scratch, out, s)
-                           : cols_t<double>(d, out_kind, f0, nf, support, scratch, out, s);
+    return for_large_split(d.n, dtype, hipErrorNotSupported, [&]<typename T, int N1, int N2>(LargeSplit<T, N1, N2>) {
+        const C2<T>* ts = reinterpret_cast<const C2<T>*>(reinterpret_cast<const char*>(support) + tsplit_offset(d.nfreq));
+        return launch_cols<T, N1, N2>(out_kind, f0, nf, reinterpret_cast<const C2<T>*>(scratch) + d.n, out, ts, s);
+    });
 }
 
 }  // namespace nw

@@ -7,7 +7,12 @@
 //   - the one-pass size table (fused_e), its visitor and the decimated lengths;
 //   - block shapes (signals per block, XCD tiles) of the one-pass kernels;
 //   - the W-table layout, the support rounding and the pass-0 ladders;
-//   - which partial-sum kernels exist.
+//   - which partial-sum kernels exist;
+//   - the two-pass engine (nw_large.hip): the (N1, N2) split and its visitor, the row pass's
+//     elements per thread, rows per block, pass-0 ladder and LDS-DMA rule, the column pass's
+//     block shape, the scale chunk and the support buffer's layout (mode `large` prints them);
+//   - the chirp-z engine (nw_chirp.hip): the (dtype, M, E) table and its visitor, the lengths
+//     it takes and a row's M class.
 #pragma once
 
 #include <stddef.h>
@@ -265,5 +270,212 @@ template <typename T, int N, int EO>
 constexpr bool kPSumOK = !(sizeof(T) == 8 && N / kPsE<T, EO, false> > 512);
 template <typename T, int N, int EO>
 constexpr bool kPhSumOK = N / kPsE<T, EO, true> <= 512;
+
+// ---- the two-pass engine (nw_large.hip) -----------------------------------------------------
+
+// power-of-two 2^15 <= n <= 2^24, fp32 or fp64
+constexpr int kLargeLog2Min = 15, kLargeLog2Max = 24;
+constexpr bool large_supported(int64_t n, int dtype) {
+    return (dtype == NW_F32 || dtype == NW_F64) && n >= (int64_t(1) << kLargeLog2Min) &&
+           n <= (int64_t(1) << kLargeLog2Max) && !(n & (n - 1));
+}
+
+// rows of at most 16384 on chip, fp64 too (N2 = 8192 with N1 = 2048, 8-column blocks and
+// 128-B runs: C5 fp64 150.0 ms/step; 16384, 16 columns, 256-B runs: 129.9)
+// (fp32 rows of 32768 -- N1 = 512, 64-column workgroups writing 512-B output pieces -- measured
+// in round 6: the row pass at one 1024-thread block per CU +37-43 %, the column pass 0-3 %
+// faster, C5 step +10 %; profiles/r06_c5_rows32k_ab.txt)
+constexpr int kMaxN2 = 16384;
+// n = N1 * N2: N2 = min(n / 32, 16384) in both dtypes (kMaxN2), N1 = n / N2 >= 32
+struct Split {
+    int n1, n2;
+};
+constexpr Split large_split(int64_t n) {
+    const int64_t n1 = n / kMaxN2 > 32 ? n / kMaxN2 : 32;
+    return {(int)n1, (int)(n / n1)};
+}
+
+// One visitor over the splits: f(LargeSplit<T, N1, N2>{}) for (n, dtype), `miss` past them.
+template <typename T, int N1, int N2> struct LargeSplit {};
+template <typename T, int LG, typename R, typename F>
+inline R for_large_length(int64_t n, R miss, F& f) {
+    if constexpr (LG > kLargeLog2Max) {
+        return miss;
+    } else {
+        constexpr Split sp = large_split(int64_t(1) << LG);
+        if (n == (int64_t(1) << LG)) return f(LargeSplit<T, sp.n1, sp.n2>{});
+        return for_large_length<T, LG + 1>(n, miss, f);
+    }
+}
+template <typename R, typename F>
+inline R for_large_split(int64_t n, int dtype, R miss, F f) {
+    if (dtype == NW_F32) return for_large_length<float, kLargeLog2Min>(n, miss, f);
+    if (dtype == NW_F64) return for_large_length<double, kLargeLog2Min>(n, miss, f);
+    return miss;
+}
+
+// N2 (on-chip rows) and its elements per thread E, both dtypes: 32 from N2 = 8192 up, 16 below
+template <typename T, int N2> constexpr int kRowE = N2 >= 8192 ? 32 : 16;
+// complex table rows (wavelet_bin loads) spill at fp64 E = 32: E = 16 there
+template <typename T, int N2> constexpr int kRowETab = sizeof(T) == 8 ? 16 : kRowE<T, N2>;
+// rows (k1) per rows_kernel workgroup (XCD tile kRowTileF x kRowTileG above) ...
+constexpr int kRowGroup = 4;
+// ... of a launch over nf scales: 1 when it holds few scales (one row per block, more blocks)
+constexpr int row_group_of(int nf) { return nf < kRowTileF ? 1 : kRowGroup; }
+// Thread t of a row's N2 / E threads owns the bins k = k1 + n1 * (t + r * threads), r < E: with
+// km the scale's last bin in the support, elements r >= row_need are zero for every thread
+NW_SHAPE_HD constexpr NW_INLINE int row_need(int km, int k1, int n1, int threads) {
+    return km < k1 ? 1 : (km - k1) / n1 / threads + 1;
+}
+// pass-0 variants of a row in steps of 4 elements at fp32 E = 32 (fp64: 4, 8, 16, 24, E): the
+// row runs pass0_variant<E, kRowFine, (E > 16)>(row_need); table rows: more scratch
+template <typename T, int E, bool TABLE> constexpr bool kRowFine = E > 16 && sizeof(T) == 4 && !TABLE;
+// fp32 E = 32 rows: pruned Xt rows by LDS-DMA ahead of the stores (C5 50.6 -> 48.5 ms per step);
+// analytic kinds only (table rows' wavelet_bin loads would exceed 128 VGPRs, as in nw_fused);
+// fp64 rows with the same DMA measured no faster (0.94 -> 0.98 ms per launch; round 5, after the
+// W-evaluator changes: rows -0.5 %, step +1.4 %, profiles/r05_c5f64_rows_xd_ab.txt)
+// (fp64 rows with the DMA, re-measured in round 4 beside the fast Morse form: no gain either,
+// profiles/r04_c5f64_rows_ab.txt)
+template <typename T, int E, bool TABLE> constexpr bool kRowXD = sizeof(T) == 4 && E >= 32 && !TABLE;
+// ... for a row whose pass 0 reads only Xt[k1][0 .. N2/2): variants NZ <= kRowLdsNz
+template <int E> constexpr int kRowLdsNz = E / 2;
+
+// cols_kernel workgroups of 1024 threads: C = 32 columns at N1 = 1024, 256-B runs (C5 cols
+// 1.039 -> 0.978 ms per launch against 512 threads)
+// cols_kernel workgroup size (C * N1 / E)
+// fp64: 512 threads x 32 elements (N1 = 1024 in 2 passes, one exchange; 16 columns, 256-B runs
+// as before) against 1024 x 16 (3 passes, two exchanges): C5 fp64 cols 3.97-4.11 -> 3.90-3.91
+// ms per 32-scale launch (profiles/r05_c5f64_cols_e32_ab.txt; -DNW_COLS64_E16: the old form)
+#ifdef NW_COLS64_E16
+template <typename T> constexpr int kColThreads = 1024;
+#else
+template <typename T> constexpr int kColThreads = sizeof(T) == 8 ? 512 : 1024;
+#endif
+// elements per thread in cols_kernel: 32 complex fp32 (64 VGPRs) or fp64 (128 VGPRs, 2 waves/SIMD)
+#ifdef NW_COLS64_E16
+template <typename T> constexpr int kColE = sizeof(T) == 4 ? 32 : 16;
+#else
+template <typename T> constexpr int kColE = 32;
+#endif
+// fp32: the column-pair form (C5 cols 4.02 -> 3.86 ms per 64-scale launch against the
+// single-column form, which fp64 keeps: its lanes already read and write 16 B;
+// -DNW_COLS32_SINGLE: fp32 on the single-column form, diagnostic A/B)
+#ifdef NW_COLS32_SINGLE
+template <typename T> constexpr bool kColPair = false;
+#else
+template <typename T> constexpr bool kColPair = sizeof(T) == 4;
+#endif
+// The column pass's block: a thread owns one slot (CPS adjacent columns n2, one lane value) and
+// E of a column's N1 points; a workgroup transforms C consecutive columns.  PAIR (fp32): two
+// columns per slot at E = 16 -- length-N1 transforms at E = 16 take one exchange more than
+// E = 32.  (E = 32 with 512-thread workgroups: one exchange instead of two, 198 VGPRs at
+// 2 waves/SIMD: C5 cols 3.92 -> 3.95 ms per launch, not kept; profiles/r04_c5_colpairs_ab.txt)
+template <typename T, bool PAIR, int N1> struct ColShape {
+    static constexpr int E = PAIR ? 16 : kColE<T>;
+    static constexpr int THREADS = PAIR ? 1024 : kColThreads<T>;
+    static constexpr int U = N1 / E;                 // threads per slot
+    static constexpr int SLOTS = THREADS / U;        // slots per workgroup
+    static constexpr int CPS = PAIR ? 2 : 1;         // columns per slot
+    static constexpr int C = SLOTS * CPS;            // columns per workgroup
+    static constexpr int LDS = N1 * C * (int)sizeof(T);   // one real component of every point
+    static_assert(N1 >= 32 && SLOTS >= (sizeof(T) == 4 ? 16 : 4), "cols geometry");
+};
+
+// bytes of B per launch pair (scales chunked to fit): 8 GiB = 64 scales of fp32 / 32 of fp64 at
+// C5.  Against 2 GiB (16 / 8 scales): C5 fp32 47.49 -> 46.15 ms per step, fp64 118.19 -> 113.15
+// (fewer, longer launches: the row pass's XCD tiles of 8 scales fill, fewer tails;
+// profiles/r04_c5_fchunk.txt)
+constexpr size_t kBBudget = size_t(8) << 30;
+constexpr size_t large_cplx_bytes(int dtype) { return dtype == NW_F32 ? 8 : 16; }
+// scales per launch pair: fc of them (at least one, at most all), by default what the budget holds
+constexpr int64_t fchunk_clamp(int64_t fc, int nfreq) { return fc < 1 ? 1 : fc < nfreq ? fc : nfreq; }
+constexpr int64_t fchunk_of(int64_t n, int nfreq, int dtype) {
+    return fchunk_clamp((int64_t)(kBBudget / ((size_t)n * large_cplx_bytes(dtype))), nfreq);
+}
+
+// fp64 pass-0 twiddles w_n^m (m = n2 k1 < n) as the product of two exact entries:
+// tsplit[m & 4095] = w_n^(m mod 4096) and tsplit[4096 + (m >> 12)] = w_n^(4096 (m >> 12))
+constexpr int kSplitLo = 4096;
+constexpr int kSplitEntries = 2 * kSplitLo;   // n <= 2^24: m >> 12 < 4096
+// support buffer: kmax (int, padded to 256 B) | row maxima (u64) | tsplit (complex fp64)
+constexpr size_t wmax_offset(int nfreq) { return ((size_t)nfreq * sizeof(int) + 255) / 256 * 256; }
+constexpr size_t tsplit_offset(int nfreq) {
+    return wmax_offset(nfreq) + ((size_t)nfreq * sizeof(uint64_t) + 255) / 256 * 256;
+}
+constexpr size_t large_support_bytes(int nfreq) { return tsplit_offset(nfreq) + kSplitEntries * 2 * sizeof(double); }
+
+// ---- the chirp-z engine (nw_chirp.hip) ------------------------------------------------------
+
+// (dtype, M) -> E of the chirp engine: fp32 M <= 16384 (E = 32 at 16384), fp64 M <= 8192;
+// 0: no such kernel.  M = 1024 << c, c < kChirpClasses
+constexpr int kChirpClasses = 5;
+constexpr int64_t chirp_mmax(int dtype) { return dtype == NW_F32 ? 16384 : 8192; }
+constexpr int chirp_e(int64_t m, int dtype) {
+    if (dtype != NW_F32 && dtype != NW_F64) return 0;
+    if (m < 1024 || m > chirp_mmax(dtype) || (m & (m - 1))) return 0;
+    return m == 16384 ? 32 : 16;
+}
+// fp32 M = 8192: |y| and |y|^2 at E = 32 (256 threads, two blocks per CU, 3 passes, no
+// scratch): measured N = 4097 power 10.60 -> 8.75 ms, N = 3001 6.60 -> 5.82 ms per launch;
+// the complex output spills at E = 32 (108-128 B) and keeps E = 16
+template <typename T, int M, int E> constexpr int kChirpAbsE = (sizeof(T) == 4 && M == 8192) ? 32 : E;
+
+// One visitor over the table: f(ChirpSize<T, M, E>{}) for the row of (m, dtype), `miss` past it.
+template <typename T, int M, int E> struct ChirpSize {};
+template <typename T, int C, typename R, typename F>
+inline R for_chirp_class(int64_t m, R miss, F& f) {
+    if constexpr (C >= kChirpClasses || chirp_e(1024 << C, kDtypeOf<T>) == 0) {
+        return miss;
+    } else {
+        if (m == (1024 << C)) return f(ChirpSize<T, (1024 << C), chirp_e(1024 << C, kDtypeOf<T>)>{});
+        return for_chirp_class<T, C + 1>(m, miss, f);
+    }
+}
+template <typename R, typename F>
+inline R for_chirp_size(int64_t m, int dtype, R miss, F f) {
+    if (dtype == NW_F32) return for_chirp_class<float, 0>(m, miss, f);
+    if (dtype == NW_F64) return for_chirp_class<double, 0>(m, miss, f);
+    return miss;
+}
+
+// the full transform length of n: M = 2^ceil(log2(2n - 1)), at least 1024
+constexpr int64_t chirp_m(int64_t n) {
+    int64_t m = 1024;
+    while (m < 2 * n - 1) m <<= 1;
+    return m;
+}
+// any n with 2n - 1 <= M_max that the power-of-two kernels do not take
+constexpr bool chirp_supported(int64_t n, int dtype) {
+    if (n < 1 || fused_supported(n, dtype)) return false;
+    return (dtype == NW_F32 || dtype == NW_F64) && 2 * n - 1 <= chirp_mmax(dtype);
+}
+// longer lengths (up to M_max - 1) fit when every row's support does (M >= n + K - 1)
+constexpr bool chirp_possible(int64_t n, int dtype) {
+    if (n < 1 || fused_supported(n, dtype) || (dtype != NW_F32 && dtype != NW_F64)) return false;
+    return n < chirp_mmax(dtype);
+}
+// The M class c (M = 1024 << c) of a row of length n whose support is ksup bins: M >= n + K - 1
+// wrap-free, >= 2K for the pruned first pass 0, >= 1024, <= the full 2^ceil(log2(2n - 1)) and
+// M_max; -1: wider than the largest on-chip transform
+constexpr int chirp_class(int64_t n, int64_t ksup, int dtype) {
+    const int64_t mfull = chirp_m(n) < chirp_mmax(dtype) ? chirp_m(n) : chirp_mmax(dtype);
+    const int64_t wrap = n + (ksup > 1 ? ksup : 1) - 1;
+    const int64_t need = wrap > 2 * ksup ? wrap : 2 * ksup;
+    if (need > mfull) return -1;
+    int c = 0;
+    while ((int64_t(1024) << c) < need) ++c;
+    return c;
+}
+// Epoch partial sums on the chirp-z form: every M class of the wavelet needs a partial-sum
+// kernel without scratch (tools/regs.py): fp32 M <= 8192 (E = 16), fp64 power every M, fp64
+// phases M <= 2048 (44-60 B of scratch above)
+constexpr bool chirp_psum_ok(int dtype, bool phase, const int64_t* counts) {
+    for (int c = 0; c < kChirpClasses; ++c) {
+        if (counts[c] == 0) continue;
+        const int64_t m = int64_t(1024) << c;
+        if (dtype == NW_F32 ? m > 8192 : (phase && m > 2048)) return false;
+    }
+    return true;
+}
 
 }  // namespace nw

@@ -2,7 +2,10 @@
 // built with -fsanitize=address,undefined by tests/test_host_asan.py.
 //   host_asan self      : invariant checks of group_rows / block_of / parallel_copy / advise_output /
 //                         normal_rows / row_view_layout / stock_params, and of the kernels' launch
-//                         geometry (nw_shape.h): grid <-> block mapping, size table, limits
+//                         geometry (nw_shape.h): grid <-> block mapping, size table, limits, the
+//                         two-pass splits and grids, the chirp-z lengths and M classes
+//   host_asan large     : the two-pass rules (split, row E, pass-0 ladder, rows per block, need,
+//                         LDS-DMA rule) per dtype, n and row kind, one line each
 //   host_asan grid      : stdin "real_length sfreq interpolate" -> "len_valid len_full delta"
 //   host_asan shapes    : the size table's rules (E, pass-0 ladders, support rounding, partial
 //                         sums, decimated lengths), one line each
@@ -255,6 +258,126 @@ static void shape_checks() {
     CHECK(reinterpret_cast<const char*>(wtab_wnz(buf, 3, 1, 4, false)) == buf + 32);
 }
 
+// ---- the two-pass and chirp-z rules (nw_shape.h)
+
+// The column grid of one form (nf x N2 / C blocks, THREADS threads of E elements) covers every
+// (scale, n2, n1) exactly once.  The mapping is a product of three independent ones -- block ->
+// (scale, column group), thread slot -> column within the group, (thread, element) -> n1 -- so
+// each factor is checked exhaustively; and the largest lane byte offsets fit 32 bits.
+template <typename T, bool PAIR, int N1, int N2>
+static void check_cols() {
+    using CL = nw::ColShape<T, PAIR, N1>;
+    CHECK(N2 % CL::C == 0 && CL::THREADS == CL::SLOTS * CL::U && CL::U * CL::E == N1 && CL::THREADS <= 1024);
+    CHECK(CL::LDS == N1 * CL::SLOTS * CL::CPS * (int)sizeof(T) && CL::LDS <= 160 * 1024);
+    const int ngroups = N2 / CL::C;
+    for (int nf : {1, 7, 8, 9}) {
+        std::vector<int> hit((size_t)nf * ngroups, 0);
+        for (int b = 0; b < nf * ngroups; ++b) hit[(size_t)(b / ngroups) * ngroups + b % ngroups]++;
+        for (int h : hit) CHECK(h == 1);
+    }
+    std::vector<int> col(CL::C, 0), n1(N1, 0);
+    for (int t = 0; t < CL::THREADS; ++t) {
+        const int c = t % CL::SLOTS, u = t / CL::SLOTS;
+        if (u == 0)
+            for (int j = 0; j < CL::CPS; ++j) col[CL::CPS * c + j]++;
+        if (c == 0)
+            for (int r = 0; r < CL::E; ++r) n1[u + CL::U * r]++;
+    }
+    for (int h : col) CHECK(h == 1);
+    for (int h : n1) CHECK(h == 1);
+    // B: ((k1 * N2 + col) complex values; out: (col + n1 * N2) values of at most a complex
+    const uint64_t last = (uint64_t)(N1 - 1) * N2 + (N2 - 1);
+    CHECK(last * 2 * sizeof(T) + 2 * sizeof(T) * CL::CPS <= (uint64_t(1) << 32));
+}
+
+static void large_checks() {
+    using namespace nw;
+    for (int dtype : {NW_F32, NW_F64}) {
+        for (int lg = 15; lg <= 24; ++lg) {
+            const int64_t n = int64_t(1) << lg;
+            const Split sp = large_split(n);
+            CHECK(large_supported(n, dtype));
+            CHECK((int64_t)sp.n1 * sp.n2 == n && sp.n1 >= 32 && sp.n1 <= 1024 && sp.n2 <= 16384);
+            const int64_t seen = for_large_split(n, dtype, int64_t(-1), []<typename T, int N1, int N2>(LargeSplit<T, N1, N2>) {
+                check_cols<T, false, N1, N2>();
+                if constexpr (sizeof(T) == 4) check_cols<T, true, N1, N2>();
+                // the row grid: block_slot onto scales x row groups, each group rgs whole rows
+                for (int nf : {1, 7, 8, 9}) {
+                    const int rgs = row_group_of(nf);
+                    CHECK(rgs == (nf < 8 ? 1 : 4) && N1 % rgs == 0);
+                    check_grid(block_grid_tile(N1 / rgs, nf, kRowTileF, kRowTileG), N1 / rgs, nf, kRowTileF);
+                }
+                return ((int64_t)sizeof(T) << 40) | ((int64_t)N1 << 20) | N2;
+            });
+            CHECK(seen == (((int64_t)(dtype == NW_F32 ? 4 : 8) << 40) | ((int64_t)sp.n1 << 20) | sp.n2));
+        }
+        for (int64_t n : {int64_t(1) << 14, int64_t(1) << 25, int64_t(3) << 15, (int64_t(1) << 20) + 1}) {
+            CHECK(!large_supported(n, dtype));
+            CHECK(for_large_split(n, dtype, -1, []<typename T, int N1, int N2>(LargeSplit<T, N1, N2>) { return 0; }) == -1);
+        }
+    }
+    CHECK(!large_supported(1 << 20, 7) && for_large_split(1 << 20, 7, -1, [](auto) { return 0; }) == -1);
+    // the support buffer's sections ascend, 256-B aligned
+    for (int nfreq : {1, 63, 64, 65, 512}) {
+        CHECK(wmax_offset(nfreq) >= (size_t)nfreq * 4 && wmax_offset(nfreq) % 256 == 0);
+        CHECK(tsplit_offset(nfreq) >= wmax_offset(nfreq) + (size_t)nfreq * 8 && tsplit_offset(nfreq) % 256 == 0);
+        CHECK(large_support_bytes(nfreq) == tsplit_offset(nfreq) + (size_t)kSplitEntries * 16);
+    }
+    CHECK(fchunk_of(1 << 24, 512, NW_F32) == 64 && fchunk_of(1 << 24, 512, NW_F64) == 32 && fchunk_of(1 << 15, 3, NW_F32) == 3);
+    CHECK(fchunk_clamp(0, 5) == 1 && fchunk_clamp(-3, 5) == 1 && fchunk_clamp(9, 5) == 5 && fchunk_clamp(2, 5) == 2);
+}
+
+static void chirp_checks() {
+    using namespace nw;
+    for (int dtype : {NW_F32, NW_F64}) {
+        const int64_t mmax = chirp_mmax(dtype);
+        for (int64_t n = 1; n <= 16383; ++n) {
+            std::vector<int64_t> ks = {0, 1, n};
+            for (int64_t m = 1024; m <= 16384; m *= 2)
+                for (int64_t d = -1; d <= 1; ++d) {
+                    ks.push_back(m / 2 + d);         // M >= 2K
+                    ks.push_back(m - n + 1 + d);     // M >= n + K - 1
+                }
+            const int64_t top = std::min(chirp_m(n), mmax);
+            for (int64_t k : ks) {
+                if (k < 0 || k > n) continue;
+                const int64_t need = std::max(n + std::max<int64_t>(k, 1) - 1, 2 * k);
+                int want = -1;
+                for (int c = kChirpClasses - 1; c >= 0; --c)
+                    if ((int64_t(1024) << c) >= need && (int64_t(1024) << c) <= top) want = c;
+                CHECK(chirp_class(n, k, dtype) == want);
+            }
+        }
+        for (int64_t m = 512; m <= 32768; m *= 2) {
+            const int e = chirp_e(m, dtype);
+            CHECK(e == (m >= 1024 && m <= mmax ? (m == 16384 ? 32 : 16) : 0));
+            const int seen = for_chirp_size(m, dtype, -1, []<typename T, int M, int E>(ChirpSize<T, M, E>) {
+                return (int)sizeof(T) * 100000 + M / E;
+            });
+            CHECK(seen == (e ? (dtype == NW_F32 ? 4 : 8) * 100000 + (int)m / e : -1));
+        }
+        CHECK(for_chirp_size(3000, dtype, -1, [](auto) { return 0; }) == -1);
+    }
+    CHECK((kChirpAbsE<float, 8192, 16>) == 32 && (kChirpAbsE<float, 4096, 16>) == 16 && (kChirpAbsE<double, 8192, 16>) == 16);
+    // the lengths tests/test_gpu_chirp.py runs, against the definitions
+    const int64_t f32n[] = {1, 2, 3, 5, 21, 300, 301, 512, 1000, 1021, 1201, 2049, 3001, 4097, 8191, 10001, 14001, 701};
+    const int64_t f64n[] = {1, 3, 21, 300, 301, 1000, 1201, 2049, 4095, 5001, 4097, 701};
+    for (int dtype : {NW_F32, NW_F64}) {
+        std::vector<int64_t> ns = dtype == NW_F32 ? std::vector<int64_t>(std::begin(f32n), std::end(f32n))
+                                                  : std::vector<int64_t>(std::begin(f64n), std::end(f64n));
+        for (int64_t n : {1024, 4096, 16384, 8192, 16383, 8193, 0, -5}) ns.push_back(n);
+        for (int64_t n : ns) {
+            const bool pow2 = n >= 1024 && n <= 16384 && (n & (n - 1)) == 0;
+            CHECK(chirp_supported(n, dtype) == (n >= 1 && !pow2 && 2 * n - 1 <= chirp_mmax(dtype)));
+            CHECK(chirp_possible(n, dtype) == (n >= 1 && !pow2 && n < chirp_mmax(dtype)));
+        }
+    }
+    CHECK(!chirp_supported(1201, 7) && !chirp_possible(1201, 7));
+    const int64_t one_big[kChirpClasses] = {0, 0, 0, 0, 1}, small[kChirpClasses] = {3, 1, 0, 0, 0}, mid[kChirpClasses] = {0, 0, 1, 1, 0};
+    CHECK(!chirp_psum_ok(NW_F32, false, one_big) && chirp_psum_ok(NW_F32, true, mid) && chirp_psum_ok(NW_F64, false, mid));
+    CHECK(!chirp_psum_ok(NW_F64, true, mid) && chirp_psum_ok(NW_F64, true, small));
+}
+
 static const char* out_name(int out) { return out == NW_OUT_CWT ? "cwt" : out == NW_OUT_POWER ? "power" : "abs"; }
 
 template <typename T, int N, int E, int OUT>
@@ -310,8 +433,50 @@ static void print_shapes() {
     }
 }
 
+// the two-pass rules of one (dtype, n, analytic or table rows), one line each, for
+// tests/test_host_asan.py to compare with tests/large_variants.py
+static const int kNeedCases[][2] = {{-1, 0}, {0, 0}, {0, 5}, {31, 31}, {32, 0}, {1000, 3}, {65535, 1}, {65536, 0},
+                                    {1 << 20, 31}, {(1 << 24) - 1, 0}, {(1 << 24) - 1, 1023}};   // (km, k1)
+template <typename T, int N1, int N2, bool TABLE>
+static void print_large_rows() {
+    constexpr int E = TABLE ? nw::kRowETab<T, N2> : nw::kRowE<T, N2>;
+    const char* dt = sizeof(T) == 4 ? "float32" : "float64";
+    const char* kd = TABLE ? "table" : "analytic";
+    const long long n = (long long)N1 * N2;
+    std::printf("split %s %lld %s %d %d\n", dt, n, kd, N1, N2);
+    std::printf("rowe %s %lld %s %d\n", dt, n, kd, E);
+    std::vector<int> lad;
+    for (int nz = 1; nz <= E; ++nz) {
+        const int v = nw::pass0_variant<E, nw::kRowFine<T, E, TABLE>, (E > 16)>(nz);
+        if (lad.empty() || lad.back() != v) lad.push_back(v);
+    }
+    std::printf("ladder %s %lld %s", dt, n, kd);
+    for (int v : lad) std::printf(" %d", v);
+    std::printf("\nrowgroup %s %lld %s", dt, n, kd);
+    for (int nf = 1; nf <= 16; ++nf) std::printf(" %d", nw::row_group_of(nf));
+    std::printf("\nneed %s %lld %s", dt, n, kd);
+    for (const auto& c : kNeedCases)
+        if (c[0] < n && c[1] < N1) std::printf(" %d", nw::row_need(c[0], c[1], N1, N2 / E));
+    std::printf("\nxd %s %lld %s", dt, n, kd);
+    for (int v : lad) std::printf(" %d", (int)(nw::kRowXD<T, E, TABLE> && v <= nw::kRowLdsNz<E>));
+    std::printf("\n");
+}
+static void print_large() {
+    for (int dtype : {NW_F32, NW_F64})
+        for (int lg = nw::kLargeLog2Min; lg <= nw::kLargeLog2Max; ++lg)
+            nw::for_large_split(int64_t(1) << lg, dtype, 0, []<typename T, int N1, int N2>(nw::LargeSplit<T, N1, N2>) {
+                print_large_rows<T, N1, N2, false>();
+                print_large_rows<T, N1, N2, true>();
+                return 1;
+            });
+}
+
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "self";
+    if (mode == "large") {
+        print_large();
+        return 0;
+    }
     if (mode == "shapes") {
         print_shapes();
         return 0;
@@ -329,6 +494,8 @@ int main(int argc, char** argv) {
     }
     self_checks();
     shape_checks();
+    large_checks();
+    chirp_checks();
     std::printf("%s\n", g_fail ? "FAIL" : "ok");
     return g_fail ? 1 : 0;
 }

@@ -84,6 +84,41 @@ def test_python_restatement_matches_the_shape_header(host_asan):
     assert psum == 20 and sum(w is not None and w.startswith('decim') for w in want) == 20
 
 
+NEED_CASES = [(-1, 0), (0, 0), (0, 5), (31, 31), (32, 0), (1000, 3), (65535, 1), (65536, 0), (1 << 20, 31),
+              ((1 << 24) - 1, 0), ((1 << 24) - 1, 1023)]          # (km, k1), as host_asan.cpp's kNeedCases
+
+
+def test_large_variants_matches_the_shape_header(host_asan):
+    """tests/large_variants.py (split, row_elems, ladder, row_group, need, from_lds: the rules the
+    GPU tests use to steer rows of the two-pass form into every variant) line by line against
+    what nw_shape.h gives for every dtype, n = 2^15 .. 2^24 and analytic or table rows."""
+    import large_variants as V
+    r = subprocess.run([host_asan, 'large'], capture_output=True, text=True, env=ENV, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    want = []
+    for dtype in ('float32', 'float64'):
+        for lg in range(15, 25):
+            n = 1 << lg
+            n1, n2 = V.split(n)
+            for table in (False, True):
+                tag = f'{dtype} {n} {"table" if table else "analytic"}'
+                e = V.row_elems(n2, dtype, table)
+                lad = sorted(V.ladder(e, dtype, table))
+                # the ladder, walked as the kernel walks it: the variant of every nd = 1 .. E
+                assert sorted({V.variant(nd, lad) for nd in range(1, e + 1)}) == lad
+                want.append(f'split {tag} {n1} {n2}')
+                want.append(f'rowe {tag} {e}')
+                want.append(f'ladder {tag} ' + ' '.join(map(str, lad)))
+                want.append(f'rowgroup {tag} ' + ' '.join(str(V.row_group(nf)) for nf in range(1, 17)))
+                want.append(f'need {tag} ' + ' '.join(str(V.need(km, k1, n1, n2 // e))
+                                                      for km, k1 in NEED_CASES if km < n and k1 < n1))
+                want.append(f'xd {tag} ' + ' '.join(str(int(V.from_lds(e, dtype, table, nz))) for nz in lad))
+    got = r.stdout.splitlines()
+    assert len(got) == len(want) == 2 * 10 * 2 * 6
+    for g, w in zip(got, want):
+        assert g == w
+
+
 def test_trans_grid_under_asan_matches_numpy(host_asan):
     """nw::host::trans_grid (the nw_trans_grid body) against numpy's arange length
     (base.py:191-194, 238-245) on random (N, sfreq, interpolate)."""
