@@ -93,6 +93,13 @@ extern "C" {
 #define NW_OUT_POWER_SUM  5  /* float64 (F, N): sum_s |y|^2 (partial sums to combine over
                                 devices or ranks, then divide by the total count) */
 #define NW_OUT_PHASE_SUM  6  /* complex128 (F, N): sum_s y/|y| (partial sums; ITC = |sum/S|) */
+/* Cross-channel reductions over the npairs signal pairs (a_e, b_e) of nw_execute_pair (no
+ * reference counterpart: connectivity from the per-epoch CWT), summed in pair order in fp64 on
+ * the device; nw_execute and nw_execute_multi* do not take them. */
+#define NW_OUT_CROSS_SUM  7  /* float64 (F, N, 4): {Re S_ab, Im S_ab, P_aa, P_bb} per point with
+                                S_ab = sum_e y_a,e conj(y_b,e), P_aa = sum_e |y_a,e|^2 */
+#define NW_OUT_PLV_SUM    8  /* complex128 (F, N): sum_e (y_a,e/|y_a,e|) conj(y_b,e/|y_b,e|);
+                                some |y| = 0 gives NaN there, as NW_OUT_ITC */
 
 /* memory placement of x / out in nw_execute */
 #define NW_MEM_HOST   0
@@ -133,7 +140,13 @@ typedef struct nw_stats {
                                reduction buffers, wavelet tables, two-pass scratch, rocFFT work
                                (it grows as calls need larger buffers; the Python classes
                                bound their plan cache by it) */
+    int64_t reduce_path;    /* NW_REDUCE_*: how the last reduction executed formed its sums */
 } nw_stats;
+
+/* nw_stats.reduce_path */
+#define NW_REDUCE_NONE     0   /* no reduction executed yet                                     */
+#define NW_REDUCE_ROWS     1   /* per-signal rows per chunk, added in signal order in fp64     */
+#define NW_REDUCE_PARTIALS 2   /* fp64 block partial sums inside the transform kernel          */
 
 /* nw_stats.kernel: which kernel wrote the output rows (the dominant kernel of a step) */
 #define NW_K_NONE        0
@@ -175,6 +188,15 @@ int nw_fused_supported(int64_t n, int dtype);
  * decim >= 2 with n / decim >= 1024, fp32 or fp64.  The reference's decim is the one
  * MorseMNE.cwt passes through to MNE (wavelets.py:170-191). */
 int nw_decim_supported(int64_t n, int dtype, int decim);
+
+/* Host-only (no GPU): whether nw_execute_pair of a plan of (n, dtype) whose wavelet is of
+ * `kind` forms the sums of out_kind (NW_OUT_CROSS_SUM / NW_OUT_PLV_SUM) as block partial sums
+ * inside the transform kernel (nw_stats.reduce_path = NW_REDUCE_PARTIALS); elsewhere the
+ * per-signal rows of each chunk are reduced (NW_REDUCE_ROWS).  1 for fp32, n = 1024 / 2048 /
+ * 4096 and the analytic kinds (NW_MORSE, NW_MORLET, NW_SHANNON); plans with decim > 1 or repeated
+ * rows keep the chunk path.  The same terms are added either way (regrouped fp64 additions; the
+ * unit phasors of NW_OUT_PLV_SUM by rsqrt instead of hypot and divide, a few fp64 ulp). */
+int nw_pair_partials_supported(int64_t n, int dtype, int kind, int out_kind);
 
 /* Create a plan for signals of n samples, up to max_batch signals per device
  * chunk, nfreq scales.  flags: NW_INTERPOLATE | NW_ENGINE_* | NW_TIMING. */
@@ -230,6 +252,16 @@ int nw_plan_row_support(nw_plan* plan, int method, int32_t* kmax_out);
  * NW_MEM_DEVICE: x/out are device pointers on the plan's device, the call is
  * asynchronous on the plan stream (see nw_plan_sync). */
 int nw_execute(nw_plan* plan, const void* x, int64_t nsig, void* out, int out_kind, int mem);
+
+/* Cross-channel epoch reductions: the CWT rows y_a,e of xa[e] and y_b,e of xb[e] (both
+ * (npairs, n) of the plan dtype) reduced over e = 0 .. npairs-1 into out, NW_OUT_CROSS_SUM
+ * (float64 (F, n_out, 4)) or NW_OUT_PLV_SUM (complex128 (F, n_out)); every sum in fp64, in pair
+ * order; (npairs, F, N) is never materialised.  The plan stages the inputs interleaved
+ * a0, b0, a1, b1, ... into its own buffer, max_batch / 2 pairs per chunk, so max_batch must
+ * be >= 2 (NW_E_INVALID).  mem as in nw_execute (host: synchronous; device: asynchronous on
+ * the plan stream).  npairs = 0 gives zero sums.  A decimated plan reduces its n / decim rows. */
+int nw_execute_pair(nw_plan* plan, const void* xa, const void* xb, int64_t npairs, void* out,
+                    int out_kind, int mem);
 
 /* Shard nsig host signals over nplans plans (one per device, identical config),
  * one host thread per plan; balanced contiguous blocks (nsig / nplans signals, one

@@ -38,6 +38,8 @@ NW_NO_DEDUP = 0x200
 NW_NO_CHIRP = 0x400
 NW_OUT_CWT, NW_OUT_ABS, NW_OUT_POWER = 0, 1, 2
 NW_OUT_POWER_MEAN, NW_OUT_ITC, NW_OUT_POWER_SUM, NW_OUT_PHASE_SUM = 3, 4, 5, 6
+NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM = 7, 8          # nw_execute_pair only
+NW_REDUCE_NONE, NW_REDUCE_ROWS, NW_REDUCE_PARTIALS = 0, 1, 2   # nw_stats.reduce_path
 NW_MEM_HOST, NW_MEM_DEVICE = 0, 1
 # nw_stats.kernel -> the kernel name rocprofv3 shows
 KERNEL_NAMES = {0: None, 1: 'nw_fused_kernel', 2: 'nw_fused_pair_kernel', 3: 'nw_chirp_kernel',
@@ -58,7 +60,8 @@ class nw_stats(ctypes.Structure):
                 ('engine', ctypes.c_int64), ('ms_rows', ctypes.c_double),
                 ('launches_rows', ctypes.c_int64), ('ms_expand', ctypes.c_double),
                 ('launches_expand', ctypes.c_int64), ('unique_rows', ctypes.c_int64),
-                ('kernel', ctypes.c_int64), ('device_bytes', ctypes.c_int64)]
+                ('kernel', ctypes.c_int64), ('device_bytes', ctypes.c_int64),
+                ('reduce_path', ctypes.c_int64)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -78,6 +81,7 @@ SIGNATURES = [
     ('nw_fused_supported', ctypes.c_int, [_I64, ctypes.c_int]),
     ('nw_decim_supported', ctypes.c_int, [_I64, ctypes.c_int, ctypes.c_int]),
     ('nw_plan_set_decim', ctypes.c_int, [_P, ctypes.c_int]),
+    ('nw_pair_partials_supported', ctypes.c_int, [_I64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ('nw_plan_create', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _I64, _I64, ctypes.c_int32,
                                       ctypes.c_int, ctypes.c_uint32]),
     ('nw_plan_set_wavelet', ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
@@ -87,6 +91,7 @@ SIGNATURES = [
     ('nw_plan_wavelet_rows', ctypes.c_int, [_P, _P]),
     ('nw_plan_row_support', ctypes.c_int, [_P, ctypes.c_int, _P]),
     ('nw_execute', ctypes.c_int, [_P, _P, _I64, _P, ctypes.c_int, ctypes.c_int]),
+    ('nw_execute_pair', ctypes.c_int, [_P, _P, _P, _I64, _P, ctypes.c_int, ctypes.c_int]),
     ('nw_execute_multi', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _I64, _P, ctypes.c_int]),
     ('nw_execute_multi_scales', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _I64, _P, ctypes.c_int]),
     ('nw_execute_multi_device', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(_P),
@@ -180,3 +185,9 @@ def decim_supported(n: int, dtype: int, decim: int) -> bool:
     """Whether a plan of (n, dtype) decimates by ``decim`` on the device (nw_decim_supported;
     host-only, no GPU needed)."""
     return bool(lib().nw_decim_supported(int(n), int(dtype), int(decim)))
+
+
+def pair_partials_supported(n: int, dtype: int, kind: int, out_kind: int) -> bool:
+    """Whether nw_execute_pair forms the sums of ``out_kind`` as block partial sums inside the
+    transform kernel for (n, dtype, wavelet kind) (nw_pair_partials_supported; host-only)."""
+    return bool(lib().nw_pair_partials_supported(int(n), int(dtype), int(kind), int(out_kind)))

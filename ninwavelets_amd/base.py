@@ -26,7 +26,7 @@ import numpy as np
 from scipy.fftpack import fft, ifft
 
 from . import _lib as L
-from .engine import REDUCTIONS, Plan, check_decim, execute_multi, np_dtype
+from .engine import PAIR_OUTS, REDUCTIONS, Plan, check_decim, execute_multi, finalize_pair, np_dtype
 from .engine import make_wavelets as _make_wavelets_dev
 
 # Device working-set budget per plan chunk (bytes); signals are streamed through it.
@@ -282,7 +282,7 @@ class WaveletBase:
 
     # ------------------------------------------------------------------ execution
     def _plan(self, n: int, nsig: int, device: int, scales: tuple[int, int] | None = None,
-              slot: int = 0, decim: int = 1) -> Plan:
+              slot: int = 0, decim: int = 1, min_batch: int = 1) -> Plan:
         """The cached plan for (n, batch, device, decim) -- of the scale slice [f0, f1) when
         ``scales`` is given (scale-sharded multi-device calls).  ``slot`` is the shard
         index of a multi-device call: a plan is not reentrant, so ``devices=[0, 0]`` gets
@@ -296,7 +296,7 @@ class WaveletBase:
         batch = 1
         while batch < min(nsig, cap):
             batch *= 2
-        batch = min(batch, cap)
+        batch = max(min(batch, cap), min_batch)     # (pair reductions: a chunk holds batch // 2 pairs)
         key = (n, nf, self.dtype.str, bool(self.interpolate), device, batch, self.engine, f0, slot, decim)
         plan = self._plans.get(key)
         if plan is None:
@@ -440,6 +440,44 @@ class WaveletBase:
         if out not in ('cwt', 'abs', 'power') + REDUCTIONS:
             raise ValueError(f"out must be one of cwt, abs, power, {', '.join(REDUCTIONS)}; got {out!r}")
         return self._run(waves, out, decim)
+
+    def cross_batch(self, waves_a: np.ndarray, waves_b: np.ndarray, freqs=None, reuse: bool = True,
+                    out: str = 'coherence', decim: int = 1) -> np.ndarray:
+        """Cross-channel reduction over the signal pairs (waves_a[e], waves_b[e]) of two (..., N)
+        arrays of equal shape (the epochs of two channels), reduced on the device in fp64 in
+        pair order: the (E, F, N) CWTs are never materialised (no reference counterpart; the
+        cache semantics are cwt_batch's).  With y_a, y_b the CWT rows of a pair,
+        S_ab = sum_e y_a conj(y_b), P_aa = sum_e |y_a|^2 and E pairs, ``out`` is one of
+          cross_sum  float64 (F, N, 4) = {Re S_ab, Im S_ab, P_aa, P_bb}
+          plv_sum    complex128 (F, N) = sum_e (y_a / |y_a|) conj(y_b / |y_b|)
+          csd        S_ab / E              coherency  S_ab / sqrt(P_aa P_bb)   (complex128)
+          coherence  |coherency|           imcoh      Im coherency             (float64)
+          plv        |plv_sum| / E  (float64; NaN where some |y| = 0, as itc)
+        (engine.finalize_pair).  Results are float64 / complex128 whatever the compute dtype.
+        One device is used: the first of the wavelet's.  ``decim`` as in cwt."""
+        decim = check_decim(decim)
+        if out not in PAIR_OUTS:
+            raise ValueError(f"out must be one of {', '.join(PAIR_OUTS)}; got {out!r}")
+        waves_a, waves_b = np.asarray(waves_a), np.asarray(waves_b)
+        if waves_a.ndim < 1 or waves_a.shape != waves_b.shape:
+            raise ValueError(f'waves_a and waves_b must have the same (..., N) shape; got {waves_a.shape} '
+                             f'and {waves_b.shape}')
+        if (not reuse) or self._cache is None:
+            self._build_cache(freqs, waves_a.shape[-1] / self.sfreq)
+        n = waves_a.shape[-1]
+        npairs = int(np.prod(waves_a.shape[:-1])) if waves_a.ndim > 1 else 1
+        on_device = self._device_decim(n, decim)
+        self._used = 1
+        try:
+            plan = self._plan(n, 2 * npairs, (self.devices or [self.device])[0],
+                              decim=decim if on_device else 1, min_batch=2)
+            sums = plan.execute_pair(waves_a.reshape(npairs, n), waves_b.reshape(npairs, n), out_kind=PAIR_OUTS[out])
+        finally:
+            if len(self._plans) > 1:
+                self._evict_plans(keep=1)
+        if decim > 1 and not on_device:
+            sums = np.ascontiguousarray(sums[:, ::decim])
+        return finalize_pair(out, sums, npairs)
 
     def plan_stats(self) -> list:
         """Per-plan device stage timings (nw_plan_stats)."""

@@ -58,10 +58,13 @@ __attribute__((format(printf, 2, 3))) void nw_logf(int level, const char* fmt, .
 }
 
 const char* out_name(int k) {
-    static const char* names[] = {"cwt", "abs", "power", "power_mean", "itc", "power_sum", "phase_sum"};
+    static const char* names[] = {"cwt", "abs", "power", "power_mean", "itc", "power_sum", "phase_sum",
+                                  "cross_sum", "plv_sum"};
     if (k == 1001) return "power partials";
     if (k == 1002) return "phase partials";
-    return k >= 0 && k < 7 ? names[k] : "?";
+    if (k == 1003) return "cross partials";
+    if (k == 1004) return "plv partials";
+    return k >= 0 && k < 9 ? names[k] : "?";
 }
 const char* kernel_name(int64_t k) {
     static const char* names[] = {"none", "nw_fused_kernel", "nw_fused_pair_kernel", "nw_chirp_kernel",
@@ -600,6 +603,8 @@ int chirp_table(nw_plan* p, const nw::WDesc& d) {
 
 constexpr int OUT_PSUM = 1001;    // internal run_chunk kinds: (ceil(c / 8), F, n) fp64 power partials,
 constexpr int OUT_PHSUM = 1002;   // complex fp64 phase partials (y / |y|)
+constexpr int OUT_XSUM = 1003;    // pair reductions: (ceil(c / 8), F, n, 4) fp64 cross partials of c interleaved
+constexpr int OUT_PLVSUM = 1004;  // signals, (.., 2) unit-phasor product partials
 
 // ---- one device chunk on the rows of d: xs (device, c signals) -> dst (device, (c, d.nfreq, n))
 
@@ -662,6 +667,12 @@ int run_one_pass(nw_plan* p, const nw::WDesc& d, const void* xs_dev, int64_t c, 
         return NW_KERNEL_STAGE(p, ST_FUSED, false,
                                nw::fused_power_partials(d, p->dtype, out_kind == OUT_PHSUM, p->d_X.ptr, p->d_wtab.ptr,
                                                         dst, c, p->stream));
+    }
+    if (out_kind == OUT_XSUM || out_kind == OUT_PLVSUM) {
+        p->stats.kernel = NW_K_FUSED_PAIR;
+        return NW_KERNEL_STAGE(p, ST_FUSED, false,
+                               nw::fused_pair_partials(d, p->dtype, out_kind == OUT_PLVSUM, p->d_X.ptr, p->d_wtab.ptr, dst,
+                                                       c, p->stream));
     }
     if (p->decim > 1) {
         p->stats.kernel = NW_K_FUSED_DECIM;
@@ -807,6 +818,7 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
     nw_logf(1, "plan %p: %s over %lld signals: %s", (void*)p, out_name(out_kind), (long long)nsig,
             psum ? "fp64 block partial sums inside the transform kernel"
                  : "per-signal rows per chunk, added in signal order in fp64");
+    p->stats.reduce_path = psum ? NW_REDUCE_PARTIALS : NW_REDUCE_ROWS;
     // partials: plain fp64 sums (phase partials as 2 fn reals)
     const int src_kind = psum ? nw::ACC_POWER_REAL
                               : phase ? nw::ACC_PHASE_Y : (fused ? nw::ACC_POWER_REAL : nw::ACC_POWER_Y);
@@ -847,6 +859,75 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
         NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, false, nw::launch_finalize(p->dtype, phase, acc, dst, fn, nsig, p->stream)));
         if (host) NW_HIP(hipMemcpyAsync(out, dst, (size_t)fn * p->esz, hipMemcpyDeviceToHost, p->stream));
     }
+    p->stats.executes++;
+    if (host) {
+        NW_HIP(hipStreamSynchronize(p->stream));
+        NW_TRY(resolve_timing(p));
+    }
+    return NW_OK;
+}
+
+// Cross-channel pair reductions (nw_execute_pair): per chunk of max_batch / 2 pairs the two
+// inputs are staged interleaved (a0, b0, a1, b1, ...) into d_x, the complex rows of the 2c
+// signals go to the scratch execute_reduce uses (any form: the rows are n_out long), and
+// k_accumulate_pair adds the pairs' products in pair order into the fp64 accumulator; where the
+// signal-pair kernel forms them itself (pair_partials_supported) the chunk writes fp64 block
+// partials instead and k_accumulate adds those.  The sums are returned as they are (npairs = 0:
+// zeros).
+int execute_pair(nw_plan* p, const nw::WDesc& d, const void* xa, const void* xb, int64_t npairs, void* out,
+                 int out_kind, bool host) {
+    const bool plv = out_kind == NW_OUT_PLV_SUM;
+    const int64_t fn = (int64_t)p->nfreq * p->n_out();
+    const size_t acc_bytes = (size_t)fn * (plv ? 2 : 4) * sizeof(double);
+    NW_TRY(p->d_acc.ensure(acc_bytes));
+    double* const acc = (double*)p->d_acc.ptr;
+    NW_HIP(hipMemsetAsync(acc, 0, acc_bytes, p->stream));
+    // fp32 at the signal-pair kernel's sizes: the kernel sums each block's 4 pairs in fp64 and the
+    // accumulator adds the ceil(2c / 8) partial rows (the same terms, regrouped); the decimated
+    // form and the repeated-row view keep the chunk path.  NW_NO_PAIR_PARTIALS (diagnostics: the
+    // A/B of tools/pair_rate.py) keeps it everywhere.
+    const bool psum = p->form == FORM_ONE_PASS && p->decim == 1 && !p->uniq.U &&
+                      nw::pair_partials_supported(p->n, p->dtype, d.kind, out_kind) && !std::getenv("NW_NO_PAIR_PARTIALS");
+    const int comps = plv ? 2 : 4;
+    nw_logf(1, "plan %p: %s over %lld pairs (%lld per chunk): %s", (void*)p, out_name(out_kind), (long long)npairs,
+            (long long)(p->max_batch / 2),
+            psum ? "fp64 block partial sums inside the transform kernel"
+                 : "per-signal rows per chunk, added in pair order in fp64");
+    p->stats.reduce_path = psum ? NW_REDUCE_PARTIALS : NW_REDUCE_ROWS;
+    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
+    if (p->form == FORM_ROCFFT) {
+        NW_TRY(need_Y(p, p->nfreq));
+        scratch = p->d_Y.ptr;
+    } else {
+        NW_TRY(p->d_out.ensure(psum ? (size_t)nw::fused_psum_groups(p->max_batch) * fn * comps * sizeof(double)
+                                    : (size_t)p->max_batch * fn * 2 * p->esz));
+        scratch = p->d_out.ptr;
+    }
+    const int64_t per = p->max_batch / 2;
+    const size_t row = (size_t)p->n * p->esz;
+    const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    for (int64_t s0 = 0; s0 < npairs; s0 += per) {
+        const int64_t c = std::min<int64_t>(per, npairs - s0);
+        NW_TRY(staged(p, ST_COPY, [&] {
+            // rows of `row` bytes, c of them, to every second row of d_x
+            NW_HIP(hipMemcpy2DAsync(p->d_x.at(0), 2 * row, (const char*)xa + (size_t)s0 * row, row, row, (size_t)c, in,
+                                    p->stream));
+            NW_HIP(hipMemcpy2DAsync(p->d_x.at(row), 2 * row, (const char*)xb + (size_t)s0 * row, row, row, (size_t)c, in,
+                                    p->stream));
+            return NW_OK;
+        }));
+        NW_TRY(run_chunk(p, d, p->d_x.ptr, 2 * c, scratch, psum ? (plv ? OUT_PLVSUM : OUT_XSUM) : NW_OUT_CWT, false));
+        // chained: run_chunk ends with a stage
+        if (psum)   // partials: plain fp64 sums over comps * fn values
+            NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, true,
+                                   nw::launch_accumulate(NW_F64, nw::ACC_POWER_REAL, scratch, acc, comps * fn,
+                                                         nw::fused_psum_groups(2 * c), p->stream)));
+        else
+            NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, true,
+                                   nw::launch_accumulate_pair(p->dtype, plv, scratch, acc, fn, c, p->stream)));
+        p->stats.chunks++;
+    }
+    NW_HIP(hipMemcpyAsync(out, acc, acc_bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, p->stream));
     p->stats.executes++;
     if (host) {
         NW_HIP(hipStreamSynchronize(p->stream));
@@ -1296,6 +1377,30 @@ int nw_execute(nw_plan* p, const void* x, int64_t nsig, void* out, int out_kind,
     return dcheck_collect(p->stream);
 }
 
+int nw_pair_partials_supported(int64_t n, int dtype, int kind, int out_kind) {
+    return nw::pair_partials_supported(n, dtype, kind, out_kind) ? 1 : 0;
+}
+
+int nw_execute_pair(nw_plan* p, const void* xa, const void* xb, int64_t npairs, void* out, int out_kind, int mem) {
+    if (!p || !out || ((!xa || !xb) && npairs > 0)) return fail(NW_E_INVALID, "nw_execute_pair: null argument");
+    if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_pair: nw_plan_set_wavelet first");
+    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM)
+        return fail(NW_E_INVALID, "nw_execute_pair: out_kind must be NW_OUT_CROSS_SUM or NW_OUT_PLV_SUM");
+    if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_pair: bad mem");
+    if (npairs < 0) return fail(NW_E_INVALID, "nw_execute_pair: npairs < 0");
+    if (p->max_batch < 2)
+        return fail(NW_E_INVALID, "nw_execute_pair: the plan's max_batch must be >= 2 (a chunk holds max_batch / 2 pairs)");
+    DeviceGuard guard(p->device);
+    p->executed = true;
+    const nw::WDesc d = exec_rows(p);
+    // settle the form of a tentative length before any buffer choice
+    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
+    nw_logf(1, "plan %p: execute %s, %lld pairs, %s buffers", (void*)p, out_name(out_kind), (long long)npairs,
+            mem == NW_MEM_HOST ? "host" : "device");
+    NW_TRY(execute_pair(p, d, xa, xb, npairs, out, out_kind, mem == NW_MEM_HOST));
+    return dcheck_collect(p->stream);
+}
+
 }  // extern "C"
 
 namespace {
@@ -1669,10 +1774,11 @@ int nw_plan_reset_stats(nw_plan* p) {
     if (!p) return fail(NW_E_INVALID, "nw_plan_reset_stats: null plan");
     DeviceGuard guard(p->device);
     NW_TRY(resolve_timing(p));
-    const int64_t uniq = p->stats.unique_rows, kernel = p->stats.kernel;
+    const int64_t uniq = p->stats.unique_rows, kernel = p->stats.kernel, path = p->stats.reduce_path;
     p->stats = nw_stats{};
     p->stats.unique_rows = uniq;
     p->stats.kernel = kernel;
+    p->stats.reduce_path = path;
     return NW_OK;
 }
 

@@ -43,6 +43,10 @@ __device__ __forceinline__ double mul_nocontract(double a, double b) {
 #pragma clang fp contract(off)
     return a * b;
 }
+__device__ __forceinline__ double add_nocontract(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
 
 // --- memory ops addressed as wave-uniform base (SGPR pair) + 32-bit per-lane byte
 // offset: `global_load/store ... v_off, s[base:base+1]` (saddr form), i.e. one VGPR
@@ -184,6 +188,12 @@ constexpr int kOutXHalf = 1000;
 constexpr int kOutPSum = 1001;
 // ... and the phase sums of ITC: acc[2e], acc[2e + 1] += y / |y| in fp64
 constexpr int kOutPhSum = 1002;
+// ... and the cross-channel sums of a signal pair (a in the low, b in the high halves; the
+// signal-pair kernel only): acc[4e ..] += {Re, Im of y_a conj(y_b), |y_a|^2, |y_b|^2}, or for
+// kOutPlvSum acc[2e ..] += (y_a / |y_a|) conj(y_b / |y_b|), in fp64 (fused_pair_partials)
+constexpr int kOutXSum = 1003;
+constexpr int kOutPlvSum = 1004;
+template <int OUT> constexpr int kPairAcc = OUT == kOutXSum ? 4 : OUT == kOutPlvSum ? 2 : 1;
 struct alignas(16) XHalfSlot { double a, b; };
 template <typename T> struct OutT<kOutXHalf, T> { using type = XHalfSlot; };
 template <int OUT, typename T>
@@ -815,6 +825,32 @@ __device__ __forceinline__ void passes_from(C2<T>* v, T* lds, int t, const C2<Sc
                     // same values whichever block boundaries the chunking draws
                     acc[2 * e] += mul_nocontract(re, inv);
                     acc[2 * e + 1] += mul_nocontract(im, inv);
+                }
+            }
+        } else if constexpr (I::LAST && (OUT == kOutXSum || OUT == kOutPlvSum)) {
+            static_assert(PAIRSIG, "cross-channel partials run the signal-pair kernel");
+            // every pair is complete (the inputs are interleaved a0, b0, a1, b1, ...)
+            NW_DCHECK_H(ocur2 != nullptr);
+            // the terms of k_accumulate_pair: each product and each sum of two rounded on its own
+            // before it is added, so block partials add the same values as the chunk path
+#pragma unroll
+            for (int e = 0; e < Q * R; ++e) {
+                double ar = (double)v[e].re.x, ai = (double)v[e].im.x;
+                double br = (double)v[e].re.y, bi = (double)v[e].im.y;
+                if constexpr (OUT == kOutPlvSum) {
+                    // unit phasors as kOutPhSum's: |y|^2 of fp32 parts is exact in fp64 up to one
+                    // rounding; y = 0 gives 0 * inf = NaN like 0/0
+                    const double ia = rsqrt(add_nocontract(mul_nocontract(ar, ar), mul_nocontract(ai, ai)));
+                    const double ib = rsqrt(add_nocontract(mul_nocontract(br, br), mul_nocontract(bi, bi)));
+                    ar = mul_nocontract(ar, ia), ai = mul_nocontract(ai, ia);
+                    br = mul_nocontract(br, ib), bi = mul_nocontract(bi, ib);
+                }
+                constexpr int NA = kPairAcc<OUT>;
+                acc[NA * e] += add_nocontract(mul_nocontract(ar, br), mul_nocontract(ai, bi));
+                acc[NA * e + 1] += add_nocontract(mul_nocontract(ai, br), -mul_nocontract(ar, bi));
+                if constexpr (OUT == kOutXSum) {
+                    acc[NA * e + 2] += add_nocontract(mul_nocontract(ar, ar), mul_nocontract(ai, ai));
+                    acc[NA * e + 3] += add_nocontract(mul_nocontract(br, br), mul_nocontract(bi, bi));
                 }
             }
         } else if constexpr (I::LAST && OUT == kOutXHalf) {

@@ -297,10 +297,14 @@ __global__ __launch_bounds__(N / E, (kWpsOf<T, E, OUT>)) void nw_fused_kernel(WD
 // (v_pk_add/mul/fma_f32; 8-B image slots; twiddles and the pass-1 table shared).  Pass 0
 // reads both X rows and the block's W registers; the last pass stores each half to its
 // own row (an odd last signal transforms a duplicate whose high half is not stored).
+// kOutXSum / kOutPlvSum (cross-channel partials, nw_execute_pair): the signals are interleaved
+// a0, b0, a1, b1, ..., so a lane value holds one pair's y_a and y_b at the same point; the last
+// pass adds the pair's products into 4E / 2E fp64 accumulators, in pair order.
 // |y| and |y|^2 read X from L2 in pass 0; cwt takes the next pair's X by LDS-DMA before the
-// stores (XD below).  4 waves/SIMD; the power partials' E fp64 accumulators take it to 3.
+// stores (XD below).  4 waves/SIMD; the power partials' E fp64 accumulators take it to 3, the
+// cross-channel partials' 4E / 2E to 2 (the PLV mode spills 28-64 B at 3).
 template <int N, int E, int OUT>
-__global__ __launch_bounds__(N / E, OUT == kOutPSum ? 3 : 4) void nw_fused_pair_kernel(WDesc d, const cplx<float>* __restrict__ X,
+__global__ __launch_bounds__(N / E, (OUT == kOutXSum || OUT == kOutPlvSum) ? 2 : OUT == kOutPSum ? 3 : 4) void nw_fused_pair_kernel(WDesc d, const cplx<float>* __restrict__ X,
                                                                   const void* __restrict__ wtab, void* __restrict__ out,
                                                                   const C2<float>* __restrict__ tw, int64_t nsig,
                                                                   int group, int nsg_pad, const int* __restrict__ wnz,
@@ -357,12 +361,15 @@ __global__ __launch_bounds__(N / E, OUT == kOutPSum ? 3 : 4) void nw_fused_pair_
         dma_x<float, N, G::T>(xrow(sb), reinterpret_cast<char*>(lds) + (N / 2) * sizeof(C2<float>), t, dma_rounds);
     }
     // power partial sums (kOutPSum): as nw_fused_kernel, both signals of a pair into one sum
-    constexpr bool PSUM = OUT == kOutPSum;
-    double acc[PSUM ? E : 1];
+    // (kOutXSum / kOutPlvSum: kPairAcc values per point, the two channels of a pair)
+    constexpr bool PSUM = OUT == kOutPSum || OUT == kOutXSum || OUT == kOutPlvSum;
+    constexpr int NACC = kPairAcc<OUT>;
+    double acc[PSUM ? NACC * E : 1];
     if constexpr (PSUM) {
 #pragma unroll
-        for (int e = 0; e < E; ++e) acc[e] = 0.0;
+        for (int e = 0; e < NACC * E; ++e) acc[e] = 0.0;
     }
+    if constexpr (NACC > 1) NW_DCHECK(cnt % 2 == 0);   // whole pairs: o2 below is never null
     for (int i = 0; i < cnt; i += 2) {
         const int64_t s = s_begin + i;
         const bool two = i + 1 < cnt;
@@ -441,11 +448,16 @@ __global__ __launch_bounds__(N / E, OUT == kOutPSum ? 3 : 4) void nw_fused_pair_
     }
     if constexpr (PSUM) {
         using IL = PassInfo<N, E, G::npass() - 1, (int)sizeof(float), true>;
-        double* prow = reinterpret_cast<double*>(out) + ((int64_t)sg * d.nfreq + fi) * (int64_t)N;
+        double* prow = reinterpret_cast<double*>(out) + ((int64_t)sg * d.nfreq + fi) * (int64_t)N * NACC;
 #pragma unroll
         for (int q = 0; q < IL::Q; ++q)
 #pragma unroll
-            for (int i = 0; i < IL::R; ++i) prow[IL::bfly(t, q) + bitrev<IL::R>(i) * IL::NS] = acc[q * IL::R + i];
+            for (int i = 0; i < IL::R; ++i) {
+                const int k = IL::bfly(t, q) + bitrev<IL::R>(i) * IL::NS;
+                NW_DCHECK(k >= 0 && k < N);
+#pragma unroll
+                for (int c = 0; c < NACC; ++c) prow[k * NACC + c] = acc[(q * IL::R + i) * NACC + c];
+            }
     }
 }
 
@@ -647,7 +659,8 @@ hipError_t launch_psum(const WDesc& d, const void* X, const void* wtab, void* pa
                              sh.tile_g);
     };
     // power partials on the signal-pair kernel: the same values as its power output
-    if constexpr (OUT == kOutPSum && kPairMode<T, E, true>) return go(nw_fused_pair_kernel<N, E, kOutPSum>, kLdsBytes<f2, N, E>);
+    if constexpr (OUT == kOutXSum || OUT == kOutPlvSum) return go(nw_fused_pair_kernel<N, E, OUT>, kLdsBytes<f2, N, E>);
+    else if constexpr (OUT == kOutPSum && kPairMode<T, E, true>) return go(nw_fused_pair_kernel<N, E, kOutPSum>, kLdsBytes<f2, N, E>);
     else return go(nw_fused_kernel<T, N, E, OUT, true, WSH>, kLdsBytes<T, N, E>);
 }
 
@@ -746,6 +759,24 @@ hipError_t fused_power_partials(const WDesc& d, int dtype, bool phase, const voi
         if constexpr (kPSumOK<T, N, E>) {
             constexpr int PE = kPsE<T, E, false>;
             if (!phase) return launch_psum<T, N, PE, kOutPSum, kPsShift<E, PE>>(d, X, wtab, partials, nsig, s);
+        }
+        return hipErrorNotSupported;
+    });
+}
+
+// cross-channel partials of nsig interleaved signals (nsig / 2 pairs): one fp64 row of 4 (plv: 2)
+// values per point per (block of kGroup signals, scale); where pair_partials_supported
+hipError_t fused_pair_partials(const WDesc& d, int dtype, bool plv, const void* X, const void* wtab, void* partials,
+                               int64_t nsig, hipStream_t s) {
+    if (nsig % 2 || d.kind == NW_TABLE) return hipErrorInvalidValue;
+    return for_fused_size(d.n, dtype, hipErrorNotSupported, [&]<typename T, int N, int E>(FusedSize<T, N, E>) {
+        if constexpr (kPairMode<T, E, true>) {
+            if constexpr (kPairXSumOK<N>) {
+                if (!plv) return launch_psum<T, N, E, kOutXSum, 0>(d, X, wtab, partials, nsig, s);
+            }
+            if constexpr (kPairPlvSumOK<N>) {
+                if (plv) return launch_psum<T, N, E, kOutPlvSum, 0>(d, X, wtab, partials, nsig, s);
+            }
         }
         return hipErrorNotSupported;
     });

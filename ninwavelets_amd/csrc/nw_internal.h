@@ -222,6 +222,10 @@ hipError_t launch_expand_rows(const void* src, void* dst, int64_t nsig, int nu, 
 enum { ACC_POWER_REAL = 0, ACC_POWER_Y = 1, ACC_PHASE_Y = 2 };
 hipError_t launch_accumulate(int dtype, int src_kind, const void* src, double* acc, int64_t fn, int64_t c,
                              hipStream_t s);
+// pair reductions: src = the complex rows (2c, F, n_out) of c interleaved pairs (a0, b0, a1, ...),
+// acc += their cross sums (4 fp64 per point) or, plv, unit-phasor products (2 per point)
+hipError_t launch_accumulate_pair(int dtype, bool plv, const void* src, double* acc, int64_t fn, int64_t c,
+                                  hipStream_t s);
 hipError_t launch_finalize(int dtype, bool itc, const double* acc, void* out, int64_t fn, int64_t nsig,
                            hipStream_t s);
 hipError_t launch_add_f64(double* acc, const double* src, int64_t count, hipStream_t s);
@@ -303,6 +307,12 @@ int64_t fused_psum_groups(int64_t nsig);
 int fused_psum_kernel_id(int64_t n, int dtype, bool phase);   // NW_K_FUSED or NW_K_FUSED_PAIR
 hipError_t fused_power_partials(const WDesc& d, int dtype, bool phase, const void* X, const void* wtab,
                                 void* partials, int64_t nsig, hipStream_t s);
+// cross-channel partials of nsig interleaved signals a0, b0, a1, ... (nw_execute_pair; where
+// pair_partials_supported): (fused_psum_groups(nsig), F, n, 4) fp64 {Re, Im of y_a conj(y_b),
+// |y_a|^2, |y_b|^2} summed over each block's pairs in pair order, or with plv (.., 2) the
+// unit-phasor products
+hipError_t fused_pair_partials(const WDesc& d, int dtype, bool plv, const void* X, const void* wtab, void* partials,
+                               int64_t nsig, hipStream_t s);
 
 // chirp-z engine (nw_chirp.hip): n not taken by the power-of-two kernels, 2n - 1 <= 16384
 // (fp32) / 8192 (fp64); one (scale, signal) row = two on-chip FFTs of M = 2^ceil(log2(2n-1))

@@ -182,6 +182,69 @@ hipError_t launch_accumulate(int dtype, int src_kind, const void* src, double* a
     return hipGetLastError();
 }
 
+// a rounded fp64 product that the compiler may not fuse into a following add
+__device__ __forceinline__ double mul_nocontract(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ double add_nocontract(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+// ---------------------------------------------------------------------------
+// Cross-channel pair reductions (nw_execute_pair).  src holds the chunk's complex rows
+// (2c, F, n_out) with the two channels of pair s interleaved: y_a = row 2s, y_b = row 2s + 1.
+// One thread per (f, k) walks the c pairs in order and adds to the fp64 accumulator
+//   PLV = false: acc[4i ..] += {Re, Im of y_a conj(y_b), |y_a|^2, |y_b|^2}
+//   PLV = true : acc[2i ..] += (y_a / |y_a|) conj(y_b / |y_b|), the unit phasors formed as
+//                k_accumulate's (hypot and divide in fp64; |y| = 0 gives 0/0 = NaN)
+// Every term is rounded on its own before it is added (no fma into the sum), so another
+// grouping of the pairs into chunks -- or into block partials -- adds the same values.
+// ---------------------------------------------------------------------------
+template <typename T, bool PLV>
+__global__ __launch_bounds__(256) void k_accumulate_pair(const cplx<T>* __restrict__ src, double* __restrict__ acc,
+                                                         int64_t fn, int64_t c) {
+    constexpr int NC = PLV ? 2 : 4;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < fn; i += stride) {
+        NW_DCHECK(i >= 0 && NC * i + NC - 1 < NC * fn);
+        double s[NC];
+#pragma unroll
+        for (int j = 0; j < NC; ++j) s[j] = acc[NC * i + j];
+        for (int64_t p = 0; p < c; ++p) {
+            const int64_t ia = 2 * p * fn + i, ib = ia + fn;
+            NW_DCHECK(ia >= 0 && ib < 2 * c * fn);
+            const cplx<T> va = src[ia], vb = src[ib];
+            double ar = (double)va.re, ai = (double)va.im, br = (double)vb.re, bi = (double)vb.im;
+            if constexpr (PLV) {
+                const double ma = hypot(ar, ai), mb = hypot(br, bi);
+                ar /= ma, ai /= ma, br /= mb, bi /= mb;
+            }
+            s[0] += add_nocontract(mul_nocontract(ar, br), mul_nocontract(ai, bi));
+            s[1] += add_nocontract(mul_nocontract(ai, br), -mul_nocontract(ar, bi));
+            if constexpr (!PLV) {
+                s[2] += add_nocontract(mul_nocontract(ar, ar), mul_nocontract(ai, ai));
+                s[3] += add_nocontract(mul_nocontract(br, br), mul_nocontract(bi, bi));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NC; ++j) acc[NC * i + j] = s[j];
+    }
+}
+
+hipError_t launch_accumulate_pair(int dtype, bool plv, const void* src, double* acc, int64_t fn, int64_t c,
+                                  hipStream_t s) {
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((fn + 255) / 256, 256 * 32));
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        for_bool(plv, [&](auto v) {
+            nw_launch(k_accumulate_pair<T, decltype(v)::value>, blocks, 256, 0, s, (const cplx<T>*)src, acc, fn, c);
+        });
+    });
+    return hipGetLastError();
+}
+
 // mean = acc / nsig (np.mean's true_divide by the count); ITC = |(re, im) / nsig|
 template <typename T, bool ITC>
 __global__ __launch_bounds__(256) void k_finalize(const double* __restrict__ acc, T* __restrict__ out, int64_t fn,

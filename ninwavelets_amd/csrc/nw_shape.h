@@ -271,6 +271,21 @@ constexpr bool kPSumOK = !(sizeof(T) == 8 && N / kPsE<T, EO, false> > 512);
 template <typename T, int N, int EO>
 constexpr bool kPhSumOK = N / kPsE<T, EO, true> <= 512;
 
+// cross-channel pair reductions (nw_execute_pair: NW_OUT_CROSS_SUM / NW_OUT_PLV_SUM): the
+// (n, dtype, wavelet kind, out_kind) whose sums are formed as block partials inside
+// nw_fused_pair_kernel.  The candidates are fp32, n = 1024 / 2048 / 4096, analytic rows; an
+// instantiation enters only with 0 B of scratch and a measured rate no lower than the chunk
+// path's (k_accumulate_pair over the chunk's complex rows).  All six hold both
+// (profiles/r11_pair_rate.txt, r11_pair_isa.txt).
+template <int N> constexpr bool kPairXSumOK = N >= 1024 && N <= 4096;     // 4E fp64 accumulators, 2 waves/SIMD
+template <int N> constexpr bool kPairPlvSumOK = N >= 1024 && N <= 4096;   // 2E fp64 accumulators, 2 waves/SIMD
+constexpr bool pair_partials_supported(int64_t n, int dtype, int kind, int out_kind) {
+    if (dtype != NW_F32 || (kind != NW_MORSE && kind != NW_MORLET && kind != NW_SHANNON)) return false;
+    const bool xs = n == 1024 ? kPairXSumOK<1024> : n == 2048 ? kPairXSumOK<2048> : n == 4096 ? kPairXSumOK<4096> : false;
+    const bool ps = n == 1024 ? kPairPlvSumOK<1024> : n == 2048 ? kPairPlvSumOK<2048> : n == 4096 ? kPairPlvSumOK<4096> : false;
+    return out_kind == NW_OUT_CROSS_SUM ? xs : out_kind == NW_OUT_PLV_SUM ? ps : false;
+}
+
 // ---- the two-pass engine (nw_large.hip) -----------------------------------------------------
 
 // power-of-two 2^15 <= n <= 2^24, fp32 or fp64

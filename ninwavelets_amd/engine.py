@@ -21,6 +21,11 @@ OUT_KINDS = {'cwt': L.NW_OUT_CWT, 'abs': L.NW_OUT_ABS, 'power': L.NW_OUT_POWER,
              'power_mean': L.NW_OUT_POWER_MEAN, 'itc': L.NW_OUT_ITC,
              'power_sum': L.NW_OUT_POWER_SUM, 'phase_sum': L.NW_OUT_PHASE_SUM}
 REDUCTIONS = ('power_mean', 'itc', 'power_sum', 'phase_sum')
+# cross-channel reductions over signal pairs -> (F, n, 4) float64 / (F, n) complex128 (Plan.execute_pair)
+PAIR_KINDS = {'cross_sum': L.NW_OUT_CROSS_SUM, 'plv_sum': L.NW_OUT_PLV_SUM}
+# what finalize_pair forms from them: name -> the sums it needs
+PAIR_OUTS = {'cross_sum': 'cross_sum', 'plv_sum': 'plv_sum', 'csd': 'cross_sum', 'coherency': 'cross_sum',
+             'coherence': 'cross_sum', 'imcoh': 'cross_sum', 'plv': 'plv_sum'}
 KINDS = {'morse': L.NW_MORSE, 'morlet': L.NW_MORLET, 'shannon': L.NW_SHANNON, 'table': L.NW_TABLE,
          # WaveletMode.Normal tables built on the device (base.py:249-256)
          'mexican_hat': L.NW_MEXICAN_HAT, 'haar': L.NW_HAAR}
@@ -56,6 +61,35 @@ def out_dtype(dtype, out_kind: str) -> np.dtype:
     if out_kind == 'cwt':
         return np.dtype(np.complex64 if dt == np.float32 else np.complex128)
     return dt
+
+
+def finalize_pair(kind: str, sums: np.ndarray, npairs: int) -> np.ndarray:
+    """The connectivity measure ``kind`` from the fp64 sums over ``npairs`` signal pairs
+    (a_e, b_e) that Plan.execute_pair returns.  From ``cross_sum`` (F, n, 4) =
+    {Re S_ab, Im S_ab, P_aa, P_bb} with S_ab = sum_e y_a conj(y_b), P_aa = sum_e |y_a|^2:
+      csd        S_ab / E                        complex128
+      coherency  S_ab / sqrt(P_aa P_bb)          complex128
+      coherence  |coherency|                     float64
+      imcoh      Im coherency                    float64
+    from ``plv_sum`` (F, n) = sum_e (y_a / |y_a|) conj(y_b / |y_b|):
+      plv        |plv_sum| / E                   float64
+    ``cross_sum`` / ``plv_sum`` return the sums themselves.  Plain numpy, float64 / complex128
+    whatever the compute dtype."""
+    if kind not in PAIR_OUTS:
+        raise ValueError(f"out must be one of {', '.join(PAIR_OUTS)}; got {kind!r}")
+    if kind in PAIR_KINDS:
+        return sums
+    if kind == 'plv':
+        return np.abs(np.asarray(sums, dtype=np.complex128)) / npairs
+    sums = np.asarray(sums, dtype=np.float64)
+    # S_ab over a real: two real divisions (numpy's complex / real is not correctly rounded: the
+    # coherence of a channel with itself would come out 1 - 1 ulp)
+    den = npairs if kind == 'csd' else np.sqrt(sums[..., 2] * sums[..., 3])
+    ratio = np.empty(sums.shape[:-1], dtype=np.complex128)
+    ratio.real, ratio.imag = sums[..., 0] / den, sums[..., 1] / den
+    if kind in ('csd', 'coherency'):
+        return ratio
+    return np.abs(ratio) if kind == 'coherence' else np.ascontiguousarray(ratio.imag)
 
 
 class HostPool:
@@ -356,6 +390,53 @@ class Plan:
             raise ValueError('out must be a C-contiguous array of the right dtype and size')
         L.check(L.lib().nw_execute(self._h, x.ctypes.data_as(ctypes.c_void_p), nsig,
                                    out.ctypes.data_as(ctypes.c_void_p), kind, L.NW_MEM_HOST))
+        return out
+
+    def execute_pair(self, xa, xb, out=None, out_kind: str = 'cross_sum'):
+        """Cross-channel reduction over the signal pairs (xa[e], xb[e]) (nw_execute_pair): xa,
+        xb of equal shape (E, n), numpy arrays (host, synchronous) or device tensors
+        (asynchronous on the plan stream; ``out`` required).  ``cross_sum`` -> float64
+        (nfreq, n_out, 4) = {Re S_ab, Im S_ab, P_aa, P_bb}; ``plv_sum`` -> complex128
+        (nfreq, n_out); see finalize_pair.  The plan needs max_batch >= 2."""
+        if out_kind not in PAIR_KINDS:
+            raise ValueError(f"out_kind must be one of {', '.join(PAIR_KINDS)}; got {out_kind!r}")
+        kind = PAIR_KINDS[out_kind]
+        plv = out_kind == 'plv_sum'
+        count = self.nfreq * self.n_out * (1 if plv else 4)
+        if _is_device_tensor(xa) or _is_device_tensor(xb):
+            import torch
+            if out is None:
+                raise ValueError('device execute needs an output tensor')
+            npairs = self._check_device_input(xa)
+            if self._check_device_input(xb) != npairs:
+                raise ValueError('the two inputs must hold the same number of signals')
+            if not _is_device_tensor(out) or out.dtype != (torch.complex128 if plv else torch.float64):
+                raise ValueError(f'device output must be a {"complex128" if plv else "float64"} tensor '
+                                 f'on device {self.device}')
+            if not out.is_contiguous() or out.numel() != count:
+                raise ValueError('device output must be contiguous, (nfreq, n_out, 4) for cross_sum / '
+                                 '(nfreq, n_out) for plv_sum')
+            if out.device.index != self.device:
+                raise ValueError(f'device buffers must live on device {self.device}')
+            with self._ordered_with_torch(xa.device):
+                L.check(L.lib().nw_execute_pair(self._h, ctypes.c_void_p(xa.data_ptr()), ctypes.c_void_p(xb.data_ptr()),
+                                                npairs, ctypes.c_void_p(out.data_ptr()), kind, L.NW_MEM_DEVICE))
+            return out
+        xa = np.ascontiguousarray(xa, dtype=self.dtype)
+        xb = np.ascontiguousarray(xb, dtype=self.dtype)
+        if xa.shape != xb.shape:
+            raise ValueError(f'the two inputs must have the same shape, got {xa.shape} and {xb.shape}')
+        if xa.ndim < 1 or xa.shape[-1] != self.n:
+            raise ValueError(f'signal length {xa.shape[-1] if xa.ndim else None} != plan n {self.n}')
+        npairs = int(np.prod(xa.shape[:-1])) if xa.ndim > 1 else 1
+        odt = np.dtype(np.complex128 if plv else np.float64)
+        shape = (self.nfreq, self.n_out) if plv else (self.nfreq, self.n_out, 4)
+        if out is None:
+            out = np.empty(shape, dtype=odt)
+        elif out.dtype != odt or not out.flags.c_contiguous or out.size != count:
+            raise ValueError('out must be a C-contiguous array of the right dtype and size')
+        L.check(L.lib().nw_execute_pair(self._h, xa.ctypes.data_as(ctypes.c_void_p), xb.ctypes.data_as(ctypes.c_void_p),
+                                        npairs, out.ctypes.data_as(ctypes.c_void_p), kind, L.NW_MEM_HOST))
         return out
 
     def stream_ptr(self) -> int:

@@ -38,3 +38,26 @@ class EpochsWavelet:
         """Inter-trial coherence |mean(cwt/|cwt|)|, (F, N) (mneutils.py:57-71), reduced
         on the device; a point where some epoch has |cwt| = 0 is NaN, as in the reference."""
         return self.wavelet.cwt_batch(self._waves(ch_name), freqs, reuse=True, out='itc', decim=decim)
+
+    # -- connectivity between two channels: cross-channel epoch reductions on the device
+    #    (WaveletBase.cross_batch; no reference counterpart) --------------------------------
+    def _cross(self, ch_a: str, ch_b: str, freqs, out: str, decim: int) -> np.ndarray:
+        return self.wavelet.cross_batch(self._waves(ch_a), self._waves(ch_b), freqs, reuse=True, out=out,
+                                        decim=decim)
+
+    def csd(self, ch_a: str, ch_b: str, freqs, decim: int = 1) -> np.ndarray:
+        """Epoch-mean cross-spectrum mean_e cwt_a conj(cwt_b), (F, N) complex128."""
+        return self._cross(ch_a, ch_b, freqs, 'csd', decim)
+
+    def coherence(self, ch_a: str, ch_b: str, freqs, decim: int = 1) -> np.ndarray:
+        """|S_ab| / sqrt(P_aa P_bb) of the epoch sums, (F, N) float64."""
+        return self._cross(ch_a, ch_b, freqs, 'coherence', decim)
+
+    def imcoh(self, ch_a: str, ch_b: str, freqs, decim: int = 1) -> np.ndarray:
+        """Imaginary part of the coherency S_ab / sqrt(P_aa P_bb), (F, N) float64."""
+        return self._cross(ch_a, ch_b, freqs, 'imcoh', decim)
+
+    def plv(self, ch_a: str, ch_b: str, freqs, decim: int = 1) -> np.ndarray:
+        """Phase-locking value |mean_e (cwt_a / |cwt_a|) conj(cwt_b / |cwt_b|)|, (F, N) float64; a
+        point where some epoch has |cwt| = 0 is NaN, as itc."""
+        return self._cross(ch_a, ch_b, freqs, 'plv', decim)
