@@ -147,6 +147,8 @@ typedef struct nw_stats {
 #define NW_REDUCE_NONE     0   /* no reduction executed yet                                     */
 #define NW_REDUCE_ROWS     1   /* per-signal rows per chunk, added in signal order in fp64     */
 #define NW_REDUCE_PARTIALS 2   /* fp64 block partial sums inside the transform kernel          */
+#define NW_REDUCE_CONN     3   /* nw_execute_conn: per-signal rows per chunk, every pair's sums
+                                  added in epoch order by nw_conn_accumulate_kernel            */
 
 /* nw_stats.kernel: which kernel wrote the output rows (the dominant kernel of a step) */
 #define NW_K_NONE        0
@@ -262,6 +264,29 @@ int nw_execute(nw_plan* plan, const void* x, int64_t nsig, void* out, int out_ki
  * the plan stream).  npairs = 0 gives zero sums.  A decimated plan reduces its n / decim rows. */
 int nw_execute_pair(nw_plan* plan, const void* xa, const void* xb, int64_t npairs, void* out,
                     int out_kind, int mem);
+
+/* Host-only (no GPU): the pair tiling nw_execute_conn uses.  tile_of_pair[npairs] (may be NULL)
+ * receives each pair's tile; *ntiles the count; limits[3] (may be NULL) = {kConnCh, kConnPairs,
+ * sample tile}.  NW_E_INVALID: nchan < 1, an index outside [0, nchan), npairs < 0. */
+int nw_conn_tiles(int32_t nchan, const int32_t* ia, const int32_t* ib, int64_t npairs,
+                  int32_t* tile_of_pair, int64_t* ntiles, int32_t* limits);
+
+/* Multi-channel connectivity: the sums of nw_execute_pair for npairs channel pairs
+ * (ia[p], ib[p]) of nchan channels from ONE transform of every epoch and channel.
+ * x: (nepochs, nchan, n) of the plan dtype.  ia, ib: HOST arrays [npairs] (any list: repeats,
+ * a > b, a == b).
+ * NW_OUT_CROSS_SUM: out_cross complex128 (npairs, F, n_out) = sum_e y_a conj(y_b),
+ *                   out_power float64 (nchan, F, n_out) = sum_e |y_c|^2 (may be NULL).
+ * NW_OUT_PLV_SUM:   out_cross complex128 (npairs, F, n_out) = sum_e unit phasor products;
+ *                   out_power must be NULL.
+ * Every sum in fp64 in epoch order, the terms those of nw_execute_pair's per-signal-rows path
+ * (bit-identical to it for the same two channels, however the epochs are chunked).
+ * Chunks of max_batch / nchan epochs: max_batch >= nchan, else NW_E_INVALID.  mem as in
+ * nw_execute_pair.  nepochs = 0 or npairs = 0: zero sums.  Decimated plans reduce n / decim rows.
+ * The fp64 accumulators live in the plan (nw_stats.device_bytes); NW_E_NOMEM if they do not fit. */
+int nw_execute_conn(nw_plan* plan, const void* x, int64_t nepochs, int32_t nchan,
+                    const int32_t* ia, const int32_t* ib, int64_t npairs,
+                    void* out_cross, void* out_power, int out_kind, int mem);
 
 /* Shard nsig host signals over nplans plans (one per device, identical config),
  * one host thread per plan; balanced contiguous blocks (nsig / nplans signals, one

@@ -40,6 +40,7 @@ NW_OUT_CWT, NW_OUT_ABS, NW_OUT_POWER = 0, 1, 2
 NW_OUT_POWER_MEAN, NW_OUT_ITC, NW_OUT_POWER_SUM, NW_OUT_PHASE_SUM = 3, 4, 5, 6
 NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM = 7, 8          # nw_execute_pair only
 NW_REDUCE_NONE, NW_REDUCE_ROWS, NW_REDUCE_PARTIALS = 0, 1, 2   # nw_stats.reduce_path
+NW_REDUCE_CONN = 3                                              # ... of nw_execute_conn
 NW_MEM_HOST, NW_MEM_DEVICE = 0, 1
 # nw_stats.kernel -> the kernel name rocprofv3 shows
 KERNEL_NAMES = {0: None, 1: 'nw_fused_kernel', 2: 'nw_fused_pair_kernel', 3: 'nw_chirp_kernel',
@@ -92,6 +93,8 @@ SIGNATURES = [
     ('nw_plan_row_support', ctypes.c_int, [_P, ctypes.c_int, _P]),
     ('nw_execute', ctypes.c_int, [_P, _P, _I64, _P, ctypes.c_int, ctypes.c_int]),
     ('nw_execute_pair', ctypes.c_int, [_P, _P, _P, _I64, _P, ctypes.c_int, ctypes.c_int]),
+    ('nw_conn_tiles', ctypes.c_int, [ctypes.c_int32, _P, _P, _I64, _P, ctypes.POINTER(_I64), _P]),
+    ('nw_execute_conn', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _P, _P, ctypes.c_int, ctypes.c_int]),
     ('nw_execute_multi', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _I64, _P, ctypes.c_int]),
     ('nw_execute_multi_scales', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _I64, _P, ctypes.c_int]),
     ('nw_execute_multi_device', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(_P),
@@ -191,3 +194,20 @@ def pair_partials_supported(n: int, dtype: int, kind: int, out_kind: int) -> boo
     """Whether nw_execute_pair forms the sums of ``out_kind`` as block partial sums inside the
     transform kernel for (n, dtype, wavelet kind) (nw_pair_partials_supported; host-only)."""
     return bool(lib().nw_pair_partials_supported(int(n), int(dtype), int(kind), int(out_kind)))
+
+
+def conn_tiles(nchan: int, ia, ib):
+    """The pair tiling nw_execute_conn uses for the pairs (ia[p], ib[p]) of ``nchan`` channels
+    (nw_conn_tiles; host-only): (tile_of_pair int32 [npairs], ntiles, (kConnCh, kConnPairs,
+    sample tile)).  ValueError for nchan < 1 or an index outside [0, nchan)."""
+    import numpy as np
+    ia = np.ascontiguousarray(ia, dtype=np.int32)
+    ib = np.ascontiguousarray(ib, dtype=np.int32)
+    if ia.ndim != 1 or ia.shape != ib.shape:
+        raise ValueError(f'ia and ib must be 1-D index lists of equal length, got {ia.shape} and {ib.shape}')
+    tile = np.empty(ia.size, dtype=np.int32)
+    ntiles = ctypes.c_int64()
+    limits = (ctypes.c_int32 * 3)()
+    check(lib().nw_conn_tiles(int(nchan), ia.ctypes.data_as(_P), ib.ctypes.data_as(_P), int(ia.size),
+                              tile.ctypes.data_as(_P), ctypes.byref(ntiles), ctypes.cast(limits, _P)))
+    return tile, int(ntiles.value), tuple(limits)

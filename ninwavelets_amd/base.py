@@ -26,7 +26,8 @@ import numpy as np
 from scipy.fftpack import fft, ifft
 
 from . import _lib as L
-from .engine import PAIR_OUTS, REDUCTIONS, Plan, check_decim, execute_multi, finalize_pair, np_dtype
+from .engine import (CONN_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim, check_indices, execute_multi, finalize_conn,
+                     finalize_pair, np_dtype)
 from .engine import make_wavelets as _make_wavelets_dev
 
 # Device working-set budget per plan chunk (bytes); signals are streamed through it.
@@ -478,6 +479,43 @@ class WaveletBase:
         if decim > 1 and not on_device:
             sums = np.ascontiguousarray(sums[:, ::decim])
         return finalize_pair(out, sums, npairs)
+
+    def connectivity_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, out: str = 'coherence',
+                           indices=None, decim: int = 1):
+        """Connectivity between the channels of ``waves`` (E, C, N), E epochs of C channels: every
+        signal is transformed ONCE and the sums of cross_batch are formed on the device for all
+        pairs ``indices`` = (ia, ib) (positions on the channel axis; any list: repeats, a > b,
+        a == b; default every pair a < b in np.triu_indices(C, 1) order) -- C E transforms where
+        one cross_batch call per pair takes C (C - 1) E.  The result is (P, F, ceil(N / decim)) with
+        ``out`` as in cross_batch (csd, coherency: complex128; coherence, imcoh, plv: float64;
+        plv_sum: complex128), each pair finalised as cross_batch finalises it; ``cross_sum``
+        returns (S complex128 (P, F, N'), P_cc float64 (C, F, N')).  No reference counterpart
+        (mne-connectivity's spectral_connectivity_epochs(..., indices=...) in its cwt_morlet mode
+        returns the same maps); cache semantics, device choice and ``decim`` as in cross_batch."""
+        decim = check_decim(decim)
+        if out not in CONN_OUTS:
+            raise ValueError(f"out must be one of {', '.join(CONN_OUTS)}; got {out!r}")
+        waves = np.asarray(waves)
+        if waves.ndim != 3:
+            raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
+        nep, nchan, n = waves.shape
+        ia, ib = check_indices(indices, nchan)
+        if (not reuse) or self._cache is None:
+            self._build_cache(freqs, n / self.sfreq)
+        on_device = self._device_decim(n, decim)
+        self._used = 1
+        try:
+            plan = self._plan(n, nep * nchan, (self.devices or [self.device])[0],
+                              decim=decim if on_device else 1, min_batch=nchan)
+            sums = plan.execute_conn(waves, (ia, ib), out_kind=CONN_OUTS[out])
+        finally:
+            if len(self._plans) > 1:
+                self._evict_plans(keep=1)
+        cross, power = sums if CONN_OUTS[out] == 'cross_sum' else (sums, None)
+        if decim > 1 and not on_device:
+            cross = np.ascontiguousarray(cross[..., ::decim])
+            power = None if power is None else np.ascontiguousarray(power[..., ::decim])
+        return finalize_conn(out, cross, power, ia, ib, nep)
 
     def plan_stats(self) -> list:
         """Per-plan device stage timings (nw_plan_stats)."""

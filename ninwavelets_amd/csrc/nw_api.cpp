@@ -265,7 +265,9 @@ struct nw_plan {
     DevBuf d_x, d_X;
     DevBuf d_Y;
     DevBuf d_out;
-    DevBuf d_acc;                    // epoch reductions: fp64 (F, n) sums (x2 for phases)
+    DevBuf d_acc;                    // epoch reductions: fp64 (F, n) sums (x2 for phases); nw_execute_conn:
+                                     // complex (npairs, F, n) | (nchan, F, n) | the pair tiles
+    std::vector<nw::ConnTile> conn_tiles;   // nw_execute_conn: the last call's tiles (the upload's source)
     // nw_execute_multi_device reductions: this device's fp64 partial sums, and (device 0's
     // plan) the peer-copy landing buffer; kept across calls (a hipFree per call would
     // synchronise the device on every epoch-loop iteration)
@@ -936,6 +938,93 @@ int execute_pair(nw_plan* p, const nw::WDesc& d, const void* xa, const void* xb,
     return NW_OK;
 }
 
+// Multi-channel connectivity (nw_execute_conn): per chunk of max_batch / nchan epochs the
+// (ec, nchan, n) block of x is staged as it lies (epoch-major), the complex rows of its ec * nchan
+// signals go to the scratch execute_pair uses (any form), and nw_conn_accumulate_kernel adds every
+// pair's products of the chunk into the fp64 accumulators, which it reads and writes once per
+// chunk; nw_conn_power_kernel adds |y|^2 per channel.  The accumulators and the tile descriptors
+// (built and uploaded once per call) share d_acc.
+int execute_conn(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ia,
+                 const int32_t* ib, int64_t npairs, void* out_cross, void* out_power, int out_kind, bool host) {
+    const bool plv = out_kind == NW_OUT_PLV_SUM;
+    const int64_t fn = (int64_t)p->nfreq * p->n_out();
+    const size_t cross_bytes = (size_t)npairs * fn * 2 * sizeof(double);
+    const size_t power_bytes = out_power ? (size_t)nchan * fn * sizeof(double) : 0;
+    p->conn_tiles = nw::host::conn_tiles(ia, ib, npairs, nullptr);
+    const size_t tile_bytes = p->conn_tiles.size() * sizeof(nw::ConnTile);
+    const size_t acc_bytes = cross_bytes + power_bytes;   // multiples of 16
+    const int got = p->d_acc.ensure(acc_bytes + tile_bytes + 16);
+    if (got != NW_OK && got != NW_E_NOMEM) return got;
+    if (got == NW_E_NOMEM)
+        return fail(NW_E_NOMEM, "nw_execute_conn: the fp64 accumulators of " + std::to_string(npairs) + " pairs and " +
+                                    std::to_string(out_power ? nchan : 0) + " channels need " +
+                                    std::to_string(acc_bytes + tile_bytes + 16) + " bytes of device memory: " + g_last_error);
+    char* const cross = p->d_acc.at(0);
+    double* const power = out_power ? (double*)p->d_acc.at(cross_bytes) : nullptr;
+    const nw::ConnTile* const tiles = (const nw::ConnTile*)p->d_acc.at(acc_bytes);
+    if (acc_bytes) NW_HIP(hipMemsetAsync(cross, 0, acc_bytes, p->stream));
+    if (tile_bytes)
+        NW_HIP(hipMemcpyAsync((void*)tiles, p->conn_tiles.data(), tile_bytes, hipMemcpyHostToDevice, p->stream));
+    // block order: pair tiles of one (scale, sample tile) neighbours on one XCD (conn_slot);
+    // NW_CONN_PLAIN_ORDER (diagnostics: the A/B of tools/conn_rate.py) keeps plain block order
+    const bool xcd = !std::getenv("NW_CONN_PLAIN_ORDER");
+    const int64_t per = p->max_batch / nchan;
+    nw_logf(1, "plan %p: %s over %lld epochs x %d channels, %lld pairs in %lld tiles (%lld epochs per chunk): "
+               "per-signal rows per chunk, every pair added in epoch order in fp64",
+            (void*)p, out_name(out_kind), (long long)nepochs, nchan, (long long)npairs, (long long)p->conn_tiles.size(),
+            (long long)per);
+    p->stats.reduce_path = NW_REDUCE_CONN;
+    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
+    if (p->form == FORM_ROCFFT) {
+        NW_TRY(need_Y(p, p->nfreq));
+        scratch = p->d_Y.ptr;
+    } else {
+        NW_TRY(p->d_out.ensure((size_t)p->max_batch * fn * 2 * p->esz));
+        scratch = p->d_out.ptr;
+    }
+    const size_t epoch_bytes = (size_t)nchan * p->n * p->esz;
+    for (int64_t e0 = 0; e0 < nepochs; e0 += per) {
+        const int64_t ec = std::min<int64_t>(per, nepochs - e0);
+        const void* xs = (const char*)x + (size_t)e0 * epoch_bytes;
+        if (host) {
+            NW_TRY(staged(p, ST_COPY, [&] {
+                NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, (size_t)ec * epoch_bytes, hipMemcpyHostToDevice, p->stream));
+                return NW_OK;
+            }));
+            xs = p->d_x.ptr;
+        }
+        NW_TRY(run_chunk(p, d, xs, ec * nchan, scratch, NW_OUT_CWT, false));
+        // chained: run_chunk ends with a stage
+        NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, true,
+                               nw::launch_conn_accumulate(p->dtype, plv, scratch, cross, power, tiles,
+                                                          (int)p->conn_tiles.size(), ec, nchan, p->nfreq, p->n_out(),
+                                                          npairs, xcd, p->stream)));
+        p->stats.chunks++;
+    }
+    const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (cross_bytes) NW_HIP(hipMemcpyAsync(out_cross, cross, cross_bytes, back, p->stream));
+    if (power_bytes) NW_HIP(hipMemcpyAsync(out_power, power, power_bytes, back, p->stream));
+    p->stats.executes++;
+    if (host) {
+        NW_HIP(hipStreamSynchronize(p->stream));
+        NW_TRY(resolve_timing(p));
+    }
+    return NW_OK;
+}
+
+// the pair list of nw_conn_tiles / nw_execute_conn: indices inside [0, nchan)
+int check_pairs(const char* who, int32_t nchan, const int32_t* ia, const int32_t* ib, int64_t npairs) {
+    if (nchan < 1) return fail(NW_E_INVALID, std::string(who) + ": nchan < 1");
+    if (npairs < 0) return fail(NW_E_INVALID, std::string(who) + ": npairs < 0");
+    if (npairs > 0x7fffffff) return fail(NW_E_INVALID, std::string(who) + ": more than 2^31 - 1 pairs");
+    if (npairs > 0 && (!ia || !ib)) return fail(NW_E_INVALID, std::string(who) + ": null pair list");
+    for (int64_t q = 0; q < npairs; ++q)
+        if (ia[q] < 0 || ia[q] >= nchan || ib[q] < 0 || ib[q] >= nchan)
+            return fail(NW_E_INVALID, std::string(who) + ": pair " + std::to_string(q) + " = (" + std::to_string(ia[q]) +
+                                          ", " + std::to_string(ib[q]) + ") is outside [0, " + std::to_string(nchan) + ")");
+    return NW_OK;
+}
+
 // ---- page-locked result buffers (nw_host_alloc): a destination inside one is written by DMA
 std::mutex g_host_mu;
 std::map<uintptr_t, size_t> g_host_bufs;   // base -> bytes
@@ -1398,6 +1487,42 @@ int nw_execute_pair(nw_plan* p, const void* xa, const void* xb, int64_t npairs, 
     nw_logf(1, "plan %p: execute %s, %lld pairs, %s buffers", (void*)p, out_name(out_kind), (long long)npairs,
             mem == NW_MEM_HOST ? "host" : "device");
     NW_TRY(execute_pair(p, d, xa, xb, npairs, out, out_kind, mem == NW_MEM_HOST));
+    return dcheck_collect(p->stream);
+}
+
+int nw_conn_tiles(int32_t nchan, const int32_t* ia, const int32_t* ib, int64_t npairs, int32_t* tile_of_pair,
+                  int64_t* ntiles, int32_t* limits) {
+    if (!ntiles) return fail(NW_E_INVALID, "nw_conn_tiles: null argument");
+    NW_TRY(check_pairs("nw_conn_tiles", nchan, ia, ib, npairs));
+    *ntiles = (int64_t)nw::host::conn_tiles(ia, ib, npairs, tile_of_pair).size();
+    if (limits) limits[0] = nw::kConnCh, limits[1] = nw::kConnPairs, limits[2] = nw::kConnTileN;
+    return NW_OK;
+}
+
+int nw_execute_conn(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ia, const int32_t* ib,
+                    int64_t npairs, void* out_cross, void* out_power, int out_kind, int mem) {
+    if (!p || (!x && nepochs > 0) || (!out_cross && npairs > 0))
+        return fail(NW_E_INVALID, "nw_execute_conn: null argument");
+    if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_conn: nw_plan_set_wavelet first");
+    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM)
+        return fail(NW_E_INVALID, "nw_execute_conn: out_kind must be NW_OUT_CROSS_SUM or NW_OUT_PLV_SUM");
+    if (out_kind == NW_OUT_PLV_SUM && out_power)
+        return fail(NW_E_INVALID, "nw_execute_conn: NW_OUT_PLV_SUM forms no power sums: out_power must be NULL");
+    if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_conn: bad mem");
+    if (nepochs < 0) return fail(NW_E_INVALID, "nw_execute_conn: nepochs < 0");
+    NW_TRY(check_pairs("nw_execute_conn", nchan, ia, ib, npairs));
+    if (p->max_batch < nchan)
+        return fail(NW_E_INVALID, "nw_execute_conn: the plan's max_batch (" + std::to_string(p->max_batch) +
+                                      ") must be >= nchan (" + std::to_string(nchan) +
+                                      "): a chunk holds max_batch / nchan epochs");
+    DeviceGuard guard(p->device);
+    p->executed = true;
+    const nw::WDesc d = exec_rows(p);
+    // settle the form of a tentative length before any buffer choice
+    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
+    nw_logf(1, "plan %p: execute conn %s, %lld epochs x %d channels, %lld pairs, %s buffers", (void*)p, out_name(out_kind),
+            (long long)nepochs, (int)nchan, (long long)npairs, mem == NW_MEM_HOST ? "host" : "device");
+    NW_TRY(execute_conn(p, d, x, nepochs, nchan, ia, ib, npairs, out_cross, out_power, out_kind, mem == NW_MEM_HOST));
     return dcheck_collect(p->stream);
 }
 

@@ -1,0 +1,192 @@
+// nw_conn.hip — multi-channel connectivity (nw_execute_conn): the complex rows of a chunk of
+// epochs x channels reduced into the cross sums of MANY channel pairs at once.
+//
+//   src   [((e * C + c) * F + f) * n_out + t]   complex T: the chunk's rows, epoch-major
+//   cross [(p * F + f) * n_out + t]             complex fp64: S_p (PLV: Phi_p), p = (ia[p], ib[p])
+//   power [(c * F + f) * n_out + t]             fp64: P_cc (not for PLV)
+//
+// Per pair and epoch the terms are k_accumulate_pair's (nw_kernels.hip), added in epoch order:
+// fp64 values, every product and every term rounded on its own (no fma into the sum), for PLV
+// each value divided by its hypot first.  A pair's sums are therefore the bits nw_execute_pair
+// gives for the same two channels on its per-signal-rows path, however the epochs are chunked.
+//
+// nw_conn_accumulate_kernel: a block owns one scale f, kConnTileN = 64 consecutive samples
+// (lane = sample: every global and LDS access is lane-contiguous) and one pair tile (<= 64 pairs
+// over <= 16 distinct channels, host::conn_tiles).  Wave w of its 4 keeps the accumulators of the
+// pairs w, w + 4, ... in registers (<= 16 pairs x 2 doubles), loaded from `cross` once per launch
+// and stored once, so the read-modify-write of `cross` costs one read and one write per chunk,
+// not per epoch.  Per epoch the tile's channels are staged once in LDS as fp64 (PLV: as unit
+// phasors, so a value is normalised once, not once per pair it enters); the staging is double
+// buffered: the next epoch's global loads are issued before the current epoch is consumed and
+// written to the other buffer after it, one barrier per epoch.
+// nw_conn_power_kernel adds P_cc: one thread per (c, f, t).
+#include <algorithm>
+
+#include "nw_dcheck.h"
+#include "nw_internal.h"
+
+namespace nw {
+namespace {
+
+// a rounded fp64 product that the compiler may not fuse into a following add (as nw_kernels.hip)
+__device__ __forceinline__ double mul_nc(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ double add_nc(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+constexpr int kConnThreads = kConnWaves * 64;
+constexpr int kConnStage = kConnCh / kConnWaves;   // channels a wave stages per epoch
+
+template <typename T, bool PLV>
+__global__ __launch_bounds__(kConnThreads) void nw_conn_accumulate_kernel(
+    const cplx<T>* __restrict__ src, double2* __restrict__ cross, const ConnTile* __restrict__ tiles, int ntiles,
+    int64_t ec, int nchan, int nfreq, int64_t n_out, int64_t npairs, int64_t nunits, int xcd) {
+    static_assert(kConnTileN == 64, "lane = sample of the tile");
+    __shared__ double stage[2][kConnCh][2][kConnTileN];   // [buffer][slot][re, im][sample]: 32 KiB
+
+    const ConnSlot sl = conn_slot((int64_t)blockIdx.x, ntiles, xcd != 0);
+    if (sl.unit >= nunits) return;   // padding of the XCD order (the whole block)
+    NW_DCHECK(sl.tile >= 0 && sl.tile < ntiles);
+    const int64_t ntn = (n_out + kConnTileN - 1) / kConnTileN;
+    const int f = (int)(sl.unit / ntn);
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t t = (sl.unit % ntn) * kConnTileN + lane;
+    const bool live = t < n_out;     // samples past the row's end are neither read nor written
+    NW_DCHECK(f >= 0 && f < nfreq);
+    const ConnTile& tile = tiles[sl.tile];
+    const int nch = tile.nch, np = tile.npairs;
+    NW_DCHECK(nch >= 0 && nch <= kConnCh && np >= 0 && np <= kConnPairs);
+    const int64_t fn = (int64_t)nfreq * n_out;
+    const int64_t ft = (int64_t)f * n_out + t;
+
+    // (an array of structs: two plain double[16] are rewritten into <16 x double> vectors before the
+    // loops unroll and then live in 32-register tuples, 1412 B of scratch; tools/regs.py)
+    struct Acc { double re, im; } acc[kConnPerWave];
+#pragma unroll
+    for (int k = 0; k < kConnPerWave; ++k) {
+        const int j = w + k * kConnWaves;
+        acc[k].re = acc[k].im = 0.0;
+        if (j < np && live) {
+            const int64_t o = tile.out[j];
+            NW_DCHECK(o >= 0 && o < npairs && o * fn + ft < npairs * fn);
+            const double2 v = cross[o * fn + ft];
+            acc[k].re = v.x, acc[k].im = v.y;
+        }
+    }
+
+    cplx<T> in[kConnStage];
+    auto load = [&](int64_t e) {
+#pragma unroll
+        for (int q = 0; q < kConnStage; ++q) {
+            const int s = w + q * kConnWaves;
+            in[q] = cplx<T>{T(0), T(0)};
+            if (s < nch && live) {
+                const int64_t c = tile.ch[s];
+                NW_DCHECK(c >= 0 && c < nchan && e >= 0 && e < ec && (e * nchan + c) * fn + ft < ec * nchan * fn);
+                in[q] = src[(e * nchan + c) * fn + ft];
+            }
+        }
+    };
+    auto store = [&](int buf) {
+#pragma unroll
+        for (int q = 0; q < kConnStage; ++q) {
+            const int s = w + q * kConnWaves;
+            if (s < nch) {
+                double re = (double)in[q].re, im = (double)in[q].im;
+                if constexpr (PLV) {
+                    const double m = hypot(re, im);
+                    re /= m, im /= m;
+                }
+                stage[buf][s][0][lane] = re;
+                stage[buf][s][1][lane] = im;
+            }
+        }
+    };
+
+    if (ec > 0) {
+        load(0);
+        store(0);
+    }
+    __syncthreads();
+    for (int64_t e = 0; e < ec; ++e) {
+        const int cur = (int)(e & 1);
+        const bool more = e + 1 < ec;
+        if (more) load(e + 1);
+#pragma unroll
+        for (int k = 0; k < kConnPerWave; ++k) {
+            const int j = w + k * kConnWaves;
+            if (j < np) {
+                const int a = tile.sa[j], b = tile.sb[j];
+                NW_DCHECK(a >= 0 && a < nch && b >= 0 && b < nch);
+                const double ar = stage[cur][a][0][lane], ai = stage[cur][a][1][lane];
+                const double br = stage[cur][b][0][lane], bi = stage[cur][b][1][lane];
+                acc[k].re += add_nc(mul_nc(ar, br), mul_nc(ai, bi));
+                acc[k].im += add_nc(mul_nc(ai, br), -mul_nc(ar, bi));
+            }
+        }
+        // the other buffer was last read before the previous barrier
+        if (more) store(cur ^ 1);
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int k = 0; k < kConnPerWave; ++k) {
+        const int j = w + k * kConnWaves;
+        if (j < np && live) {
+            const int64_t o = tile.out[j];
+            NW_DCHECK(o >= 0 && o < npairs && o * fn + ft < npairs * fn);
+            cross[o * fn + ft] = double2{acc[k].re, acc[k].im};
+        }
+    }
+}
+
+// power[c, f, t] += sum_e |y_{e,c}[f, t]|^2, the term k_accumulate_pair adds to P_aa
+template <typename T>
+__global__ __launch_bounds__(256) void nw_conn_power_kernel(const cplx<T>* __restrict__ src, double* __restrict__ power,
+                                                            int64_t ec, int nchan, int64_t fn) {
+    const int64_t count = (int64_t)nchan * fn;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        NW_DCHECK(i >= 0 && i < count);
+        double p = power[i];
+        for (int64_t e = 0; e < ec; ++e) {
+            NW_DCHECK(e * count + i < ec * count);
+            const cplx<T> v = src[e * count + i];
+            const double re = (double)v.re, im = (double)v.im;
+            p += add_nc(mul_nc(re, re), mul_nc(im, im));
+        }
+        power[i] = p;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_conn_accumulate(int dtype, bool plv, const void* src, void* cross, double* power,
+                                  const ConnTile* tiles, int ntiles, int64_t ec, int nchan, int nfreq, int64_t n_out,
+                                  int64_t npairs, bool xcd, hipStream_t s) {
+    const int64_t nunits = conn_units(nfreq, n_out);
+    const int64_t blocks = ntiles > 0 ? conn_blocks(nunits, ntiles, xcd) : 0;
+    if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+    for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (blocks > 0)
+            for_bool(plv, [&](auto v) {
+                nw_launch(nw_conn_accumulate_kernel<T, decltype(v)::value>, dim3((unsigned)blocks), dim3(kConnThreads), 0, s,
+                          (const cplx<T>*)src, (double2*)cross, tiles, ntiles, ec, nchan, nfreq, n_out, npairs, nunits,
+                          xcd ? 1 : 0);
+            });
+        if (power) {
+            const int64_t fn = (int64_t)nfreq * n_out;
+            const int64_t pb = std::max<int64_t>(1, std::min<int64_t>(((int64_t)nchan * fn + 255) / 256, 256 * 32));
+            nw_launch(nw_conn_power_kernel<T>, dim3((unsigned)pb), dim3(256), 0, s, (const cplx<T>*)src, power, ec, nchan, fn);
+        }
+    });
+    return hipGetLastError();
+}
+
+}  // namespace nw

@@ -154,6 +154,41 @@ void block_of(int64_t nsig, int i, int n, int64_t* s0, int64_t* cnt) {
     *cnt = base + (i < extra ? 1 : 0);
 }
 
+std::vector<ConnTile> conn_tiles(const int32_t* ia, const int32_t* ib, int64_t npairs, int32_t* tile_of_pair) {
+    std::vector<int64_t> order((size_t)npairs);
+    for (int64_t p = 0; p < npairs; ++p) order[(size_t)p] = p;
+    std::stable_sort(order.begin(), order.end(), [&](int64_t p, int64_t q) {
+        const int32_t kp[4] = {ia[p] / 8, ib[p] / 8, ia[p], ib[p]}, kq[4] = {ia[q] / 8, ib[q] / 8, ia[q], ib[q]};
+        return std::lexicographical_compare(kp, kp + 4, kq, kq + 4);
+    });
+    std::vector<ConnTile> tiles;
+    // the slot of channel c in tile t, appended if absent; -1: the tile's channel list is full
+    auto slot_of = [](ConnTile& t, int32_t c, bool add) {
+        for (int s = 0; s < t.nch; ++s)
+            if (t.ch[s] == c) return s;
+        if (!add || t.nch == kConnCh) return -1;
+        t.ch[t.nch] = c;
+        return (int)t.nch++;
+    };
+    for (int64_t p : order) {
+        const int32_t a = ia[p], b = ib[p];
+        bool fits = !tiles.empty() && tiles.back().npairs < kConnPairs;
+        if (fits) {
+            ConnTile& t = tiles.back();
+            const int fresh = (slot_of(t, a, false) < 0) + (b != a && slot_of(t, b, false) < 0);
+            fits = t.nch + fresh <= kConnCh;
+        }
+        if (!fits) tiles.push_back(ConnTile{});
+        ConnTile& t = tiles.back();
+        const int k = t.npairs++;
+        t.sa[k] = slot_of(t, a, true);
+        t.sb[k] = slot_of(t, b, true);
+        t.out[k] = (int32_t)p;
+        if (tile_of_pair) tile_of_pair[p] = (int32_t)(tiles.size() - 1);
+    }
+    return tiles;
+}
+
 void parallel_copy(char* dst, const char* src, size_t bytes, unsigned max_threads) {
     const size_t min_share = size_t(4) << 20;
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());

@@ -9,6 +9,8 @@
 
 #include <vector>
 
+#include "nw_shape.h"
+
 namespace nw {
 
 // One WaveletMode.Normal row (base.py:196-216, 249-256): an np.arange timeline
@@ -51,6 +53,14 @@ RowGroups group_rows(bool shannon, int F, const double* freqs, const double* tab
 
 // Balanced contiguous blocks: nsig / n per part, one more for the first nsig % n parts.
 void block_of(int64_t nsig, int i, int n, int64_t* s0, int64_t* cnt);
+
+// Pair tiles of nw_execute_conn (nw_shape.h: ConnTile, kConnPairs, kConnCh): the npairs pairs
+// (ia[p], ib[p]) -- any list: repeats, a > b, a == b -- sorted by (a / 8, b / 8, a, b) and packed
+// greedily, a tile closing when the next pair would be its kConnPairs + 1-th or bring it past
+// kConnCh distinct channels.  All pairs a < b of C channels give at most m (m + 1) / 2 tiles,
+// m = ceil(C / 8).  tile_of_pair (may be null) receives each pair's tile.  The indices must lie
+// in [0, nchan): the caller checks.
+std::vector<ConnTile> conn_tiles(const int32_t* ia, const int32_t* ib, int64_t npairs, int32_t* tile_of_pair);
 
 // memcpy split over up to max_threads host threads (>= 4 MiB per thread).
 void parallel_copy(char* dst, const char* src, size_t bytes, unsigned max_threads);

@@ -226,6 +226,13 @@ hipError_t launch_accumulate(int dtype, int src_kind, const void* src, double* a
 // acc += their cross sums (4 fp64 per point) or, plv, unit-phasor products (2 per point)
 hipError_t launch_accumulate_pair(int dtype, bool plv, const void* src, double* acc, int64_t fn, int64_t c,
                                   hipStream_t s);
+// connectivity (nw_conn.hip): src = the complex rows (ec, nchan, F, n_out) of ec epochs; cross
+// (npairs, F, n_out) complex fp64 += per pair tile and epoch, in epoch order, k_accumulate_pair's
+// terms (plv: of the unit phasors); power (nchan, F, n_out) fp64 += |y|^2 (null: not formed).
+// tiles: device array of ntiles ConnTile (host::conn_tiles).  xcd: the block order (conn_slot).
+hipError_t launch_conn_accumulate(int dtype, bool plv, const void* src, void* cross, double* power,
+                                  const ConnTile* tiles, int ntiles, int64_t ec, int nchan, int nfreq, int64_t n_out,
+                                  int64_t npairs, bool xcd, hipStream_t s);
 hipError_t launch_finalize(int dtype, bool itc, const double* acc, void* out, int64_t fn, int64_t nsig,
                            hipStream_t s);
 hipError_t launch_add_f64(double* acc, const double* src, int64_t count, hipStream_t s);

@@ -8,6 +8,7 @@
 //   - block shapes (signals per block, XCD tiles) of the one-pass kernels;
 //   - the W-table layout, the support rounding and the pass-0 ladders;
 //   - which partial-sum kernels exist;
+//   - the connectivity kernel (nw_conn.hip): its pair tile, sample tile and block order;
 //   - the two-pass engine (nw_large.hip): the (N1, N2) split and its visitor, the row pass's
 //     elements per thread, rows per block, pass-0 ladder and LDS-DMA rule, the column pass's
 //     block shape, the scale chunk and the support buffer's layout (mode `large` prints them);
@@ -284,6 +285,45 @@ constexpr bool pair_partials_supported(int64_t n, int dtype, int kind, int out_k
     const bool xs = n == 1024 ? kPairXSumOK<1024> : n == 2048 ? kPairXSumOK<2048> : n == 4096 ? kPairXSumOK<4096> : false;
     const bool ps = n == 1024 ? kPairPlvSumOK<1024> : n == 2048 ? kPairPlvSumOK<2048> : n == 4096 ? kPairPlvSumOK<4096> : false;
     return out_kind == NW_OUT_CROSS_SUM ? xs : out_kind == NW_OUT_PLV_SUM ? ps : false;
+}
+
+// ---- multi-channel connectivity (nw_conn.hip) -------------------------------------------------
+
+// nw_conn_accumulate_kernel: a block owns one scale, kConnTileN consecutive output samples (lane =
+// sample) and one pair tile: at most kConnPairs pairs that together touch at most kConnCh distinct
+// channels (the host tiler nw::host::conn_tiles).  Its kConnWaves waves split the tile's pairs
+// (wave w: pairs w, w + kConnWaves, ...), so a wave keeps kConnPairs / kConnWaves complex fp64
+// accumulators in registers; per epoch the tile's channels are staged once in LDS as fp64.
+constexpr int kConnPairs = 64;
+constexpr int kConnCh = 16;
+constexpr int kConnTileN = 64;
+constexpr int kConnWaves = 4;
+constexpr int kConnPerWave = kConnPairs / kConnWaves;
+static_assert(kConnPairs % kConnWaves == 0 && kConnCh % kConnWaves == 0, "conn geometry");
+// One pair tile as the kernel reads it: the channels it stages, and per pair the two staging slots
+// (indices into ch[]) and the row of the caller's pair list the sums belong to.
+struct ConnTile {
+    int32_t nch, npairs;
+    int32_t ch[kConnCh];
+    int32_t sa[kConnPairs], sb[kConnPairs], out[kConnPairs];
+};
+// block -> (unit, pair tile), a unit being one (scale, sample tile).  xcd = true: blocks b, b + 8,
+// ... share an XCD, and the pair tiles of one unit are consecutive among them, so the unit's rows
+// are read from HBM once and then from that XCD's L2; units are padded to a multiple of 8 (a slot
+// with unit >= nunits is padding and its block returns).  xcd = false: pair tile fastest in plain
+// block order (consecutive blocks go to consecutive XCDs).
+struct ConnSlot {
+    int64_t unit;
+    int tile;
+};
+NW_SHAPE_HD NW_INLINE ConnSlot conn_slot(int64_t b, int ntiles, bool xcd) {
+    if (!xcd) return {b / ntiles, (int)(b % ntiles)};
+    const int64_t local = b >> 3;
+    return {(local / ntiles) * 8 + (b & 7), (int)(local % ntiles)};
+}
+constexpr int64_t conn_units(int nfreq, int64_t n_out) { return (int64_t)nfreq * ((n_out + kConnTileN - 1) / kConnTileN); }
+constexpr int64_t conn_blocks(int64_t nunits, int ntiles, bool xcd) {
+    return (xcd ? (nunits + 7) / 8 * 8 : nunits) * ntiles;
 }
 
 // ---- the two-pass engine (nw_large.hip) -----------------------------------------------------

@@ -26,6 +26,12 @@ PAIR_KINDS = {'cross_sum': L.NW_OUT_CROSS_SUM, 'plv_sum': L.NW_OUT_PLV_SUM}
 # what finalize_pair forms from them: name -> the sums it needs
 PAIR_OUTS = {'cross_sum': 'cross_sum', 'plv_sum': 'plv_sum', 'csd': 'cross_sum', 'coherency': 'cross_sum',
              'coherence': 'cross_sum', 'imcoh': 'cross_sum', 'plv': 'plv_sum'}
+# multi-channel connectivity (Plan.execute_conn): the same two sums for every channel pair of a list,
+# cross_sum -> complex128 (P, F, n) + float64 (C, F, n), plv_sum -> complex128 (P, F, n); and what
+# finalize_conn forms from them
+CONN_KINDS = {'cross_sum': L.NW_OUT_CROSS_SUM, 'plv_sum': L.NW_OUT_PLV_SUM}
+CONN_OUTS = {'cross_sum': 'cross_sum', 'plv_sum': 'plv_sum', 'csd': 'cross_sum', 'coherency': 'cross_sum',
+             'coherence': 'cross_sum', 'imcoh': 'cross_sum', 'plv': 'plv_sum'}
 KINDS = {'morse': L.NW_MORSE, 'morlet': L.NW_MORLET, 'shannon': L.NW_SHANNON, 'table': L.NW_TABLE,
          # WaveletMode.Normal tables built on the device (base.py:249-256)
          'mexican_hat': L.NW_MEXICAN_HAT, 'haar': L.NW_HAAR}
@@ -90,6 +96,60 @@ def finalize_pair(kind: str, sums: np.ndarray, npairs: int) -> np.ndarray:
     if kind in ('csd', 'coherency'):
         return ratio
     return np.abs(ratio) if kind == 'coherence' else np.ascontiguousarray(ratio.imag)
+
+
+def all_pairs(nchan: int):
+    """(ia, ib), int32: every channel pair a < b of ``nchan`` channels in np.triu_indices(nchan, 1)
+    order, the default pair list of the connectivity calls."""
+    ia, ib = np.triu_indices(int(nchan), 1)
+    return ia.astype(np.int32), ib.astype(np.int32)
+
+
+def check_indices(indices, nchan: int):
+    """``indices`` = (ia, ib), two equally long 1-D lists of channel positions in [0, nchan)
+    (None: all_pairs(nchan)), as contiguous int32 arrays; ValueError otherwise.  Any list is
+    allowed: repeated pairs, a > b, a == b."""
+    if indices is None:
+        return all_pairs(nchan)
+    try:
+        ia, ib = indices
+        ia, ib = np.asarray(ia), np.asarray(ib)
+    except (TypeError, ValueError):
+        raise ValueError('indices must be a pair (ia, ib) of index lists') from None
+    if ia.ndim != 1 or ib.ndim != 1 or ia.shape != ib.shape:
+        raise ValueError(f'indices must be two 1-D lists of equal length, got shapes {ia.shape} and {ib.shape}')
+    if ia.size and not (np.issubdtype(ia.dtype, np.integer) and np.issubdtype(ib.dtype, np.integer)):
+        raise ValueError(f'indices must be integers, got {ia.dtype} and {ib.dtype}')
+    if ia.size and (min(ia.min(), ib.min()) < 0 or max(ia.max(), ib.max()) >= nchan):
+        raise ValueError(f'indices must lie in [0, {nchan}): got {int(min(ia.min(), ib.min()))} .. '
+                         f'{int(max(ia.max(), ib.max()))}')
+    return np.ascontiguousarray(ia, dtype=np.int32), np.ascontiguousarray(ib, dtype=np.int32)
+
+
+def finalize_conn(kind: str, cross: np.ndarray, power, ia, ib, nepochs: int):
+    """The connectivity measure ``kind`` of every pair p = (ia[p], ib[p]) from the sums over
+    ``nepochs`` epochs that Plan.execute_conn returns: ``cross`` complex128 (P, F, n) = S_p (for
+    ``plv`` / ``plv_sum``: Phi_p) and ``power`` float64 (C, F, n) = P_cc (unused, may be None, for
+    the two plv kinds).  finalize_pair is applied pair by pair to stack(Re S, Im S, P_aa, P_bb), so
+    the rounding is that of the two-channel calls (the coherence of a channel with itself is
+    exactly 1) and only one pair's intermediate arrays exist at a time.  ``cross_sum`` returns
+    (cross, power) and ``plv_sum`` returns cross; the others (P, F, n): csd and coherency
+    complex128, coherence, imcoh and plv float64."""
+    if kind not in CONN_OUTS:
+        raise ValueError(f"out must be one of {', '.join(CONN_OUTS)}; got {kind!r}")
+    if kind == 'cross_sum':
+        return cross, power
+    if kind == 'plv_sum':
+        return cross
+    cross = np.asarray(cross, dtype=np.complex128)
+    out = np.empty(cross.shape, dtype=np.complex128 if kind in ('csd', 'coherency') else np.float64)
+    for p in range(cross.shape[0]):
+        if kind == 'plv':
+            out[p] = finalize_pair('plv', cross[p], nepochs)
+        else:
+            sums = np.stack([cross[p].real, cross[p].imag, power[ia[p]], power[ib[p]]], axis=-1)
+            out[p] = finalize_pair(kind, sums, nepochs)
+    return out
 
 
 class HostPool:
@@ -438,6 +498,65 @@ class Plan:
         L.check(L.lib().nw_execute_pair(self._h, xa.ctypes.data_as(ctypes.c_void_p), xb.ctypes.data_as(ctypes.c_void_p),
                                         npairs, out.ctypes.data_as(ctypes.c_void_p), kind, L.NW_MEM_HOST))
         return out
+
+    def execute_conn(self, x, indices=None, out=None, out_kind: str = 'cross_sum'):
+        """Multi-channel connectivity sums (nw_execute_conn): x (E, C, n), the E epochs of C
+        channels, every signal transformed once and reduced on the device into the sums of the
+        pairs ``indices`` = (ia, ib) (default all_pairs(C)).  ``cross_sum`` -> (cross complex128
+        (P, nfreq, n_out) = sum_e y_a conj(y_b), power float64 (C, nfreq, n_out) = sum_e |y_c|^2);
+        ``plv_sum`` -> complex128 (P, nfreq, n_out); see finalize_conn.  numpy arrays: synchronous,
+        ``out`` optional.  Device tensors: asynchronous on the plan stream, ``out`` required:
+        (cross, power) tensors for cross_sum (power may be None: not formed), the tensor for
+        plv_sum.  The plan needs max_batch >= C (a chunk holds max_batch // C epochs)."""
+        if out_kind not in CONN_KINDS:
+            raise ValueError(f"out_kind must be one of {', '.join(CONN_KINDS)}; got {out_kind!r}")
+        kind = CONN_KINDS[out_kind]
+        plv = out_kind == 'plv_sum'
+        if getattr(x, 'ndim', 0) != 3:
+            raise ValueError(f'x must be (epochs, channels, n), got shape {tuple(getattr(x, "shape", ()))}')
+        nep, nchan = int(x.shape[0]), int(x.shape[1])
+        ia, ib = check_indices(indices, nchan)
+        npairs = int(ia.size)
+        fn = self.nfreq * self.n_out
+        P = ctypes.c_void_p
+        ip = (ia.ctypes.data_as(P), ib.ctypes.data_as(P))
+        if _is_device_tensor(x):
+            import torch
+            if out is None:
+                raise ValueError('device execute needs output tensors')
+            if self._check_device_input(x) != nep * nchan:
+                raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
+            cross, power = (out, None) if plv else out
+            for t, dt, count, name in ((cross, torch.complex128, npairs * fn, 'cross'),
+                                       (power, torch.float64, nchan * fn, 'power')):
+                if t is None and name == 'power':
+                    continue
+                if not _is_device_tensor(t) or t.dtype != dt:
+                    raise ValueError(f'device output {name} must be a {dt} tensor on device {self.device}')
+                if not t.is_contiguous() or t.numel() != count:
+                    raise ValueError(f'device output {name} must be contiguous and hold {count} values')
+                if t.device.index != self.device:
+                    raise ValueError(f'device buffers must live on device {self.device}')
+            with self._ordered_with_torch(x.device):
+                L.check(L.lib().nw_execute_conn(self._h, P(x.data_ptr()), nep, nchan, *ip, npairs, P(cross.data_ptr()),
+                                                P(power.data_ptr()) if power is not None else None, kind,
+                                                L.NW_MEM_DEVICE))
+            return out
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        if x.shape[-1] != self.n:
+            raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
+        cross, power = (out, None) if plv or out is None else out
+        shapes = (((npairs, self.nfreq, self.n_out), np.complex128), ((nchan, self.nfreq, self.n_out), np.float64))
+        if cross is None:
+            cross = np.empty(*shapes[0])
+        if power is None and not plv:
+            power = np.empty(*shapes[1])
+        for a, (shape, dt) in zip((cross, power), shapes):
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or a.size != int(np.prod(shape))):
+                raise ValueError('out must be C-contiguous arrays of the right dtype and size')
+        L.check(L.lib().nw_execute_conn(self._h, x.ctypes.data_as(P), nep, nchan, *ip, npairs, cross.ctypes.data_as(P),
+                                        None if plv else power.ctypes.data_as(P), kind, L.NW_MEM_HOST))
+        return cross if plv else (cross, power)
 
     def stream_ptr(self) -> int:
         """The hipStream_t the plan launches on."""

@@ -61,3 +61,15 @@ class EpochsWavelet:
         """Phase-locking value |mean_e (cwt_a / |cwt_a|) conj(cwt_b / |cwt_b|)|, (F, N) float64; a
         point where some epoch has |cwt| = 0 is NaN, as itc."""
         return self._cross(ch_a, ch_b, freqs, 'plv', decim)
+
+    # -- connectivity between many channels: one transform per epoch and channel, every pair's
+    #    sums from it (WaveletBase.connectivity_batch; no reference counterpart) ---------------
+    def connectivity(self, ch_names, freqs, method: str = 'coherence', indices=None, decim: int = 1):
+        """``method`` (cross_batch's outs: coherence, imcoh, coherency, csd, plv, ...) for the
+        channel pairs ``indices`` = (ia, ib), positions in ``ch_names`` (default: every pair
+        a < b), (P, F, N): what mne-connectivity's spectral_connectivity_epochs(..., indices=...)
+        returns per pair in its cwt_morlet mode."""
+        ch_names = list(ch_names)
+        idx = [self.epochs.ch_names.index(c) for c in ch_names]
+        waves = self.epochs.get_data()[:, idx, :]
+        return self.wavelet.connectivity_batch(waves, freqs, reuse=True, out=method, indices=indices, decim=decim)

@@ -1,0 +1,143 @@
+"""Multi-channel connectivity on device tensors (the library given by NINWAVE_LIB), NW_TIMING plans,
+warm-up, the arms interleaved in one process, device time = the sum of the stage times of
+nw_plan_stats, wall time around a synchronise.
+
+A  one Plan.execute_conn call over all pairs of C = 8 channels (E = 64 epochs, F = 64 Morse scales)
+   against the 28 Plan.execute_pair calls that give the same sums, the same plan and so the same
+   signals per chunk (128) in both: fp32 n = 4096 (the gate: the single call is faster on both
+   clocks, cross_sum and plv_sum), then fp64 n = 4096 and fp32 n = 1201 for the record.
+B  nw_conn_accumulate_kernel alone (cross_sum without power sums: the epilogue stage is that one
+   kernel) per launch at C = 32, all 496 pairs, fp32, n = 4096, F = 64, ec epochs per chunk, against
+   its algorithmic bytes -- the chunk's rows read once, C ec F n 8 B, plus the accumulators read and
+   written, 2 P F n 16 B -- as a fraction of 8 TB/s, in both block orders (XCD-aware, conn_slot;
+   NW_CONN_PLAIN_ORDER: plain).
+    [EC="2 8 32"] python tools/conn_rate.py [output file, default profiles/r12_conn_rate.txt] [A|B|AB]"""
+import os, sys, time
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+import ninwavelets_amd as nw
+from ninwavelets_amd import _lib as L
+from ninwavelets_amd.engine import all_pairs
+
+STAGES = ('ms_forward', 'ms_multiply', 'ms_inverse', 'ms_epilogue', 'ms_fused', 'ms_copy', 'ms_rows', 'ms_expand')
+HBM = 8e12
+out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'profiles', 'r12_conn_rate.txt')
+parts = sys.argv[2] if len(sys.argv) > 2 else 'AB'
+lines = []
+
+
+def say(text):
+    print(text, flush=True)
+    lines.append(text)
+
+
+def algorithmic_bytes(C, P, F, n, ec, esz):
+    """rows of the chunk read once + the cross accumulators read and written"""
+    return C * ec * F * n * 2 * esz + 2 * P * F * n * 16
+
+
+def timed(plan, fn, reps, arms):
+    """min and median over reps of (device ms, wall ms) per arm, the arms interleaved"""
+    dev = {k: [] for k in arms}
+    wall = {k: [] for k in arms}
+    for k in arms:
+        fn(k); plan.sync(); torch.cuda.synchronize()
+    for _ in range(reps):
+        for k in arms:
+            plan.reset_stats()
+            t0 = time.perf_counter(); fn(k); plan.sync(); torch.cuda.synchronize()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+            st = plan.stats()
+            dev[k].append(sum(st[s] for s in STAGES))
+    return {k: (min(dev[k]), float(np.median(dev[k])), min(wall[k]), float(np.median(wall[k]))) for k in arms}
+
+
+def part_a(dt, n, gate):
+    E, C, F, batch = 64, 8, 64, 128
+    tdt = torch.float32 if dt == 'float32' else torch.float64
+    ia, ib = all_pairs(C)
+    P = len(ia)
+    plan = nw.Plan(n, F, dt, max_batch=batch, timing=True)
+    plan.set_wavelet('morse', [17.5, 3.], np.arange(1., F + 1), L.trans_grid(n / 1000., 1000., False))
+    common = torch.randn((E, 1, n), device='cuda', dtype=tdt)
+    x = (0.6 * common + 0.8 * torch.randn((E, C, n), device='cuda', dtype=tdt)).contiguous()
+    chans = [x[:, c].contiguous() for c in range(C)]            # the pair calls' inputs, made outside the clock
+    oc = torch.empty((P, F, n), device='cuda', dtype=torch.complex128)
+    opw = torch.empty((C, F, n), device='cuda', dtype=torch.float64)
+    pc = torch.empty((F, n, 4), device='cuda', dtype=torch.float64)
+    pp = torch.empty((F, n), device='cuda', dtype=torch.complex128)
+
+    def once(arm):
+        kind, how = arm.split('/')
+        if how == 'conn':
+            plan.execute_conn(x, (ia, ib), out=(oc, opw) if kind == 'cross_sum' else oc, out_kind=kind)
+        else:
+            for a, b in zip(ia, ib):
+                plan.execute_pair(chans[a], chans[b], out=pc if kind == 'cross_sum' else pp, out_kind=kind)
+
+    arms = ('cross_sum/conn', 'cross_sum/pairs', 'plv_sum/conn', 'plv_sum/pairs')
+    r = timed(plan, once, 5, arms)
+    once('cross_sum/pairs')
+    path = plan.stats()['reduce_path']
+    plan.close()
+    ok = True
+    for kind in ('cross_sum', 'plv_sum'):
+        c, p = r[kind + '/conn'], r[kind + '/pairs']
+        say('A %s n=%d C=%d E=%d F=%d %-9s one execute_conn: device %.3f ms (median %.3f) wall %.3f ms (median %.3f) | '
+            '%d execute_pair (reduce_path %d): device %.3f ms (median %.3f) wall %.3f ms (median %.3f) | '
+            'pairs / conn: device %.2fx wall %.2fx' % (dt, n, C, E, F, kind, c[0], c[1], c[2], c[3], P, path, p[0], p[1],
+                                                        p[2], p[3], p[0] / c[0], p[2] / c[2]))
+        ok = ok and c[0] < p[0] and c[2] < p[2]
+    if gate:
+        say('A gate (%s n=%d: the single call faster on both clocks, both kinds): %s' % (dt, n, 'PASS' if ok else 'FAIL'))
+    return ok
+
+
+def part_b(ec):
+    dt, n, F, C = 'float32', 4096, 64, 32
+    ia, ib = all_pairs(C)
+    P = len(ia)
+    E = 2 * ec                                                      # two launches per call
+    plan = nw.Plan(n, F, dt, max_batch=ec * C, timing=True)
+    plan.set_wavelet('morse', [17.5, 3.], np.arange(1., F + 1), L.trans_grid(n / 1000., 1000., False))
+    x = torch.randn((E, C, n), device='cuda', dtype=torch.float32)
+    oc = torch.empty((P, F, n), device='cuda', dtype=torch.complex128)
+    ms = {}
+    for order in ('xcd', 'plain'):
+        os.environ.pop('NW_CONN_PLAIN_ORDER', None)
+        if order == 'plain':
+            os.environ['NW_CONN_PLAIN_ORDER'] = '1'
+        best = []
+        for rep in range(4):
+            plan.reset_stats()
+            plan.execute_conn(x, (ia, ib), out=(oc, None), out_kind='cross_sum'); plan.sync()
+            st = plan.stats()
+            if rep:
+                best.append(st['ms_epilogue'] / st['chunks'])
+        ms[order] = min(best)
+    os.environ.pop('NW_CONN_PLAIN_ORDER', None)
+    plan.close()
+    nbytes = algorithmic_bytes(C, P, F, n, ec, 4)
+    ntiles = L.conn_tiles(C, ia, ib)[1]
+    for order in ('xcd', 'plain'):
+        say('B fp32 n=%d F=%d C=%d P=%d (%d tiles) ec=%d %-5s order: nw_conn_accumulate_kernel %.3f ms per launch, '
+            '%.3f ms per epoch; algorithmic %.3f GB (rows %.3f + accumulators %.3f) -> %.2f TB/s = %.1f %% of 8 TB/s' % (
+                n, F, C, P, ntiles, ec, order, ms[order], ms[order] / ec, nbytes / 1e9, C * ec * F * n * 8 / 1e9,
+                2 * P * F * n * 16 / 1e9, nbytes / ms[order] / 1e9, 100 * nbytes / (ms[order] * 1e-3) / HBM))
+
+
+say('# tools/conn_rate.py on %s, %s' % (torch.cuda.get_device_name(0), os.environ.get('NINWAVE_LIB', 'libninwave.so')))
+gate = True
+if 'A' in parts:
+    gate = part_a('float32', 4096, True)
+    part_a('float64', 4096, False)
+    part_a('float32', 1201, False)
+if 'B' in parts:
+    for ec in [int(v) for v in os.environ.get('EC', '2 8 32').split()]:
+        part_b(ec)
+os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+with open(out_path, 'w') as f:
+    f.write('\n'.join(lines) + '\n')
+sys.exit(0 if gate else 1)
