@@ -318,14 +318,87 @@ template <int COMP, typename T> __device__ __forceinline__ T& comp(C2<T>& c) {
     if constexpr (COMP == 0) return c.re; else return c.im;
 }
 
-template <int N, int E, int P, int OSZ = 8, bool PK = false> struct PassInfo;
+template <int N, int E, int P, int OSZ = 8, bool PK = false, bool LN = false> struct PassInfo;
+typedef __attribute__((address_space(3))) void lds_void_t;
+
+// Lane-addressed exchange images (nw_shape.h, lane_image): on in the translation units that
+// define NW_LANE_IMAGE_TU (nw_fused.hip), for the kernels of shape kLaneImageShape that store or
+// sum their outputs; the forward R2C kernel (kOutXHalf) keeps the padded images, as do the row
+// pass of nw_large.hip and the chirp-z kernels (neither was measured with this layout).
+#ifdef NW_LANE_IMAGE_TU
+constexpr bool kLaneImageTU = true;
+#else
+constexpr bool kLaneImageTU = false;
+#endif
+template <typename T, int N, int E, int OUT>
+constexpr bool kLaneImage = kLaneImageTU && kLaneImageShape<T, N, E> && OUT != kOutXHalf;
+
+// 16 ds_write_addtid_b32 of one wave in a row: lane l stores d[k] at byte m0 + OFF0 + k * STEP
+// + 4 l of the LDS.  M0 is written in the statement that reads it (the compiler does not keep it
+// across statements) and is followed by one wait state before the first store.  The compiler
+// does not count LDS operations issued from asm: WAIT ends the statement with lgkmcnt(0).
+// EXEC must be all ones (whole waves: every lane's dword belongs to the image).
+template <int OFF0, int STEP, bool WAIT>
+__device__ __forceinline__ void addtid_store16(uint32_t m0, const float* d) {
+    static_assert(OFF0 >= 0 && OFF0 + 15 * STEP < 65536, "16-bit offset field");
+    asm volatile(
+        "s_mov_b32 m0, %16\n\ts_nop 0\n\t"
+        "ds_write_addtid_b32 %0 offset:%17+0*%18\n\t"
+        "ds_write_addtid_b32 %1 offset:%17+1*%18\n\t"
+        "ds_write_addtid_b32 %2 offset:%17+2*%18\n\t"
+        "ds_write_addtid_b32 %3 offset:%17+3*%18\n\t"
+        "ds_write_addtid_b32 %4 offset:%17+4*%18\n\t"
+        "ds_write_addtid_b32 %5 offset:%17+5*%18\n\t"
+        "ds_write_addtid_b32 %6 offset:%17+6*%18\n\t"
+        "ds_write_addtid_b32 %7 offset:%17+7*%18\n\t"
+        "ds_write_addtid_b32 %8 offset:%17+8*%18\n\t"
+        "ds_write_addtid_b32 %9 offset:%17+9*%18\n\t"
+        "ds_write_addtid_b32 %10 offset:%17+10*%18\n\t"
+        "ds_write_addtid_b32 %11 offset:%17+11*%18\n\t"
+        "ds_write_addtid_b32 %12 offset:%17+12*%18\n\t"
+        "ds_write_addtid_b32 %13 offset:%17+13*%18\n\t"
+        "ds_write_addtid_b32 %14 offset:%17+14*%18\n\t"
+        "ds_write_addtid_b32 %15 offset:%17+15*%18"
+        :: "v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]), "v"(d[4]), "v"(d[5]), "v"(d[6]), "v"(d[7]),
+           "v"(d[8]), "v"(d[9]), "v"(d[10]), "v"(d[11]), "v"(d[12]), "v"(d[13]), "v"(d[14]), "v"(d[15]),
+           "s"(m0), "i"(OFF0), "i"(STEP)
+        : "memory", "m0");
+    if constexpr (WAIT) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// one component of the pass-P outputs -> the lane-addressed image feeding pass P + 1
+template <typename T, int N, int E, int P, int COMP>
+__device__ __forceinline__ void lane_write(C2<T>* v, T* lds, int t) {
+    namespace L = lane_image;
+    static_assert(kLaneImageShape<T, N, E> && (P == 0 || P == 1), "the fp32 n = 16384 exchanges");
+    static_assert(Geometry<N, E>::T % 64 == 0 && Geometry<N, E>::T == L::kT && L::kRebias == 16,
+                  "whole waves (EXEC all ones), 16 stores per M0");
+    static_assert(L::kElems <= kImgElems<T, N, E>, "the padded images' region holds these");
+    NW_DCHECK_H(__builtin_amdgcn_read_exec() == ~0ull);
+    const uint32_t img = (uint32_t)(uintptr_t)(lds_void_t*)lds;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    float d[E];
+    // d[k]: the value of output k (pass 0: slot 32 t + k; pass 1: butterfly t's output i' = k)
+#pragma unroll
+    for (int k = 0; k < E; ++k) d[k] = comp<COMP>(v[bitrev<E>(k)]);
+    if constexpr (P == 0) {
+        addtid_store16<L::off_01(0), L::off_01(1) - L::off_01(0), false>(img + L::m0_01(wave), d);
+        addtid_store16<L::off_01(16), L::off_01(1) - L::off_01(0), true>(img + L::m0_01(wave), d + 16);
+    } else {
+        static_assert(PassInfo<N, E, P, 16>::R == E && PassInfo<N, E, P, 16>::Q == 1, "one radix-E butterfly per thread");
+        addtid_store16<L::off_12(0), L::off_12(1) - L::off_12(0), false>(img + L::m0_12(wave, 0), d);
+        addtid_store16<L::off_12(16), L::off_12(17) - L::off_12(16), true>(img + L::m0_12(wave, 16), d + 16);
+    }
+}
 
 // ---- one component of the pass-P outputs -> LDS (P = 0: slots t*E + s, as pairs)
-template <typename T, int N, int E, int P, int COMP>
+template <typename T, int N, int E, int P, int COMP, bool LN = false>
 __device__ __forceinline__ void lds_write(C2<T>* v, T* lds, int t) {
     using G = Geometry<N, E>;
     constexpr int PG = kPadX<T, N, E, P + 1>;
-    if constexpr (P == 0) {
+    if constexpr (LN) {
+        lane_write<T, N, E, P, COMP>(v, lds, t);
+    } else if constexpr (P == 0) {
         NW_DCHECK_H(lds_idx_p<PG>(t * E + E - 1) < kImgElems<T, N, E>);
         Pair<T>* dst = reinterpret_cast<Pair<T>*>(lds + lds_idx_p<PG>(t * E));
 #pragma unroll
@@ -351,7 +424,7 @@ __device__ __forceinline__ void lds_write(C2<T>* v, T* lds, int t) {
 // in the LAST pass, where j = Q*t + q so a thread's outputs come in adjacent pairs.
 // OSZ: bytes of one output value (pairing is only worth it for outputs <= 8 B: a pair of
 // 16-B complex128 outputs is two 16-B stores per lane, each touching every other 16 B)
-template <int N, int E, int P, int OSZ, bool PK> struct PassInfo {
+template <int N, int E, int P, int OSZ, bool PK, bool LN> struct PassInfo {
     using G = Geometry<N, E>;
     static constexpr int R = G::radix(P);
     static constexpr int NS = G::ns(P);
@@ -371,7 +444,9 @@ template <int N, int E, int P, int OSZ, bool PK> struct PassInfo {
     // 16-31 of each group take the pair block 16 blocks further (512 slots: 16 * 34 =
     // 544 = 32 mod 64 dwords), so a group covers the 64 banks once.  Stores stay whole:
     // each store instruction writes two 512-B runs.
-    static constexpr bool SWZ = PAIRED && G::T == 512 && kPadG<E> == 32;
+    // (LN, the lane-addressed image: its row stride does this, a lane owns outputs 2t, 2t + 1
+    // and a store instruction writes one 1-KiB run)
+    static constexpr bool SWZ = PAIRED && G::T == 512 && kPadG<E> == 32 && !LN;
     // the signal-pair kernel's pass 1 reads the per-16-padded image (kPad16)
     static constexpr bool REMAP = PK && NW_PAIR_PAD16 && P == 1 && !LAST && E == 16 && G::T == 256 && Q == 1;
     __device__ static __forceinline__ int bfly(int t, int q) {
@@ -426,12 +501,33 @@ template <typename T, int N, int E> struct Tab1 {
     }
 };
 
-template <typename T, int N, int E, int P, int COMP, int OSZ>
+template <typename T, int N, int E, int P, int COMP, int OSZ, bool LN = false>
 __device__ __forceinline__ void lds_read(C2<T>* v, const T* lds, int t) {
-    using I = PassInfo<N, E, P, OSZ, kIsPair<T>>;
+    using I = PassInfo<N, E, P, OSZ, kIsPair<T>, LN>;
     constexpr int R = I::R, Q = I::Q;
     constexpr int PG = kPadX<T, N, E, P>;
-    if constexpr (I::PAIRED) {
+    if constexpr (LN) {
+        namespace L = lane_image;
+        if constexpr (P == 1) {
+            static_assert(Q == 1 && R == E && !I::PAIRED, "pass 1: butterfly t, slots t + 512 r");
+            const T* src = lds + L::rbase_01(I::bfly(t, 0));
+#pragma unroll
+            for (int r = 0; r < R; ++r) comp<COMP>(v[r]) = src[L::roff_01(r)];
+        } else {
+            static_assert(P == 2 && Q == 2 && I::PAIRED && I::STRIDE == 1024, "pass 2: pairs 2t, 2t + 1, slots j2 + 1024 r");
+            const T* src = lds + L::rbase_12(I::bfly(t, 0));
+            // (the compiler merges these 16 reads, 128 B apart, into 8 ds_read2_b64.  Issued as 16
+            // ds_read_b64 from one asm statement C4 ran 3.142 against 3.166 ms per launch, but the
+            // |y| and |y|^2 outputs were then no longer the parent's bit for bit: not kept,
+            // profiles/r13_lane_image_ab.txt)
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const Pair<T> pr = *reinterpret_cast<const Pair<T>*>(src + L::roff_12(r));
+                comp<COMP>(v[r]) = pr.a;
+                comp<COMP>(v[R + r]) = pr.b;
+            }
+        }
+    } else if constexpr (I::PAIRED) {
         NW_DCHECK_H(lds_idx_p<PG>(I::bfly(t, 0)) + (Q - 1) + lds_off_p<PG>((R - 1) * I::STRIDE) < kImgElems<T, N, E>);
         const T* src = lds + lds_idx_p<PG>(I::bfly(t, 0));
 #pragma unroll
@@ -467,7 +563,6 @@ __device__ __forceinline__ void lds_barrier() {
 // a wave at (wave-uniform base) + 16*l.  X[N/2] (the real Nyquist bin) travels by a
 // scalar load.  The DMA is issued before the stores, so the next pass 0 waits for
 // it with vmcnt(#stores issued after it), not for the stores.
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void gbl_void_t;
 
 // LDS-DMA of X[0 .. N/2) (the R2C half spectrum without its Nyquist bin) into LDS at dst:
@@ -563,7 +658,7 @@ template <typename F> __device__ __forceinline__ void xpose2(C2<F>& a, C2<F>& b,
 template <typename T, int N, int E, int OUT, int SP = kStoreGlobal>
 struct LastStores {
     using O = typename OutT<OUT, T>::type;
-    using I = PassInfo<N, E, Geometry<N, E>::npass() - 1, (int)sizeof(O)>;
+    using I = PassInfo<N, E, Geometry<N, E>::npass() - 1, (int)sizeof(O), false, kLaneImage<T, N, E, OUT>>;
     static constexpr int R = I::R, Q = I::Q;
     static constexpr int STEP = I::PAIRED ? 2 : 1;
     static constexpr int PACK_W = (int)(16 / sizeof(O));
@@ -692,7 +787,8 @@ __device__ __forceinline__ void passes_from(C2<T>* v, T* lds, int t, const C2<Sc
     using S = Sc<T>;
     constexpr bool PAIRSIG = !std::is_same<T, S>::value;
     constexpr int OSZ = (int)sizeof(typename OutT<OUT, S>::type);
-    using I = PassInfo<N, E, P, OSZ, kIsPair<T>>;
+    constexpr bool LN = kLaneImage<T, N, E, OUT>;
+    using I = PassInfo<N, E, P, OSZ, kIsPair<T>, LN>;
     if constexpr (P < Geometry<N, E>::npass()) {
         constexpr int R = I::R, Q = I::Q, LR = ilog2<R>();
         constexpr bool TABLED = P == 1 && Tab1<T, N, E>::ON;
@@ -714,13 +810,13 @@ __device__ __forceinline__ void passes_from(C2<T>* v, T* lds, int t, const C2<Sc
 #endif
 #ifndef NW_ABL_NOEXCH
         lds_barrier();                         // earlier readers of the image are done
-        lds_write<T, N, E, P - 1, 0>(v, lds, t);
+        lds_write<T, N, E, P - 1, 0, LN>(v, lds, t);
         lds_barrier();
-        lds_read<T, N, E, P, 0, OSZ>(v, lds, t);
+        lds_read<T, N, E, P, 0, OSZ, LN>(v, lds, t);
         lds_barrier();
-        lds_write<T, N, E, P - 1, 1>(v, lds, t);
+        lds_write<T, N, E, P - 1, 1, LN>(v, lds, t);
         lds_barrier();
-        lds_read<T, N, E, P, 1, OSZ>(v, lds, t);
+        lds_read<T, N, E, P, 1, OSZ, LN>(v, lds, t);
 #else   // ablation (diagnostic builds only): no exchange, the registers stay live
 #pragma unroll
         for (int i = 0; i < E; ++i) asm volatile("" : "+v"(v[i].re), "+v"(v[i].im));

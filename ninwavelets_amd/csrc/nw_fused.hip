@@ -23,6 +23,8 @@
 
 // the fp64 n = 16384 pass-1 twiddle table (Tab1, nw_fft_dev.h) is on in this file's kernels
 #define NW_TAB1_F64_16384 1
+// ... and the lane-addressed exchange images of the fp32 n = 16384 kernels (nw_shape.h, lane_image)
+#define NW_LANE_IMAGE_TU 1
 #include "nw_fft_dev.h"
 
 namespace nw {
@@ -267,7 +269,7 @@ __global__ __launch_bounds__(N / E, (kWpsOf<T, E, OUT>)) void nw_fused_kernel(WD
     }
     if constexpr (PSUM) {
         // the block's partial: row (group sg, scale fi) of the (groups, F, N) partial buffer
-        using IL = PassInfo<N, E, G::npass() - 1, (int)sizeof(T)>;
+        using IL = PassInfo<N, E, G::npass() - 1, (int)sizeof(T), false, kLaneImage<T, N, E, OUT>>;
         double* prow = reinterpret_cast<double*>(out) + ((int64_t)sg * d.nfreq + fi) * (int64_t)N * NACC;
 #pragma unroll
         for (int q = 0; q < IL::Q; ++q)

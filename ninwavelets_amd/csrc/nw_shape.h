@@ -287,6 +287,55 @@ constexpr bool pair_partials_supported(int64_t n, int dtype, int kind, int out_k
     return out_kind == NW_OUT_CROSS_SUM ? xs : out_kind == NW_OUT_PLV_SUM ? ps : false;
 }
 
+// ---- lane-addressed exchange images (fp32, n = 16384, E = 32) ---------------------------------
+
+// The two LDS exchanges of the fp32 n = 16384 one-pass kernels (512 threads, passes of radix
+// 32, 32, 16) laid out so that every wave store is 64 consecutive dwords from a wave-uniform
+// base: ds_write_addtid_b32 (address M0 + offset + 4 * lane, no address VGPR, 2 LDS cycles per
+// dword and wave against 6-13 for the 8- and 16-byte stores of the padded images).  Slot indices
+// i are those of the padded images (nw_fft_dev.h lds_write / lds_read): only the address of a
+// slot changes, not which value it holds.
+//   0 -> 1: slot i = 32 t + p (thread t's output p)            -> dword p * S1 + t
+//           read by butterfly u, element r as slot u + 512 r    =  (u % 32) * S1 + u / 32 + 16 r
+//   1 -> 2: slot i = (j / 32) * 1024 + j % 32 + 32 i' (butterfly j's output i')
+//                                                               -> dword i' * S2 + j
+//           read by butterfly j2, element r as slot j2 + 1024 r =  (j2 / 32) * S2 + j2 % 32 + 32 r
+// S1 = 513: a 32-lane ds_read_b32 group (u = 32 g + l) hits bank l + g + const, each once.
+// S2 = 544 = 32 mod 64: lanes 0-15 of a ds_read_b64 group (pairs j2 = 2t, 2t + 1) cover dwords
+// 0-31 of one row and lanes 16-31 those of the next, 32 banks on: the 64 banks once, without
+// the lane remap the padded image needs there (PassInfo::SWZ).
+// -DNW_LANE_IMAGE=0: the padded images everywhere (diagnostic A/B).
+#ifndef NW_LANE_IMAGE
+#define NW_LANE_IMAGE 1
+#endif
+template <typename T, int N, int E>
+constexpr bool kLaneImageShape = NW_LANE_IMAGE && std::is_same<T, float>::value && N == 16384 && E == 32;
+namespace lane_image {
+constexpr int kN = 16384, kE = 32, kT = kN / kE;   // threads = butterflies of pass 1
+constexpr int kS1 = 513, kS2 = 544;                // row strides in dwords
+constexpr int kElems = kE * kS2;                   // dwords of the image region (both images fit)
+constexpr int kBytes = kElems * 4;
+constexpr int kTab1Bytes = kE * (kE - 1) * 8;      // the pass-1 twiddle table behind the image
+constexpr int kCuLdsBytes = 160 * 1024;
+constexpr int kRebias = 16;                        // 1 -> 2: outputs i' >= this take a second M0
+// slot -> dword address
+NW_SHAPE_HD constexpr int addr01(int i) { return (i % kE) * kS1 + i / kE; }
+NW_SHAPE_HD constexpr int addr12(int i) { return ((i % 1024) / 32) * kS2 + (i / 1024) * 32 + i % 32; }
+// writers: M0 (bytes from the image's start) of a wave, and the instruction's offset field
+NW_SHAPE_HD constexpr int m0_01(int wave) { return 256 * wave; }
+NW_SHAPE_HD constexpr int off_01(int p) { return 4 * p * kS1; }
+NW_SHAPE_HD constexpr int m0_12(int wave, int ip) { return 256 * wave + (ip >= kRebias ? 4 * kRebias * kS2 : 0); }
+NW_SHAPE_HD constexpr int off_12(int ip) { return 4 * (ip % kRebias) * kS2; }
+// readers: one base per lane (dwords) plus a compile-time offset per element r
+NW_SHAPE_HD constexpr int rbase_01(int u) { return (u % kE) * kS1 + u / kE; }
+NW_SHAPE_HD constexpr int roff_01(int r) { return (kT / kE) * r; }
+NW_SHAPE_HD constexpr int rbase_12(int j2) { return (j2 / 32) * kS2 + j2 % 32; }
+NW_SHAPE_HD constexpr int roff_12(int r) { return 32 * r; }
+static_assert(addr01(kN - 1) < kElems && addr12(kN - 1) < kElems, "both images inside the region");
+static_assert(off_01(kE - 1) < 65536 && off_12(kE - 1) < 65536, "16-bit offset field");
+static_assert(2 * (kBytes + kTab1Bytes) <= kCuLdsBytes, "two blocks per CU");
+}  // namespace lane_image
+
 // ---- multi-channel connectivity (nw_conn.hip) -------------------------------------------------
 
 // nw_conn_accumulate_kernel: a block owns one scale, kConnTileN consecutive output samples (lane =
