@@ -100,6 +100,13 @@ extern "C" {
                                 S_ab = sum_e y_a,e conj(y_b,e), P_aa = sum_e |y_a,e|^2 */
 #define NW_OUT_PLV_SUM    8  /* complex128 (F, N): sum_e (y_a,e/|y_a,e|) conj(y_b,e/|y_b,e|);
                                 some |y| = 0 gives NaN there, as NW_OUT_ITC */
+#define NW_OUT_LAG_SUM    9  /* float64 (F, N, 4): the phase-lag sums {L0, L1, L2, L3} = sum_e of
+                                {m_e, |m_e|, m_e^2, sgn m_e} with m_e = Im y_a,e conj(y_b,e), formed
+                                as the imaginary term of NW_OUT_CROSS_SUM (L0 is Im S_ab of the
+                                per-signal-rows path bit for bit); sgn(+-0) = 0 and sgn(NaN) = NaN, so
+                                L3 is an exact integer and a NaN row makes all four NaN.  What PLI,
+                                dPLI, wPLI and their debiased forms need (nw_execute_pair,
+                                nw_execute_conn) */
 
 /* memory placement of x / out in nw_execute */
 #define NW_MEM_HOST   0
@@ -197,7 +204,8 @@ int nw_decim_supported(int64_t n, int dtype, int decim);
  * per-signal rows of each chunk are reduced (NW_REDUCE_ROWS).  1 for fp32, n = 1024 / 2048 /
  * 4096 and the analytic kinds (NW_MORSE, NW_MORLET, NW_SHANNON); plans with decim > 1 or repeated
  * rows keep the chunk path.  The same terms are added either way (regrouped fp64 additions; the
- * unit phasors of NW_OUT_PLV_SUM by rsqrt instead of hypot and divide, a few fp64 ulp). */
+ * unit phasors of NW_OUT_PLV_SUM by rsqrt instead of hypot and divide, a few fp64 ulp).
+ * 0 for NW_OUT_LAG_SUM at every size: its sums always come from the per-signal rows. */
 int nw_pair_partials_supported(int64_t n, int dtype, int kind, int out_kind);
 
 /* Create a plan for signals of n samples, up to max_batch signals per device
@@ -257,7 +265,8 @@ int nw_execute(nw_plan* plan, const void* x, int64_t nsig, void* out, int out_ki
 
 /* Cross-channel epoch reductions: the CWT rows y_a,e of xa[e] and y_b,e of xb[e] (both
  * (npairs, n) of the plan dtype) reduced over e = 0 .. npairs-1 into out, NW_OUT_CROSS_SUM
- * (float64 (F, n_out, 4)) or NW_OUT_PLV_SUM (complex128 (F, n_out)); every sum in fp64, in pair
+ * (float64 (F, n_out, 4)), NW_OUT_PLV_SUM (complex128 (F, n_out)) or NW_OUT_LAG_SUM (float64
+ * (F, n_out, 4), always NW_REDUCE_ROWS); every sum in fp64, in pair
  * order; (npairs, F, N) is never materialised.  The plan stages the inputs interleaved
  * a0, b0, a1, b1, ... into its own buffer, max_batch / 2 pairs per chunk, so max_batch must
  * be >= 2 (NW_E_INVALID).  mem as in nw_execute (host: synchronous; device: asynchronous on
@@ -278,6 +287,8 @@ int nw_conn_tiles(int32_t nchan, const int32_t* ia, const int32_t* ib, int64_t n
  * NW_OUT_CROSS_SUM: out_cross complex128 (npairs, F, n_out) = sum_e y_a conj(y_b),
  *                   out_power float64 (nchan, F, n_out) = sum_e |y_c|^2 (may be NULL).
  * NW_OUT_PLV_SUM:   out_cross complex128 (npairs, F, n_out) = sum_e unit phasor products;
+ *                   out_power must be NULL.
+ * NW_OUT_LAG_SUM:   out_cross float64 (npairs, F, n_out, 4) = the phase-lag sums {L0 .. L3};
  *                   out_power must be NULL.
  * Every sum in fp64 in epoch order, the terms those of nw_execute_pair's per-signal-rows path
  * (bit-identical to it for the same two channels, however the epochs are chunked).

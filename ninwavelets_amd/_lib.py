@@ -39,6 +39,7 @@ NW_NO_CHIRP = 0x400
 NW_OUT_CWT, NW_OUT_ABS, NW_OUT_POWER = 0, 1, 2
 NW_OUT_POWER_MEAN, NW_OUT_ITC, NW_OUT_POWER_SUM, NW_OUT_PHASE_SUM = 3, 4, 5, 6
 NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM = 7, 8          # nw_execute_pair only
+NW_OUT_LAG_SUM = 9                               # ... and nw_execute_conn: the phase-lag sums
 NW_REDUCE_NONE, NW_REDUCE_ROWS, NW_REDUCE_PARTIALS = 0, 1, 2   # nw_stats.reduce_path
 NW_REDUCE_CONN = 3                                              # ... of nw_execute_conn
 NW_MEM_HOST, NW_MEM_DEVICE = 0, 1

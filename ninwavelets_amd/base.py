@@ -26,8 +26,8 @@ import numpy as np
 from scipy.fftpack import fft, ifft
 
 from . import _lib as L
-from .engine import (CONN_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim, check_indices, execute_multi, finalize_conn,
-                     finalize_pair, np_dtype)
+from .engine import (CONN_OUTS, LAG_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim, check_indices, execute_multi,
+                     finalize_conn, finalize_lag, finalize_pair, np_dtype)
 from .engine import make_wavelets as _make_wavelets_dev
 
 # Device working-set budget per plan chunk (bytes); signals are streamed through it.
@@ -516,6 +516,76 @@ class WaveletBase:
             cross = np.ascontiguousarray(cross[..., ::decim])
             power = None if power is None else np.ascontiguousarray(power[..., ::decim])
         return finalize_conn(out, cross, power, ia, ib, nep)
+
+    def lag_batch(self, waves_a: np.ndarray, waves_b: np.ndarray, freqs=None, reuse: bool = True,
+                  out: str = 'wpli', decim: int = 1) -> np.ndarray:
+        """Phase-lag connectivity of the signal pairs (waves_a[e], waves_b[e]), (F, N'): cross_batch
+        for the measures that ignore zero-lag coupling (mne-connectivity's names).  With
+        m_e = Im y_a conj(y_b) of pair e, the device forms {L0, L1, L2, L3} = the sums over e of
+        m, |m|, m^2, sgn m in fp64 in pair order, and ``out`` is one of
+          lag_sum         float64 (F, N', 4), the sums themselves
+          pli             |L3| / E                  dpli            0.5 + 0.5 L3 / E
+          pli2_unbiased   (E pli^2 - 1) / (E - 1)   wpli            |L0| / L1
+          wpli2_debiased  (L0^2 - L2) / (L1^2 - L2)
+          ciplv, ppc      from cross_batch's plv_sum
+        (engine.finalize_lag; float64).  Argument checks, cache semantics, device choice and
+        ``decim`` as in cross_batch."""
+        decim = check_decim(decim)
+        if out not in LAG_OUTS:
+            raise ValueError(f"out must be one of {', '.join(LAG_OUTS)}; got {out!r}")
+        waves_a, waves_b = np.asarray(waves_a), np.asarray(waves_b)
+        if waves_a.ndim < 1 or waves_a.shape != waves_b.shape:
+            raise ValueError(f'waves_a and waves_b must have the same (..., N) shape; got {waves_a.shape} '
+                             f'and {waves_b.shape}')
+        n = waves_a.shape[-1]
+        npairs = int(np.prod(waves_a.shape[:-1])) if waves_a.ndim > 1 else 1
+        if out in ('pli2_unbiased', 'ppc') and npairs < 2:
+            raise ValueError(f'{out} needs at least 2 epochs, got {npairs}')
+        if (not reuse) or self._cache is None:
+            self._build_cache(freqs, n / self.sfreq)
+        on_device = self._device_decim(n, decim)
+        self._used = 1
+        try:
+            plan = self._plan(n, 2 * npairs, (self.devices or [self.device])[0],
+                              decim=decim if on_device else 1, min_batch=2)
+            sums = plan.execute_pair(waves_a.reshape(npairs, n), waves_b.reshape(npairs, n), out_kind=LAG_OUTS[out])
+        finally:
+            if len(self._plans) > 1:
+                self._evict_plans(keep=1)
+        if decim > 1 and not on_device:
+            sums = np.ascontiguousarray(sums[:, ::decim])
+        return finalize_lag(out, sums, npairs)
+
+    def lag_connectivity_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, out: str = 'wpli',
+                               indices=None, decim: int = 1) -> np.ndarray:
+        """lag_batch's measures for the channel pairs ``indices`` of ``waves`` (E, C, N) from ONE
+        transform per epoch and channel, (P, F, N') float64 (``lag_sum``: (P, F, N', 4)), as
+        connectivity_batch does for the cross sums: its argument checks, pair lists, cache
+        semantics, device choice and ``decim``."""
+        decim = check_decim(decim)
+        if out not in LAG_OUTS:
+            raise ValueError(f"out must be one of {', '.join(LAG_OUTS)}; got {out!r}")
+        waves = np.asarray(waves)
+        if waves.ndim != 3:
+            raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
+        nep, nchan, n = waves.shape
+        ia, ib = check_indices(indices, nchan)
+        if out in ('pli2_unbiased', 'ppc') and nep < 2:
+            raise ValueError(f'{out} needs at least 2 epochs, got {nep}')
+        if (not reuse) or self._cache is None:
+            self._build_cache(freqs, n / self.sfreq)
+        on_device = self._device_decim(n, decim)
+        self._used = 1
+        try:
+            plan = self._plan(n, nep * nchan, (self.devices or [self.device])[0],
+                              decim=decim if on_device else 1, min_batch=nchan)
+            sums = plan.execute_conn(waves, (ia, ib), out_kind=LAG_OUTS[out])
+        finally:
+            if len(self._plans) > 1:
+                self._evict_plans(keep=1)
+        if decim > 1 and not on_device:
+            sums = np.ascontiguousarray(sums[:, :, ::decim])
+        return finalize_lag(out, sums, nep)
 
     def plan_stats(self) -> list:
         """Per-plan device stage timings (nw_plan_stats)."""

@@ -59,12 +59,12 @@ __attribute__((format(printf, 2, 3))) void nw_logf(int level, const char* fmt, .
 
 const char* out_name(int k) {
     static const char* names[] = {"cwt", "abs", "power", "power_mean", "itc", "power_sum", "phase_sum",
-                                  "cross_sum", "plv_sum"};
+                                  "cross_sum", "plv_sum", "lag_sum"};
     if (k == 1001) return "power partials";
     if (k == 1002) return "phase partials";
     if (k == 1003) return "cross partials";
     if (k == 1004) return "plv partials";
-    return k >= 0 && k < 9 ? names[k] : "?";
+    return k >= 0 && k < 10 ? names[k] : "?";
 }
 const char* kernel_name(int64_t k) {
     static const char* names[] = {"none", "nw_fused_kernel", "nw_fused_pair_kernel", "nw_chirp_kernel",
@@ -879,6 +879,7 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
 int execute_pair(nw_plan* p, const nw::WDesc& d, const void* xa, const void* xb, int64_t npairs, void* out,
                  int out_kind, bool host) {
     const bool plv = out_kind == NW_OUT_PLV_SUM;
+    const int mode = nw::sum_mode(out_kind);   // NW_OUT_LAG_SUM: four sums per point, always from the rows
     const int64_t fn = (int64_t)p->nfreq * p->n_out();
     const size_t acc_bytes = (size_t)fn * (plv ? 2 : 4) * sizeof(double);
     NW_TRY(p->d_acc.ensure(acc_bytes));
@@ -926,7 +927,7 @@ int execute_pair(nw_plan* p, const nw::WDesc& d, const void* xa, const void* xb,
                                                          nw::fused_psum_groups(2 * c), p->stream)));
         else
             NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, true,
-                                   nw::launch_accumulate_pair(p->dtype, plv, scratch, acc, fn, c, p->stream)));
+                                   nw::launch_accumulate_pair(p->dtype, mode, scratch, acc, fn, c, p->stream)));
         p->stats.chunks++;
     }
     NW_HIP(hipMemcpyAsync(out, acc, acc_bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, p->stream));
@@ -946,9 +947,10 @@ int execute_pair(nw_plan* p, const nw::WDesc& d, const void* xa, const void* xb,
 // (built and uploaded once per call) share d_acc.
 int execute_conn(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ia,
                  const int32_t* ib, int64_t npairs, void* out_cross, void* out_power, int out_kind, bool host) {
-    const bool plv = out_kind == NW_OUT_PLV_SUM;
+    const int mode = nw::sum_mode(out_kind);
     const int64_t fn = (int64_t)p->nfreq * p->n_out();
-    const size_t cross_bytes = (size_t)npairs * fn * 2 * sizeof(double);
+    // 16 B per pair and point (a complex fp64), NW_OUT_LAG_SUM: 32 B (its four sums)
+    const size_t cross_bytes = (size_t)npairs * fn * (mode == nw::SUM_LAG ? 4 : 2) * sizeof(double);
     const size_t power_bytes = out_power ? (size_t)nchan * fn * sizeof(double) : 0;
     p->conn_tiles = nw::host::conn_tiles(ia, ib, npairs, nullptr);
     const size_t tile_bytes = p->conn_tiles.size() * sizeof(nw::ConnTile);
@@ -996,7 +998,7 @@ int execute_conn(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs,
         NW_TRY(run_chunk(p, d, xs, ec * nchan, scratch, NW_OUT_CWT, false));
         // chained: run_chunk ends with a stage
         NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, true,
-                               nw::launch_conn_accumulate(p->dtype, plv, scratch, cross, power, tiles,
+                               nw::launch_conn_accumulate(p->dtype, mode, scratch, cross, power, tiles,
                                                           (int)p->conn_tiles.size(), ec, nchan, p->nfreq, p->n_out(),
                                                           npairs, xcd, p->stream)));
         p->stats.chunks++;
@@ -1473,8 +1475,9 @@ int nw_pair_partials_supported(int64_t n, int dtype, int kind, int out_kind) {
 int nw_execute_pair(nw_plan* p, const void* xa, const void* xb, int64_t npairs, void* out, int out_kind, int mem) {
     if (!p || !out || ((!xa || !xb) && npairs > 0)) return fail(NW_E_INVALID, "nw_execute_pair: null argument");
     if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_pair: nw_plan_set_wavelet first");
-    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM)
-        return fail(NW_E_INVALID, "nw_execute_pair: out_kind must be NW_OUT_CROSS_SUM or NW_OUT_PLV_SUM");
+    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM && out_kind != NW_OUT_LAG_SUM)
+        return fail(NW_E_INVALID,
+                    "nw_execute_pair: out_kind must be NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM or NW_OUT_LAG_SUM");
     if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_pair: bad mem");
     if (npairs < 0) return fail(NW_E_INVALID, "nw_execute_pair: npairs < 0");
     if (p->max_batch < 2)
@@ -1504,10 +1507,13 @@ int nw_execute_conn(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, c
     if (!p || (!x && nepochs > 0) || (!out_cross && npairs > 0))
         return fail(NW_E_INVALID, "nw_execute_conn: null argument");
     if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_conn: nw_plan_set_wavelet first");
-    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM)
-        return fail(NW_E_INVALID, "nw_execute_conn: out_kind must be NW_OUT_CROSS_SUM or NW_OUT_PLV_SUM");
+    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM && out_kind != NW_OUT_LAG_SUM)
+        return fail(NW_E_INVALID,
+                    "nw_execute_conn: out_kind must be NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM or NW_OUT_LAG_SUM");
     if (out_kind == NW_OUT_PLV_SUM && out_power)
         return fail(NW_E_INVALID, "nw_execute_conn: NW_OUT_PLV_SUM forms no power sums: out_power must be NULL");
+    if (out_kind == NW_OUT_LAG_SUM && out_power)
+        return fail(NW_E_INVALID, "nw_execute_conn: NW_OUT_LAG_SUM forms no power sums: out_power must be NULL");
     if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_conn: bad mem");
     if (nepochs < 0) return fail(NW_E_INVALID, "nw_execute_conn: nepochs < 0");
     NW_TRY(check_pairs("nw_execute_conn", nchan, ia, ib, npairs));

@@ -4,6 +4,8 @@
 //   src   [((e * C + c) * F + f) * n_out + t]   complex T: the chunk's rows, epoch-major
 //   cross [(p * F + f) * n_out + t]             complex fp64: S_p (PLV: Phi_p), p = (ia[p], ib[p])
 //   power [(c * F + f) * n_out + t]             fp64: P_cc (not for PLV)
+//   SUM_LAG: cross [((p * F + f) * n_out + t) * 4 ..] fp64 {L0, L1, L2, L3} = the sums over the epochs
+//   of m, |m|, m^2, sgn m with m = Im y_a conj(y_b) (the imaginary term of S_p); no power
 //
 // Per pair and epoch the terms are k_accumulate_pair's (nw_kernels.hip), added in epoch order:
 // fp64 values, every product and every term rounded on its own (no fma into the sum), for PLV
@@ -18,7 +20,9 @@
 // not per epoch.  Per epoch the tile's channels are staged once in LDS as fp64 (PLV: as unit
 // phasors, so a value is normalised once, not once per pair it enters); the staging is double
 // buffered: the next epoch's global loads are issued before the current epoch is consumed and
-// written to the other buffer after it, one barrier per epoch.
+// written to the other buffer after it, one barrier per epoch.  SUM_LAG stages as the cross mode
+// does and keeps 16 pairs x 4 doubles a wave (128 accumulator registers, at a lower occupancy: no
+// second sweep of the epochs); a lane reads and writes its 32 B per pair as two 16-byte accesses.
 // nw_conn_power_kernel adds P_cc: one thread per (c, f, t).
 #include <algorithm>
 
@@ -41,11 +45,17 @@ __device__ __forceinline__ double add_nc(double a, double b) {
 constexpr int kConnThreads = kConnWaves * 64;
 constexpr int kConnStage = kConnCh / kConnWaves;   // channels a wave stages per epoch
 
-template <typename T, bool PLV>
+// a pair's accumulators: S_p (Phi_p), or the four phase-lag sums
+struct ConnAcc2 { double re, im; };
+struct ConnAcc4 { double l0, l1, l2, l3; };
+
+template <typename T, int MODE>
 __global__ __launch_bounds__(kConnThreads) void nw_conn_accumulate_kernel(
     const cplx<T>* __restrict__ src, double2* __restrict__ cross, const ConnTile* __restrict__ tiles, int ntiles,
     int64_t ec, int nchan, int nfreq, int64_t n_out, int64_t npairs, int64_t nunits, int xcd) {
     static_assert(kConnTileN == 64, "lane = sample of the tile");
+    constexpr bool PLV = MODE == SUM_PLV, LAG = MODE == SUM_LAG;
+    constexpr int NV = LAG ? 2 : 1;   // double2 values per pair and point in `cross`
     __shared__ double stage[2][kConnCh][2][kConnTileN];   // [buffer][slot][re, im][sample]: 32 KiB
 
     const ConnSlot sl = conn_slot((int64_t)blockIdx.x, ntiles, xcd != 0);
@@ -66,16 +76,24 @@ __global__ __launch_bounds__(kConnThreads) void nw_conn_accumulate_kernel(
 
     // (an array of structs: two plain double[16] are rewritten into <16 x double> vectors before the
     // loops unroll and then live in 32-register tuples, 1412 B of scratch; tools/regs.py)
-    struct Acc { double re, im; } acc[kConnPerWave];
+    // SUM_LAG: four doubles per pair, 128 accumulator registers a lane
+    std::conditional_t<LAG, ConnAcc4, ConnAcc2> acc[kConnPerWave];
 #pragma unroll
     for (int k = 0; k < kConnPerWave; ++k) {
         const int j = w + k * kConnWaves;
-        acc[k].re = acc[k].im = 0.0;
+        if constexpr (LAG) acc[k].l0 = acc[k].l1 = acc[k].l2 = acc[k].l3 = 0.0;
+        else acc[k].re = acc[k].im = 0.0;
         if (j < np && live) {
             const int64_t o = tile.out[j];
             NW_DCHECK(o >= 0 && o < npairs && o * fn + ft < npairs * fn);
-            const double2 v = cross[o * fn + ft];
-            acc[k].re = v.x, acc[k].im = v.y;
+            if constexpr (LAG) {
+                NW_DCHECK(NV * (o * fn + ft) + 1 < NV * npairs * fn);
+                const double2 u = cross[NV * (o * fn + ft)], v = cross[NV * (o * fn + ft) + 1];
+                acc[k].l0 = u.x, acc[k].l1 = u.y, acc[k].l2 = v.x, acc[k].l3 = v.y;
+            } else {
+                const double2 v = cross[o * fn + ft];
+                acc[k].re = v.x, acc[k].im = v.y;
+            }
         }
     }
 
@@ -125,8 +143,16 @@ __global__ __launch_bounds__(kConnThreads) void nw_conn_accumulate_kernel(
                 NW_DCHECK(a >= 0 && a < nch && b >= 0 && b < nch);
                 const double ar = stage[cur][a][0][lane], ai = stage[cur][a][1][lane];
                 const double br = stage[cur][b][0][lane], bi = stage[cur][b][1][lane];
-                acc[k].re += add_nc(mul_nc(ar, br), mul_nc(ai, bi));
-                acc[k].im += add_nc(mul_nc(ai, br), -mul_nc(ar, bi));
+                if constexpr (LAG) {
+                    const double m = add_nc(mul_nc(ai, br), -mul_nc(ar, bi));
+                    acc[k].l0 = add_nc(acc[k].l0, m);
+                    acc[k].l1 = add_nc(acc[k].l1, fabs(m));
+                    acc[k].l2 = add_nc(acc[k].l2, mul_nc(m, m));
+                    acc[k].l3 = add_nc(acc[k].l3, lag_sgn(m));
+                } else {
+                    acc[k].re += add_nc(mul_nc(ar, br), mul_nc(ai, bi));
+                    acc[k].im += add_nc(mul_nc(ai, br), -mul_nc(ar, bi));
+                }
             }
         }
         // the other buffer was last read before the previous barrier
@@ -140,7 +166,13 @@ __global__ __launch_bounds__(kConnThreads) void nw_conn_accumulate_kernel(
         if (j < np && live) {
             const int64_t o = tile.out[j];
             NW_DCHECK(o >= 0 && o < npairs && o * fn + ft < npairs * fn);
-            cross[o * fn + ft] = double2{acc[k].re, acc[k].im};
+            if constexpr (LAG) {
+                NW_DCHECK(NV * (o * fn + ft) + 1 < NV * npairs * fn);
+                cross[NV * (o * fn + ft)] = double2{acc[k].l0, acc[k].l1};
+                cross[NV * (o * fn + ft) + 1] = double2{acc[k].l2, acc[k].l3};
+            } else {
+                cross[o * fn + ft] = double2{acc[k].re, acc[k].im};
+            }
         }
     }
 }
@@ -166,7 +198,7 @@ __global__ __launch_bounds__(256) void nw_conn_power_kernel(const cplx<T>* __res
 
 }  // namespace
 
-hipError_t launch_conn_accumulate(int dtype, bool plv, const void* src, void* cross, double* power,
+hipError_t launch_conn_accumulate(int dtype, int mode, const void* src, void* cross, double* power,
                                   const ConnTile* tiles, int ntiles, int64_t ec, int nchan, int nfreq, int64_t n_out,
                                   int64_t npairs, bool xcd, hipStream_t s) {
     const int64_t nunits = conn_units(nfreq, n_out);
@@ -175,12 +207,12 @@ hipError_t launch_conn_accumulate(int dtype, bool plv, const void* src, void* cr
     for_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         if (blocks > 0)
-            for_bool(plv, [&](auto v) {
+            for_sum_mode(mode, [&](auto v) {
                 nw_launch(nw_conn_accumulate_kernel<T, decltype(v)::value>, dim3((unsigned)blocks), dim3(kConnThreads), 0, s,
                           (const cplx<T>*)src, (double2*)cross, tiles, ntiles, ec, nchan, nfreq, n_out, npairs, nunits,
                           xcd ? 1 : 0);
             });
-        if (power) {
+        if (power && mode != SUM_LAG) {   // the phase-lag sums carry no power
             const int64_t fn = (int64_t)nfreq * n_out;
             const int64_t pb = std::max<int64_t>(1, std::min<int64_t>(((int64_t)nchan * fn + 255) / 256, 256 * 32));
             nw_launch(nw_conn_power_kernel<T>, dim3((unsigned)pb), dim3(256), 0, s, (const cplx<T>*)src, power, ec, nchan, fn);

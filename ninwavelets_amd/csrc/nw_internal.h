@@ -222,15 +222,32 @@ hipError_t launch_expand_rows(const void* src, void* dst, int64_t nsig, int nu, 
 enum { ACC_POWER_REAL = 0, ACC_POWER_Y = 1, ACC_PHASE_Y = 2 };
 hipError_t launch_accumulate(int dtype, int src_kind, const void* src, double* acc, int64_t fn, int64_t c,
                              hipStream_t s);
+// what the pair / connectivity accumulators add per pair and epoch (k_accumulate_pair,
+// nw_conn_accumulate_kernel): the cross sums, the unit-phasor products, or the phase-lag sums
+enum { SUM_CROSS = 0, SUM_PLV = 1, SUM_LAG = 2 };
+inline int sum_mode(int out_kind) {
+    return out_kind == NW_OUT_PLV_SUM ? SUM_PLV : out_kind == NW_OUT_LAG_SUM ? SUM_LAG : SUM_CROSS;
+}
+// f(std::integral_constant<int, MODE>) for a launch's sum mode (SUM_CROSS for any other value)
+template <typename F>
+inline auto for_sum_mode(int mode, F f) {
+    if (mode == SUM_PLV) return f(std::integral_constant<int, SUM_PLV>{});
+    if (mode == SUM_LAG) return f(std::integral_constant<int, SUM_LAG>{});
+    return f(std::integral_constant<int, SUM_CROSS>{});
+}
+// sgn of the phase-lag sums: -1, 0 (for either zero) or 1, and NaN for NaN
+__device__ __forceinline__ double lag_sgn(double m) { return m > 0.0 ? 1.0 : m < 0.0 ? -1.0 : m == 0.0 ? 0.0 : m; }
 // pair reductions: src = the complex rows (2c, F, n_out) of c interleaved pairs (a0, b0, a1, ...),
-// acc += their cross sums (4 fp64 per point) or, plv, unit-phasor products (2 per point)
-hipError_t launch_accumulate_pair(int dtype, bool plv, const void* src, double* acc, int64_t fn, int64_t c,
+// acc += their cross sums (4 fp64 per point), SUM_PLV: unit-phasor products (2 per point),
+// SUM_LAG: phase-lag sums (4 per point)
+hipError_t launch_accumulate_pair(int dtype, int mode, const void* src, double* acc, int64_t fn, int64_t c,
                                   hipStream_t s);
 // connectivity (nw_conn.hip): src = the complex rows (ec, nchan, F, n_out) of ec epochs; cross
 // (npairs, F, n_out) complex fp64 += per pair tile and epoch, in epoch order, k_accumulate_pair's
-// terms (plv: of the unit phasors); power (nchan, F, n_out) fp64 += |y|^2 (null: not formed).
+// terms (SUM_PLV: of the unit phasors; SUM_LAG: (npairs, F, n_out, 4) fp64, the phase-lag sums);
+// power (nchan, F, n_out) fp64 += |y|^2 (null, and always for SUM_LAG: not formed).
 // tiles: device array of ntiles ConnTile (host::conn_tiles).  xcd: the block order (conn_slot).
-hipError_t launch_conn_accumulate(int dtype, bool plv, const void* src, void* cross, double* power,
+hipError_t launch_conn_accumulate(int dtype, int mode, const void* src, void* cross, double* power,
                                   const ConnTile* tiles, int ntiles, int64_t ec, int nchan, int nfreq, int64_t n_out,
                                   int64_t npairs, bool xcd, hipStream_t s);
 hipError_t launch_finalize(int dtype, bool itc, const double* acc, void* out, int64_t fn, int64_t nsig,

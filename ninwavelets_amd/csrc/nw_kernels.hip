@@ -196,15 +196,18 @@ __device__ __forceinline__ double add_nocontract(double a, double b) {
 // Cross-channel pair reductions (nw_execute_pair).  src holds the chunk's complex rows
 // (2c, F, n_out) with the two channels of pair s interleaved: y_a = row 2s, y_b = row 2s + 1.
 // One thread per (f, k) walks the c pairs in order and adds to the fp64 accumulator
-//   PLV = false: acc[4i ..] += {Re, Im of y_a conj(y_b), |y_a|^2, |y_b|^2}
-//   PLV = true : acc[2i ..] += (y_a / |y_a|) conj(y_b / |y_b|), the unit phasors formed as
-//                k_accumulate's (hypot and divide in fp64; |y| = 0 gives 0/0 = NaN)
+//   SUM_CROSS: acc[4i ..] += {Re, Im of y_a conj(y_b), |y_a|^2, |y_b|^2}
+//   SUM_PLV  : acc[2i ..] += (y_a / |y_a|) conj(y_b / |y_b|), the unit phasors formed as
+//              k_accumulate's (hypot and divide in fp64; |y| = 0 gives 0/0 = NaN)
+//   SUM_LAG  : acc[4i ..] += {m, |m|, m^2, sgn m} with m = Im y_a conj(y_b), the imaginary term of
+//              SUM_CROSS (sgn of either zero is 0, of NaN NaN: lag_sgn)
 // Every term is rounded on its own before it is added (no fma into the sum), so another
 // grouping of the pairs into chunks -- or into block partials -- adds the same values.
 // ---------------------------------------------------------------------------
-template <typename T, bool PLV>
+template <typename T, int MODE>
 __global__ __launch_bounds__(256) void k_accumulate_pair(const cplx<T>* __restrict__ src, double* __restrict__ acc,
                                                          int64_t fn, int64_t c) {
+    constexpr bool PLV = MODE == SUM_PLV;
     constexpr int NC = PLV ? 2 : 4;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < fn; i += stride) {
@@ -221,11 +224,19 @@ __global__ __launch_bounds__(256) void k_accumulate_pair(const cplx<T>* __restri
                 const double ma = hypot(ar, ai), mb = hypot(br, bi);
                 ar /= ma, ai /= ma, br /= mb, bi /= mb;
             }
-            s[0] += add_nocontract(mul_nocontract(ar, br), mul_nocontract(ai, bi));
-            s[1] += add_nocontract(mul_nocontract(ai, br), -mul_nocontract(ar, bi));
-            if constexpr (!PLV) {
-                s[2] += add_nocontract(mul_nocontract(ar, ar), mul_nocontract(ai, ai));
-                s[3] += add_nocontract(mul_nocontract(br, br), mul_nocontract(bi, bi));
+            if constexpr (MODE == SUM_LAG) {
+                const double m = add_nocontract(mul_nocontract(ai, br), -mul_nocontract(ar, bi));
+                s[0] = add_nocontract(s[0], m);
+                s[1] = add_nocontract(s[1], fabs(m));
+                s[2] = add_nocontract(s[2], mul_nocontract(m, m));
+                s[3] = add_nocontract(s[3], lag_sgn(m));
+            } else {
+                s[0] += add_nocontract(mul_nocontract(ar, br), mul_nocontract(ai, bi));
+                s[1] += add_nocontract(mul_nocontract(ai, br), -mul_nocontract(ar, bi));
+                if constexpr (!PLV) {
+                    s[2] += add_nocontract(mul_nocontract(ar, ar), mul_nocontract(ai, ai));
+                    s[3] += add_nocontract(mul_nocontract(br, br), mul_nocontract(bi, bi));
+                }
             }
         }
 #pragma unroll
@@ -233,12 +244,12 @@ __global__ __launch_bounds__(256) void k_accumulate_pair(const cplx<T>* __restri
     }
 }
 
-hipError_t launch_accumulate_pair(int dtype, bool plv, const void* src, double* acc, int64_t fn, int64_t c,
+hipError_t launch_accumulate_pair(int dtype, int mode, const void* src, double* acc, int64_t fn, int64_t c,
                                   hipStream_t s) {
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((fn + 255) / 256, 256 * 32));
     for_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        for_bool(plv, [&](auto v) {
+        for_sum_mode(mode, [&](auto v) {
             nw_launch(k_accumulate_pair<T, decltype(v)::value>, blocks, 256, 0, s, (const cplx<T>*)src, acc, fn, c);
         });
     });

@@ -32,6 +32,12 @@ PAIR_OUTS = {'cross_sum': 'cross_sum', 'plv_sum': 'plv_sum', 'csd': 'cross_sum',
 CONN_KINDS = {'cross_sum': L.NW_OUT_CROSS_SUM, 'plv_sum': L.NW_OUT_PLV_SUM}
 CONN_OUTS = {'cross_sum': 'cross_sum', 'plv_sum': 'plv_sum', 'csd': 'cross_sum', 'coherency': 'cross_sum',
              'coherence': 'cross_sum', 'imcoh': 'cross_sum', 'plv': 'plv_sum'}
+# phase-lag connectivity (Plan.execute_pair / execute_conn with out_kind='lag_sum'): float64
+# (..., 4) = {L0, L1, L2, L3}, the epoch sums of m, |m|, m^2, sgn m with m = Im y_a conj(y_b); and
+# what finalize_lag forms, name -> the sums it needs (ciplv and ppc come from the unit-phasor sums)
+LAG_KINDS = {'lag_sum': L.NW_OUT_LAG_SUM}
+LAG_OUTS = {'lag_sum': 'lag_sum', 'pli': 'lag_sum', 'pli2_unbiased': 'lag_sum', 'dpli': 'lag_sum',
+            'wpli': 'lag_sum', 'wpli2_debiased': 'lag_sum', 'ciplv': 'plv_sum', 'ppc': 'plv_sum'}
 KINDS = {'morse': L.NW_MORSE, 'morlet': L.NW_MORLET, 'shannon': L.NW_SHANNON, 'table': L.NW_TABLE,
          # WaveletMode.Normal tables built on the device (base.py:249-256)
          'mexican_hat': L.NW_MEXICAN_HAT, 'haar': L.NW_HAAR}
@@ -96,6 +102,49 @@ def finalize_pair(kind: str, sums: np.ndarray, npairs: int) -> np.ndarray:
     if kind in ('csd', 'coherency'):
         return ratio
     return np.abs(ratio) if kind == 'coherence' else np.ascontiguousarray(ratio.imag)
+
+
+def finalize_lag(kind: str, sums: np.ndarray, nepochs: int) -> np.ndarray:
+    """The phase-lag measure ``kind`` (mne-connectivity's spectral_connectivity_epochs names) from
+    the fp64 sums over E = ``nepochs`` epochs.  From ``lag_sum`` (..., 4) = {L0, L1, L2, L3}, the
+    sums of m, |m|, m^2, sgn m with m = Im y_a conj(y_b):
+      pli             |L3| / E
+      dpli            0.5 + 0.5 L3 / E        (the mean Heaviside step of m, H(0) = 1/2)
+      pli2_unbiased   (E pli^2 - 1) / (E - 1)
+      wpli            |L0| / L1                        (0 where L1 = 0)
+      wpli2_debiased  (L0^2 - L2) / (L1^2 - L2)        (0 where the denominator is 0)
+    from a complex ``plv_sum`` Phi = sum_e (y_a / |y_a|) conj(y_b / |y_b|):
+      ciplv           i / sqrt(1 - r^2), r = clip(Re Phi / E, -1, 1), i = |Im Phi| / E  (i where |r| = 1)
+      ppc             (|Phi|^2 - E) / (E (E - 1))
+    ``lag_sum`` returns the sums themselves.  Plain numpy, float64, any leading shape;
+    pli2_unbiased and ppc need E >= 2 (ValueError)."""
+    if kind not in LAG_OUTS:
+        raise ValueError(f"out must be one of {', '.join(LAG_OUTS)}; got {kind!r}")
+    if kind == 'lag_sum':
+        return sums
+    E = int(nepochs)
+    if kind in ('pli2_unbiased', 'ppc') and E < 2:
+        raise ValueError(f'{kind} needs at least 2 epochs, got {E}')
+    if LAG_OUTS[kind] == 'plv_sum':
+        phi = np.asarray(sums, dtype=np.complex128)
+        if kind == 'ppc':
+            return (phi.real * phi.real + phi.imag * phi.imag - E) / (E * (E - 1))
+        r, i = np.clip(phi.real / E, -1., 1.), np.abs(phi.imag) / E
+        den = np.sqrt(1. - r * r)
+        edge = den == 0
+        return np.where(edge, i, i / np.where(edge, 1., den))
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.ndim < 1 or sums.shape[-1] != 4:
+        raise ValueError(f'lag sums must be (..., 4), got shape {sums.shape}')
+    l0, l1, l2, l3 = (sums[..., j] for j in range(4))
+    if kind == 'dpli':
+        return 0.5 + 0.5 * l3 / E
+    if kind in ('pli', 'pli2_unbiased'):
+        pli = np.abs(l3) / E
+        return pli if kind == 'pli' else (E * pli * pli - 1.) / (E - 1)
+    num, den = (np.abs(l0), l1) if kind == 'wpli' else (l0 * l0 - l2, l1 * l1 - l2)
+    zero = den == 0
+    return np.where(zero, 0., num / np.where(zero, 1., den))
 
 
 def all_pairs(nchan: int):
@@ -457,10 +506,11 @@ class Plan:
         xb of equal shape (E, n), numpy arrays (host, synchronous) or device tensors
         (asynchronous on the plan stream; ``out`` required).  ``cross_sum`` -> float64
         (nfreq, n_out, 4) = {Re S_ab, Im S_ab, P_aa, P_bb}; ``plv_sum`` -> complex128
-        (nfreq, n_out); see finalize_pair.  The plan needs max_batch >= 2."""
-        if out_kind not in PAIR_KINDS:
-            raise ValueError(f"out_kind must be one of {', '.join(PAIR_KINDS)}; got {out_kind!r}")
-        kind = PAIR_KINDS[out_kind]
+        (nfreq, n_out); see finalize_pair.  ``lag_sum`` -> float64 (nfreq, n_out, 4) = the
+        phase-lag sums {L0, L1, L2, L3}; see finalize_lag.  The plan needs max_batch >= 2."""
+        if out_kind not in PAIR_KINDS and out_kind not in LAG_KINDS:
+            raise ValueError(f"out_kind must be one of {', '.join({**PAIR_KINDS, **LAG_KINDS})}; got {out_kind!r}")
+        kind = {**PAIR_KINDS, **LAG_KINDS}[out_kind]
         plv = out_kind == 'plv_sum'
         count = self.nfreq * self.n_out * (1 if plv else 4)
         if _is_device_tensor(xa) or _is_device_tensor(xb):
@@ -474,7 +524,7 @@ class Plan:
                 raise ValueError(f'device output must be a {"complex128" if plv else "float64"} tensor '
                                  f'on device {self.device}')
             if not out.is_contiguous() or out.numel() != count:
-                raise ValueError('device output must be contiguous, (nfreq, n_out, 4) for cross_sum / '
+                raise ValueError('device output must be contiguous, (nfreq, n_out, 4) for cross_sum and lag_sum / '
                                  '(nfreq, n_out) for plv_sum')
             if out.device.index != self.device:
                 raise ValueError(f'device buffers must live on device {self.device}')
@@ -507,11 +557,14 @@ class Plan:
         ``plv_sum`` -> complex128 (P, nfreq, n_out); see finalize_conn.  numpy arrays: synchronous,
         ``out`` optional.  Device tensors: asynchronous on the plan stream, ``out`` required:
         (cross, power) tensors for cross_sum (power may be None: not formed), the tensor for
-        plv_sum.  The plan needs max_batch >= C (a chunk holds max_batch // C epochs)."""
-        if out_kind not in CONN_KINDS:
-            raise ValueError(f"out_kind must be one of {', '.join(CONN_KINDS)}; got {out_kind!r}")
-        kind = CONN_KINDS[out_kind]
-        plv = out_kind == 'plv_sum'
+        plv_sum.  ``lag_sum`` -> float64 (P, nfreq, n_out, 4), the phase-lag sums of every pair (see
+        finalize_lag), one array or tensor as plv_sum.  The plan needs max_batch >= C (a chunk holds
+        max_batch // C epochs)."""
+        if out_kind not in CONN_KINDS and out_kind not in LAG_KINDS:
+            raise ValueError(f"out_kind must be one of {', '.join({**CONN_KINDS, **LAG_KINDS})}; got {out_kind!r}")
+        kind = {**CONN_KINDS, **LAG_KINDS}[out_kind]
+        lag = out_kind == 'lag_sum'
+        plv = out_kind == 'plv_sum' or lag          # one output, no power sums
         if getattr(x, 'ndim', 0) != 3:
             raise ValueError(f'x must be (epochs, channels, n), got shape {tuple(getattr(x, "shape", ()))}')
         nep, nchan = int(x.shape[0]), int(x.shape[1])
@@ -527,7 +580,8 @@ class Plan:
             if self._check_device_input(x) != nep * nchan:
                 raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
             cross, power = (out, None) if plv else out
-            for t, dt, count, name in ((cross, torch.complex128, npairs * fn, 'cross'),
+            for t, dt, count, name in ((cross, torch.float64 if lag else torch.complex128,
+                                        npairs * fn * (4 if lag else 1), 'cross'),
                                        (power, torch.float64, nchan * fn, 'power')):
                 if t is None and name == 'power':
                     continue
@@ -546,7 +600,8 @@ class Plan:
         if x.shape[-1] != self.n:
             raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
         cross, power = (out, None) if plv or out is None else out
-        shapes = (((npairs, self.nfreq, self.n_out), np.complex128), ((nchan, self.nfreq, self.n_out), np.float64))
+        shapes = (((npairs, self.nfreq, self.n_out, 4), np.float64) if lag else
+                  ((npairs, self.nfreq, self.n_out), np.complex128), ((nchan, self.nfreq, self.n_out), np.float64))
         if cross is None:
             cross = np.empty(*shapes[0])
         if power is None and not plv:

@@ -62,6 +62,42 @@ class EpochsWavelet:
         point where some epoch has |cwt| = 0 is NaN, as itc."""
         return self._cross(ch_a, ch_b, freqs, 'plv', decim)
 
+    # -- phase-lag connectivity between two channels (WaveletBase.lag_batch): measures that do not
+    #    respond to zero-lag coupling, mne-connectivity's names ----------------------------------
+    def _lag(self, ch_a: str, ch_b: str, freqs, out: str, decim: int) -> np.ndarray:
+        return self.wavelet.lag_batch(self._waves(ch_a), self._waves(ch_b), freqs, reuse=True, out=out, decim=decim)
+
+    def pli(self, ch_a: str, ch_b: str, freqs, decim: int = 1) -> np.ndarray:
+        """Phase-lag index |mean_e sgn Im(cwt_a conj(cwt_b))|, (F, N) float64."""
+        return self._lag(ch_a, ch_b, freqs, 'pli', decim)
+
+    def dpli(self, ch_a: str, ch_b: str, freqs, decim: int = 1) -> np.ndarray:
+        """Directed phase-lag index: the mean Heaviside step of Im(cwt_a conj(cwt_b)) (H(0) = 1/2),
+        (F, N) float64."""
+        return self._lag(ch_a, ch_b, freqs, 'dpli', decim)
+
+    def wpli(self, ch_a: str, ch_b: str, freqs, decim: int = 1) -> np.ndarray:
+        """Weighted phase-lag index |sum_e m_e| / sum_e |m_e| with m_e = Im(cwt_a conj(cwt_b)), (F, N)
+        float64; 0 where every m_e is 0."""
+        return self._lag(ch_a, ch_b, freqs, 'wpli', decim)
+
+    def wpli2_debiased(self, ch_a: str, ch_b: str, freqs, decim: int = 1) -> np.ndarray:
+        """Debiased squared wPLI ((sum m)^2 - sum m^2) / ((sum |m|)^2 - sum m^2), (F, N) float64."""
+        return self._lag(ch_a, ch_b, freqs, 'wpli2_debiased', decim)
+
+    def ciplv(self, ch_a: str, ch_b: str, freqs, decim: int = 1) -> np.ndarray:
+        """Corrected imaginary PLV |Im plv| / sqrt(1 - (Re plv)^2) of the mean unit-phasor product,
+        (F, N) float64; NaN where some |cwt| = 0, as plv."""
+        return self._lag(ch_a, ch_b, freqs, 'ciplv', decim)
+
+    def lag_connectivity(self, ch_names, freqs, method: str = 'wpli', indices=None, decim: int = 1):
+        """``method`` (lag_batch's outs: pli, pli2_unbiased, dpli, wpli, wpli2_debiased, ciplv, ppc,
+        lag_sum) for the channel pairs ``indices`` of ``ch_names``, (P, F, N), as connectivity."""
+        ch_names = list(ch_names)
+        idx = [self.epochs.ch_names.index(c) for c in ch_names]
+        waves = self.epochs.get_data()[:, idx, :]
+        return self.wavelet.lag_connectivity_batch(waves, freqs, reuse=True, out=method, indices=indices, decim=decim)
+
     # -- connectivity between many channels: one transform per epoch and channel, every pair's
     #    sums from it (WaveletBase.connectivity_batch; no reference counterpart) ---------------
     def connectivity(self, ch_names, freqs, method: str = 'coherence', indices=None, decim: int = 1):

@@ -11,7 +11,12 @@ B  nw_conn_accumulate_kernel alone (cross_sum without power sums: the epilogue s
    its algorithmic bytes -- the chunk's rows read once, C ec F n 8 B, plus the accumulators read and
    written, 2 P F n 16 B -- as a fraction of 8 TB/s, in both block orders (XCD-aware, conn_slot;
    NW_CONN_PLAIN_ORDER: plain).
-    [EC="2 8 32"] python tools/conn_rate.py [output file, default profiles/r12_conn_rate.txt] [A|B|AB]"""
+C  the phase-lag sums (out_kind lag_sum), no gate: at A's fp32 n = 4096 shapes one
+   execute_conn(lag_sum) against execute_conn(cross_sum) of the same plan and against the 28
+   execute_pair(lag_sum) calls; at B's shapes the kernel's lag mode per launch against its algorithmic
+   bytes, the chunk's rows read once plus 2 P F n 32 B of accumulators (recorded in
+   profiles/r14_lag_rate.txt).
+    [EC="2 8 32"] python tools/conn_rate.py [output file, default profiles/r12_conn_rate.txt] [A|B|AB|C]"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,6 +133,68 @@ def part_b(ec):
                 2 * P * F * n * 16 / 1e9, nbytes / ms[order] / 1e9, 100 * nbytes / (ms[order] * 1e-3) / HBM))
 
 
+def part_c_calls():
+    dt, n, E, C, F, batch = 'float32', 4096, 64, 8, 64, 128
+    ia, ib = all_pairs(C)
+    P = len(ia)
+    plan = nw.Plan(n, F, dt, max_batch=batch, timing=True)
+    plan.set_wavelet('morse', [17.5, 3.], np.arange(1., F + 1), L.trans_grid(n / 1000., 1000., False))
+    common = torch.randn((E, 1, n), device='cuda', dtype=torch.float32)
+    x = (0.6 * common + 0.8 * torch.randn((E, C, n), device='cuda', dtype=torch.float32)).contiguous()
+    chans = [x[:, c].contiguous() for c in range(C)]
+    oc = torch.empty((P, F, n), device='cuda', dtype=torch.complex128)
+    opw = torch.empty((C, F, n), device='cuda', dtype=torch.float64)
+    ol = torch.empty((P, F, n, 4), device='cuda', dtype=torch.float64)
+    pl = torch.empty((F, n, 4), device='cuda', dtype=torch.float64)
+
+    def once(arm):
+        if arm == 'lag_sum/conn':
+            plan.execute_conn(x, (ia, ib), out=ol, out_kind='lag_sum')
+        elif arm == 'cross_sum/conn':
+            plan.execute_conn(x, (ia, ib), out=(oc, opw), out_kind='cross_sum')
+        else:
+            for a, b in zip(ia, ib):
+                plan.execute_pair(chans[a], chans[b], out=pl, out_kind='lag_sum')
+
+    r = timed(plan, once, 5, ('lag_sum/conn', 'cross_sum/conn', 'lag_sum/pairs'))
+    once('lag_sum/pairs')
+    path = plan.stats()['reduce_path']
+    plan.close()
+    lag, cross, pairs = r['lag_sum/conn'], r['cross_sum/conn'], r['lag_sum/pairs']
+    say('C %s n=%d C=%d E=%d F=%d one execute_conn lag_sum: device %.3f ms (median %.3f) wall %.3f ms (median %.3f) | '
+        'cross_sum: device %.3f ms (median %.3f) wall %.3f ms (median %.3f) | lag / cross: device %.2fx wall %.2fx' % (
+            dt, n, C, E, F, lag[0], lag[1], lag[2], lag[3], cross[0], cross[1], cross[2], cross[3], lag[0] / cross[0],
+            lag[2] / cross[2]))
+    say('C %s n=%d C=%d E=%d F=%d one execute_conn lag_sum | %d execute_pair lag_sum (reduce_path %d): device %.3f ms '
+        '(median %.3f) wall %.3f ms (median %.3f) | pairs / conn: device %.2fx wall %.2fx' % (
+            dt, n, C, E, F, P, path, pairs[0], pairs[1], pairs[2], pairs[3], pairs[0] / lag[0], pairs[2] / lag[2]))
+
+
+def part_c_kernel(ec):
+    dt, n, F, C = 'float32', 4096, 64, 32
+    ia, ib = all_pairs(C)
+    P = len(ia)
+    E = 2 * ec                                                      # two launches per call
+    plan = nw.Plan(n, F, dt, max_batch=ec * C, timing=True)
+    plan.set_wavelet('morse', [17.5, 3.], np.arange(1., F + 1), L.trans_grid(n / 1000., 1000., False))
+    x = torch.randn((E, C, n), device='cuda', dtype=torch.float32)
+    ol = torch.empty((P, F, n, 4), device='cuda', dtype=torch.float64)
+    best = []
+    for rep in range(4):
+        plan.reset_stats()
+        plan.execute_conn(x, (ia, ib), out=ol, out_kind='lag_sum'); plan.sync()
+        st = plan.stats()
+        if rep:
+            best.append(st['ms_epilogue'] / st['chunks'])
+    plan.close()
+    ms = min(best)
+    rows, accs = C * ec * F * n * 8, 2 * P * F * n * 32
+    say('C fp32 n=%d F=%d C=%d P=%d (%d tiles) ec=%d: nw_conn_accumulate_kernel (lag) %.3f ms per launch, %.3f ms per '
+        'epoch; algorithmic %.3f GB (rows %.3f + accumulators %.3f) -> %.2f TB/s = %.1f %% of 8 TB/s' % (
+            n, F, C, P, L.conn_tiles(C, ia, ib)[1], ec, ms, ms / ec, (rows + accs) / 1e9, rows / 1e9, accs / 1e9,
+            (rows + accs) / ms / 1e9, 100 * (rows + accs) / (ms * 1e-3) / HBM))
+
+
 say('# tools/conn_rate.py on %s, %s' % (torch.cuda.get_device_name(0), os.environ.get('NINWAVE_LIB', 'libninwave.so')))
 gate = True
 if 'A' in parts:
@@ -137,6 +204,10 @@ if 'A' in parts:
 if 'B' in parts:
     for ec in [int(v) for v in os.environ.get('EC', '2 8 32').split()]:
         part_b(ec)
+if 'C' in parts:
+    part_c_calls()
+    for ec in [int(v) for v in os.environ.get('EC', '2 8 32').split()]:
+        part_c_kernel(ec)
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, 'w') as f:
     f.write('\n'.join(lines) + '\n')
