@@ -156,6 +156,8 @@ typedef struct nw_stats {
 #define NW_REDUCE_PARTIALS 2   /* fp64 block partial sums inside the transform kernel          */
 #define NW_REDUCE_CONN     3   /* nw_execute_conn: per-signal rows per chunk, every pair's sums
                                   added in epoch order by nw_conn_accumulate_kernel            */
+#define NW_REDUCE_CONN_TIME 4  /* nw_execute_conn_time: per-signal rows per chunk, every (epoch,
+                                  pair, scale) summed over the window by nw_conn_time_kernel    */
 
 /* nw_stats.kernel: which kernel wrote the output rows (the dominant kernel of a step) */
 #define NW_K_NONE        0
@@ -298,6 +300,39 @@ int nw_conn_tiles(int32_t nchan, const int32_t* ia, const int32_t* ib, int64_t n
 int nw_execute_conn(nw_plan* plan, const void* x, int64_t nepochs, int32_t nchan,
                     const int32_t* ia, const int32_t* ib, int64_t npairs,
                     void* out_cross, void* out_power, int out_kind, int mem);
+
+/* Host-only (no GPU): *count = T, the number of samples t0, t0 + step, ... < t1 of a window of
+ * nw_execute_conn_time.  NW_E_INVALID unless 0 <= t0 <= t1 <= n_out and step >= 1. */
+int nw_conn_time_count(int64_t n_out, int64_t t0, int64_t t1, int64_t step, int64_t* count);
+
+/* Over-time connectivity: nw_execute_conn's sums taken over the SAMPLES of each epoch instead of
+ * over the epochs -- one value per epoch, pair and scale (mne-connectivity's
+ * spectral_connectivity_time).  x, ia, ib, nchan, chunking (max_batch / nchan epochs,
+ * max_batch >= nchan), mem and every engine form as in nw_execute_conn.  The window is given in the
+ * plan's OUTPUT samples (n_out = n / decim): the samples s_j = t0 + j * step, j = 0 .. T - 1, with
+ * 0 <= t0 <= t1 <= n_out, step >= 1 (NW_E_INVALID otherwise) and T as nw_conn_time_count gives it.
+ * Outputs are epoch-major:
+ * NW_OUT_CROSS_SUM: out_sum complex128 (nepochs, npairs, F) = sum_j y_a conj(y_b),
+ *                   out_power float64 (nepochs, nchan, F) = sum_j |y_c|^2 (may be NULL).
+ * NW_OUT_PLV_SUM:   out_sum complex128 (nepochs, npairs, F) = sum_j unit phasor products;
+ *                   out_power must be NULL.
+ * NW_OUT_LAG_SUM:   out_sum float64 (nepochs, npairs, F, 4) = the phase-lag sums {L0 .. L3} over j;
+ *                   out_power must be NULL.
+ * The terms are nw_execute_conn's: fp64 values, every product and every term rounded on its own,
+ * for NW_OUT_PLV_SUM each value divided by its hypot first.
+ * SUMMATION ORDER (part of the contract).  There are 64 partial sums ("lanes").  Lane l starts at
+ * +0.0 and adds the terms of j = l, l + 64, l + 128, ... (j < T) in that order; a lane without such
+ * a j stays +0.0.  The 64 lane values are then folded: for d = 32, 16, 8, 4, 2, 1,
+ * v_l <- v_l + v_{l xor d}, and v_0 is the result (v = v[:h] + v[h:] for h = 32, 16, ..., 1).  Each
+ * component (re, im, each of the four lag sums, a power) is folded on its own.  A result therefore
+ * depends only on its two rows and on (t0, t1, step): not on the pair list, on its tiling or on how
+ * the epochs are chunked.
+ * nepochs = 0 or npairs = 0: empty outputs; t0 == t1: zero sums.  The sums of all epochs live in
+ * the plan (nw_stats.device_bytes); NW_E_NOMEM if they do not fit. */
+int nw_execute_conn_time(nw_plan* plan, const void* x, int64_t nepochs, int32_t nchan,
+                         const int32_t* ia, const int32_t* ib, int64_t npairs,
+                         int64_t t0, int64_t t1, int64_t step,
+                         void* out_sum, void* out_power, int out_kind, int mem);
 
 /* Shard nsig host signals over nplans plans (one per device, identical config),
  * one host thread per plan; balanced contiguous blocks (nsig / nplans signals, one

@@ -42,6 +42,7 @@ NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM = 7, 8          # nw_execute_pair only
 NW_OUT_LAG_SUM = 9                               # ... and nw_execute_conn: the phase-lag sums
 NW_REDUCE_NONE, NW_REDUCE_ROWS, NW_REDUCE_PARTIALS = 0, 1, 2   # nw_stats.reduce_path
 NW_REDUCE_CONN = 3                                              # ... of nw_execute_conn
+NW_REDUCE_CONN_TIME = 4                                         # ... of nw_execute_conn_time
 NW_MEM_HOST, NW_MEM_DEVICE = 0, 1
 # nw_stats.kernel -> the kernel name rocprofv3 shows
 KERNEL_NAMES = {0: None, 1: 'nw_fused_kernel', 2: 'nw_fused_pair_kernel', 3: 'nw_chirp_kernel',
@@ -96,6 +97,9 @@ SIGNATURES = [
     ('nw_execute_pair', ctypes.c_int, [_P, _P, _P, _I64, _P, ctypes.c_int, ctypes.c_int]),
     ('nw_conn_tiles', ctypes.c_int, [ctypes.c_int32, _P, _P, _I64, _P, ctypes.POINTER(_I64), _P]),
     ('nw_execute_conn', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _P, _P, ctypes.c_int, ctypes.c_int]),
+    ('nw_conn_time_count', ctypes.c_int, [_I64, _I64, _I64, _I64, ctypes.POINTER(_I64)]),
+    ('nw_execute_conn_time', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _I64, _I64, _I64, _P, _P,
+                                            ctypes.c_int, ctypes.c_int]),
     ('nw_execute_multi', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _I64, _P, ctypes.c_int]),
     ('nw_execute_multi_scales', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _I64, _P, ctypes.c_int]),
     ('nw_execute_multi_device', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(_P),
@@ -212,3 +216,11 @@ def conn_tiles(nchan: int, ia, ib):
     check(lib().nw_conn_tiles(int(nchan), ia.ctypes.data_as(_P), ib.ctypes.data_as(_P), int(ia.size),
                               tile.ctypes.data_as(_P), ctypes.byref(ntiles), ctypes.cast(limits, _P)))
     return tile, int(ntiles.value), tuple(limits)
+
+
+def conn_time_count(n_out: int, t0: int, t1: int, step: int = 1) -> int:
+    """T, the number of samples t0, t0 + step, ... < t1 that nw_execute_conn_time sums
+    (nw_conn_time_count; host-only).  ValueError unless 0 <= t0 <= t1 <= n_out and step >= 1."""
+    count = ctypes.c_int64()
+    check(lib().nw_conn_time_count(int(n_out), int(t0), int(t1), int(step), ctypes.byref(count)))
+    return int(count.value)

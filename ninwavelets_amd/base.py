@@ -27,7 +27,7 @@ from scipy.fftpack import fft, ifft
 
 from . import _lib as L
 from .engine import (CONN_OUTS, LAG_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim, check_indices, execute_multi,
-                     finalize_conn, finalize_lag, finalize_pair, np_dtype)
+                     finalize_conn, finalize_conn_time, finalize_lag, finalize_pair, np_dtype, time_window)
 from .engine import make_wavelets as _make_wavelets_dev
 
 # Device working-set budget per plan chunk (bytes); signals are streamed through it.
@@ -586,6 +586,50 @@ class WaveletBase:
         if decim > 1 and not on_device:
             sums = np.ascontiguousarray(sums[:, :, ::decim])
         return finalize_lag(out, sums, nep)
+
+    def connectivity_time_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, out: str = 'coherence',
+                                indices=None, window=None, decim: int = 1, average: bool = False):
+        """Over-time connectivity of ``waves`` (E, C, N): connectivity_batch's and
+        lag_connectivity_batch's measures with every sum taken over the SAMPLES of an epoch instead
+        of over the epochs, one value per epoch, pair and scale: (E, P, F) (what mne-connectivity's
+        spectral_connectivity_time returns per epoch).  Every signal is transformed once and reduced
+        on the device; the (E, C, F, N) rows never leave it.  ``out``: any name of CONN_OUTS or
+        LAG_OUTS (engine.finalize_conn_time, the sample count T in the place of the epoch count;
+        ``cross_sum`` returns (S (E, P, F), P_cc (E, C, F)), ``lag_sum`` (E, P, F, 4)).  ``window`` =
+        (t0, t1) in full-rate samples (None: the whole epoch); with ``decim`` the samples summed are
+        the decimated samples j * decim in [t0, t1).  ``average=True``: the mean over the epochs of
+        the finalised measure, (P, F) (ValueError for the ``*_sum`` kinds).  pli2_unbiased and ppc
+        need T >= 2.  Pair lists, cache semantics, device choice and plan eviction as in
+        connectivity_batch."""
+        decim = check_decim(decim)
+        if out not in CONN_OUTS and out not in LAG_OUTS:
+            raise ValueError(f"out must be one of {', '.join({**CONN_OUTS, **LAG_OUTS})}; got {out!r}")
+        if average and out.endswith('_sum'):
+            raise ValueError(f'average=True takes a finalised measure, not the sums {out!r}')
+        waves = np.asarray(waves)
+        if waves.ndim != 3:
+            raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
+        nep, nchan, n = waves.shape
+        ia, ib = check_indices(indices, nchan)
+        count = time_window(n, decim, window, False)[3]     # the same count on either kind of plan
+        if out in ('pli2_unbiased', 'ppc') and count < 2:
+            raise ValueError(f'{out} needs at least 2 samples in the window, got {count}')
+        if (not reuse) or self._cache is None:
+            self._build_cache(freqs, n / self.sfreq)
+        on_device = self._device_decim(n, decim)
+        t0, t1, step, count = time_window(n, decim, window, on_device)
+        need = CONN_OUTS[out] if out in CONN_OUTS else LAG_OUTS[out]
+        self._used = 1
+        try:
+            plan = self._plan(n, nep * nchan, (self.devices or [self.device])[0],
+                              decim=decim if on_device else 1, min_batch=nchan)
+            sums = plan.execute_conn_time(waves, (ia, ib), (t0, t1), step, out_kind=need)
+        finally:
+            if len(self._plans) > 1:
+                self._evict_plans(keep=1)
+        sums, power = sums if need == 'cross_sum' else (sums, None)
+        res = finalize_conn_time(out, sums, power, ia, ib, count)
+        return res.mean(axis=0) if average else res
 
     def plan_stats(self) -> list:
         """Per-plan device stage timings (nw_plan_stats)."""

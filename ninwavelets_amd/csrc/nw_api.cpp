@@ -1014,6 +1014,86 @@ int execute_conn(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs,
     return NW_OK;
 }
 
+// Over-time connectivity (nw_execute_conn_time): the chunks and the scratch of execute_conn; per
+// chunk nw_conn_time_kernel reduces every pair's products along the window's `count` samples
+// t0 + j * step and writes the chunk's epochs' slice of the (E, P, F) sums, which live in d_acc with
+// the (E, C, F) power sums and the tile descriptors.  Every value is written by exactly one block of
+// one launch: no memset.  One copy back at the end.
+int execute_conn_time(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ia,
+                      const int32_t* ib, int64_t npairs, int64_t t0, int64_t t1, int64_t step, void* out_sum,
+                      void* out_power, int out_kind, bool host) {
+    const int mode = nw::sum_mode(out_kind);
+    const int64_t count = nw::conn_time_count(t0, t1, step);
+    const int64_t fn = (int64_t)p->nfreq * p->n_out();
+    const size_t pair_bytes = (size_t)p->nfreq * (mode == nw::SUM_LAG ? 4 : 2) * sizeof(double);   // of one (e, p)
+    const size_t sum_bytes = (size_t)nepochs * npairs * pair_bytes;
+    const size_t power_bytes = out_power ? (size_t)nepochs * nchan * p->nfreq * sizeof(double) : 0;
+    p->conn_tiles = nw::host::conn_tiles(ia, ib, npairs, nullptr);
+    const size_t tile_bytes = p->conn_tiles.size() * sizeof(nw::ConnTile);
+    const size_t acc_bytes = sum_bytes + power_bytes;   // multiples of 8: the tiles start 16-aligned below
+    const size_t tile_at = (acc_bytes + 15) / 16 * 16;
+    const int got = p->d_acc.ensure(tile_at + tile_bytes + 16);
+    if (got != NW_OK && got != NW_E_NOMEM) return got;
+    if (got == NW_E_NOMEM)
+        return fail(NW_E_NOMEM, "nw_execute_conn_time: the fp64 sums of " + std::to_string(nepochs) + " epochs, " +
+                                    std::to_string(npairs) + " pairs and " + std::to_string(out_power ? nchan : 0) +
+                                    " channels need " + std::to_string(tile_at + tile_bytes + 16) +
+                                    " bytes of device memory: " + g_last_error);
+    char* const sums = p->d_acc.at(0);
+    char* const power = out_power ? p->d_acc.at(sum_bytes) : nullptr;
+    const nw::ConnTile* const tiles = (const nw::ConnTile*)p->d_acc.at(tile_at);
+    if (tile_bytes)
+        NW_HIP(hipMemcpyAsync((void*)tiles, p->conn_tiles.data(), tile_bytes, hipMemcpyHostToDevice, p->stream));
+    const bool xcd = !std::getenv("NW_CONN_PLAIN_ORDER");
+    const int64_t per = p->max_batch / nchan;
+    nw_logf(1, "plan %p: %s over time, %lld epochs x %d channels, %lld pairs in %lld tiles (%lld epochs per chunk), "
+               "window [%lld, %lld) step %lld of %lld samples, %s buffers: per-signal rows per chunk, every (epoch, "
+               "pair, scale) summed over its %lld samples in fp64 in lane order",
+            (void*)p, out_name(out_kind), (long long)nepochs, nchan, (long long)npairs, (long long)p->conn_tiles.size(),
+            (long long)per, (long long)t0, (long long)t1, (long long)step, (long long)p->n_out(),
+            host ? "host" : "device", (long long)count);
+    p->stats.reduce_path = NW_REDUCE_CONN_TIME;
+    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
+    if (p->form == FORM_ROCFFT) {
+        NW_TRY(need_Y(p, p->nfreq));
+        scratch = p->d_Y.ptr;
+    } else {
+        NW_TRY(p->d_out.ensure((size_t)p->max_batch * fn * 2 * p->esz));
+        scratch = p->d_out.ptr;
+    }
+    const size_t epoch_bytes = (size_t)nchan * p->n * p->esz;
+    for (int64_t e0 = 0; e0 < nepochs; e0 += per) {
+        const int64_t ec = std::min<int64_t>(per, nepochs - e0);
+        const void* xs = (const char*)x + (size_t)e0 * epoch_bytes;
+        if (host) {
+            NW_TRY(staged(p, ST_COPY, [&] {
+                NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, (size_t)ec * epoch_bytes, hipMemcpyHostToDevice, p->stream));
+                return NW_OK;
+            }));
+            xs = p->d_x.ptr;
+        }
+        NW_TRY(run_chunk(p, d, xs, ec * nchan, scratch, NW_OUT_CWT, false));
+        // chained: run_chunk ends with a stage
+        if (npairs > 0 || power)
+            NW_TRY(NW_KERNEL_STAGE(
+                p, ST_EPI, true,
+                nw::launch_conn_time(p->dtype, mode, scratch, sums + (size_t)e0 * npairs * pair_bytes,
+                                     power ? (double*)power + e0 * nchan * p->nfreq : nullptr, tiles,
+                                     (int)p->conn_tiles.size(), ec, nchan, p->nfreq, p->n_out(), npairs, t0, count, step,
+                                     xcd, p->stream)));
+        p->stats.chunks++;
+    }
+    const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (sum_bytes) NW_HIP(hipMemcpyAsync(out_sum, sums, sum_bytes, back, p->stream));
+    if (power_bytes) NW_HIP(hipMemcpyAsync(out_power, power, power_bytes, back, p->stream));
+    p->stats.executes++;
+    if (host) {
+        NW_HIP(hipStreamSynchronize(p->stream));
+        NW_TRY(resolve_timing(p));
+    }
+    return NW_OK;
+}
+
 // the pair list of nw_conn_tiles / nw_execute_conn: indices inside [0, nchan)
 int check_pairs(const char* who, int32_t nchan, const int32_t* ia, const int32_t* ib, int64_t npairs) {
     if (nchan < 1) return fail(NW_E_INVALID, std::string(who) + ": nchan < 1");
@@ -1529,6 +1609,50 @@ int nw_execute_conn(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, c
     nw_logf(1, "plan %p: execute conn %s, %lld epochs x %d channels, %lld pairs, %s buffers", (void*)p, out_name(out_kind),
             (long long)nepochs, (int)nchan, (long long)npairs, mem == NW_MEM_HOST ? "host" : "device");
     NW_TRY(execute_conn(p, d, x, nepochs, nchan, ia, ib, npairs, out_cross, out_power, out_kind, mem == NW_MEM_HOST));
+    return dcheck_collect(p->stream);
+}
+
+int nw_conn_time_count(int64_t n_out, int64_t t0, int64_t t1, int64_t step, int64_t* count) {
+    if (!count) return fail(NW_E_INVALID, "nw_conn_time_count: null argument");
+    if (step < 1) return fail(NW_E_INVALID, "nw_conn_time_count: step (" + std::to_string(step) + ") must be >= 1");
+    if (t0 < 0 || t0 > t1 || t1 > n_out)
+        return fail(NW_E_INVALID, "nw_conn_time_count: the window [" + std::to_string(t0) + ", " + std::to_string(t1) +
+                                      ") must satisfy 0 <= t0 <= t1 <= n_out (" + std::to_string(n_out) + ")");
+    *count = nw::conn_time_count(t0, t1, step);
+    return NW_OK;
+}
+
+int nw_execute_conn_time(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ia, const int32_t* ib,
+                         int64_t npairs, int64_t t0, int64_t t1, int64_t step, void* out_sum, void* out_power,
+                         int out_kind, int mem) {
+    if (!p || (!x && nepochs > 0) || (!out_sum && npairs > 0 && nepochs > 0))
+        return fail(NW_E_INVALID, "nw_execute_conn_time: null argument");
+    if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_conn_time: nw_plan_set_wavelet first");
+    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM && out_kind != NW_OUT_LAG_SUM)
+        return fail(NW_E_INVALID,
+                    "nw_execute_conn_time: out_kind must be NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM or NW_OUT_LAG_SUM");
+    if (out_kind == NW_OUT_PLV_SUM && out_power)
+        return fail(NW_E_INVALID, "nw_execute_conn_time: NW_OUT_PLV_SUM forms no power sums: out_power must be NULL");
+    if (out_kind == NW_OUT_LAG_SUM && out_power)
+        return fail(NW_E_INVALID, "nw_execute_conn_time: NW_OUT_LAG_SUM forms no power sums: out_power must be NULL");
+    if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_conn_time: bad mem");
+    if (nepochs < 0) return fail(NW_E_INVALID, "nw_execute_conn_time: nepochs < 0");
+    NW_TRY(check_pairs("nw_execute_conn_time", nchan, ia, ib, npairs));
+    if (p->max_batch < nchan)
+        return fail(NW_E_INVALID, "nw_execute_conn_time: the plan's max_batch (" + std::to_string(p->max_batch) +
+                                      ") must be >= nchan (" + std::to_string(nchan) +
+                                      "): a chunk holds max_batch / nchan epochs");
+    if (step < 1) return fail(NW_E_INVALID, "nw_execute_conn_time: step (" + std::to_string(step) + ") must be >= 1");
+    if (t0 < 0 || t0 > t1 || t1 > p->n_out())
+        return fail(NW_E_INVALID, "nw_execute_conn_time: the window [" + std::to_string(t0) + ", " + std::to_string(t1) +
+                                      ") must satisfy 0 <= t0 <= t1 <= n_out (" + std::to_string(p->n_out()) + ")");
+    DeviceGuard guard(p->device);
+    p->executed = true;
+    const nw::WDesc d = exec_rows(p);
+    // settle the form of a tentative length before any buffer choice
+    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
+    NW_TRY(execute_conn_time(p, d, x, nepochs, nchan, ia, ib, npairs, t0, t1, step, out_sum, out_power, out_kind,
+                             mem == NW_MEM_HOST));
     return dcheck_collect(p->stream);
 }
 

@@ -250,6 +250,13 @@ hipError_t launch_accumulate_pair(int dtype, int mode, const void* src, double* 
 hipError_t launch_conn_accumulate(int dtype, int mode, const void* src, void* cross, double* power,
                                   const ConnTile* tiles, int ntiles, int64_t ec, int nchan, int nfreq, int64_t n_out,
                                   int64_t npairs, bool xcd, hipStream_t s);
+// over-time connectivity (nw_conn_time.hip): src as above; sum (ec, npairs, F) complex fp64 (SUM_LAG:
+// (ec, npairs, F, 4) fp64) = the sums over the samples t0 + j * step, j < count, of the same terms, in
+// the order of nw_shape.h's conn_time_lane; power (ec, nchan, F) fp64 likewise (null, and always for
+// SUM_PLV and SUM_LAG: not formed).  Every value is written, none is read.
+hipError_t launch_conn_time(int dtype, int mode, const void* src, void* sum, double* power, const ConnTile* tiles,
+                            int ntiles, int64_t ec, int nchan, int nfreq, int64_t n_out, int64_t npairs, int64_t t0,
+                            int64_t count, int64_t step, bool xcd, hipStream_t s);
 hipError_t launch_finalize(int dtype, bool itc, const double* acc, void* out, int64_t fn, int64_t nsig,
                            hipStream_t s);
 hipError_t launch_add_f64(double* acc, const double* src, int64_t count, hipStream_t s);

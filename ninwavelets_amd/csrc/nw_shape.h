@@ -9,6 +9,8 @@
 //   - the W-table layout, the support rounding and the pass-0 ladders;
 //   - which partial-sum kernels exist;
 //   - the connectivity kernel (nw_conn.hip): its pair tile, sample tile and block order;
+//   - the over-time connectivity kernel (nw_conn_time.hip): its block -> (epoch, scale, pair tile)
+//     map, block count, the sample count of a window and the lane of a sample (the order contract);
 //   - the two-pass engine (nw_large.hip): the (N1, N2) split and its visitor, the row pass's
 //     elements per thread, rows per block, pass-0 ladder and LDS-DMA rule, the column pass's
 //     block shape, the scale chunk and the support buffer's layout (mode `large` prints them);
@@ -374,6 +376,37 @@ constexpr int64_t conn_units(int nfreq, int64_t n_out) { return (int64_t)nfreq *
 constexpr int64_t conn_blocks(int64_t nunits, int ntiles, bool xcd) {
     return (xcd ? (nunits + 7) / 8 * 8 : nunits) * ntiles;
 }
+
+// ---- over-time connectivity (nw_conn_time.hip) ------------------------------------------------
+
+// nw_conn_time_kernel: a block owns one epoch e of the chunk, one scale f and one pair tile, and
+// sums over the window's samples s_j = t0 + j * step, j = 0 .. T - 1.  Its unit is e * F + f; the
+// block order is conn_slot's (the pair tiles of one (e, f) neighbours on one XCD).
+struct ConnTimeSlot {
+    int64_t e;   // epoch of the chunk; >= ec: padding of the XCD order
+    int f, tile;
+};
+NW_SHAPE_HD NW_INLINE ConnTimeSlot conn_time_slot(int64_t b, int nfreq, int ntiles, bool xcd) {
+    const ConnSlot sl = conn_slot(b, ntiles, xcd);
+    return {sl.unit / nfreq, (int)(sl.unit % nfreq), sl.tile};
+}
+constexpr int64_t conn_time_blocks(int64_t ec, int nfreq, int ntiles, bool xcd) {
+    return conn_blocks(ec * nfreq, ntiles, xcd);
+}
+// T: the samples t0, t0 + step, ... < t1 (0 <= t0 <= t1, step >= 1)
+constexpr int64_t conn_time_count(int64_t t0, int64_t t1, int64_t step) { return (t1 - t0 + step - 1) / step; }
+// The summation order (the contract of nw_execute_conn_time, ninwave.h): lane conn_time_lane(j)
+// adds the terms of its samples j in increasing order to an accumulator that starts at +0.0; the
+// kConnTileN lane values are then folded, v_l <- v_l + v_{l xor d} for d = 32, 16, 8, 4, 2, 1,
+// and lane 0 holds the sum.
+constexpr int conn_time_lane(int64_t j) { return (int)(j % kConnTileN); }
+constexpr int64_t conn_time_tiles(int64_t count) { return (count + kConnTileN - 1) / kConnTileN; }
+static_assert(conn_time_count(0, 0, 1) == 0 && conn_time_count(37, 1001, 1) == 964 && conn_time_count(0, 1, 4) == 1 &&
+                  conn_time_count(8, 1000, 4) == 248 && conn_time_count(8, 1001, 4) == 249,
+              "window sample count");
+static_assert(conn_time_lane(0) == 0 && conn_time_lane(63) == 63 && conn_time_lane(64) == 0 && conn_time_tiles(65) == 2,
+              "lane of a sample");
+static_assert(conn_time_blocks(2, 9, 3, false) == 54 && conn_time_blocks(2, 9, 3, true) == 72, "block count");
 
 // ---- the two-pass engine (nw_large.hip) -----------------------------------------------------
 

@@ -201,6 +201,70 @@ def finalize_conn(kind: str, cross: np.ndarray, power, ia, ib, nepochs: int):
     return out
 
 
+def finalize_conn_time(kind: str, sums, power, ia, ib, nsamples: int):
+    """The connectivity measure ``kind`` (any name of CONN_OUTS or LAG_OUTS) per epoch, pair and
+    scale from the over-time sums of Plan.execute_conn_time over T = ``nsamples`` window samples:
+    ``sums`` complex128 (E, P, F) = S (plv, plv_sum, ciplv, ppc: Phi) or float64 (E, P, F, 4) = the lag
+    sums, ``power`` float64 (E, C, F) (cross-sum kinds only).  Per pair finalize_pair is applied to
+    stack(Re S, Im S, P[:, ia[p]], P[:, ib[p]]), or finalize_lag to the pair's sums, with T in the
+    place of the epoch count: csd = S / T, plv = |Phi| / T, pli = |L3| / T and so on (the coherence of
+    a channel with itself is exactly 1).  ``cross_sum`` returns (sums, power), ``plv_sum`` and
+    ``lag_sum`` return sums; the others (E, P, F): csd and coherency complex128, the rest float64.
+    pli2_unbiased and ppc need T >= 2 (ValueError)."""
+    if kind not in CONN_OUTS and kind not in LAG_OUTS:
+        raise ValueError(f"out must be one of {', '.join({**CONN_OUTS, **LAG_OUTS})}; got {kind!r}")
+    if kind == 'cross_sum':
+        return sums, power
+    if kind in ('plv_sum', 'lag_sum'):
+        return sums
+    T = int(nsamples)
+    if kind in LAG_OUTS:
+        if kind in ('pli2_unbiased', 'ppc') and T < 2:
+            raise ValueError(f'{kind} needs at least 2 samples in the window, got {T}')
+        sums = np.asarray(sums)
+        shape = sums.shape[:-1] if LAG_OUTS[kind] == 'lag_sum' else sums.shape
+        out = np.empty(shape, dtype=np.float64)
+        for p in range(shape[1]):
+            out[:, p] = finalize_lag(kind, sums[:, p], T)
+        return out
+    sums = np.asarray(sums, dtype=np.complex128)
+    out = np.empty(sums.shape, dtype=np.complex128 if kind in ('csd', 'coherency') else np.float64)
+    for p in range(sums.shape[1]):
+        if kind == 'plv':
+            out[:, p] = finalize_pair('plv', sums[:, p], T)
+        else:
+            four = np.stack([sums[:, p].real, sums[:, p].imag, power[:, ia[p]], power[:, ib[p]]], axis=-1)
+            out[:, p] = finalize_pair(kind, four, T)
+    return out
+
+
+def time_window(n: int, decim: int, window, on_device: bool):
+    """The window of connectivity_time_batch in a plan's output samples: (t0, t1, step, T).  ``window``
+    = (t0, t1) in full-rate samples of an n-sample signal (None: (0, n)); the samples summed are the
+    decimated samples j * decim in [t0, t1).  On a device-decimated plan (``on_device``, n_out =
+    n // decim) that is [ceil(t0 / decim), ceil(t1 / decim)) with step 1; on a full-rate plan
+    t0' = ceil(t0 / decim) * decim with step decim.  ValueError unless 0 <= t0 <= t1 <= n, integers."""
+    import operator
+    if window is None:
+        window = (0, n)
+    try:
+        t0, t1 = window
+        t0, t1 = operator.index(t0), operator.index(t1)
+    except (TypeError, ValueError):
+        raise ValueError(f'window must be a pair (t0, t1) of integers, got {window!r}') from None
+    if not 0 <= t0 <= t1 <= n:
+        raise ValueError(f'window must satisfy 0 <= t0 <= t1 <= {n}, got ({t0}, {t1})')
+    j0, j1 = -(-t0 // decim), -(-t1 // decim)
+    if on_device:
+        j1 = min(j1, n // decim)
+        j0 = min(j0, j1)
+        return j0, j1, 1, j1 - j0
+    if decim == 1:
+        return t0, t1, 1, t1 - t0
+    s0 = min(j0 * decim, t1)
+    return s0, t1, decim, -(-(t1 - s0) // decim)
+
+
 class HostPool:
     """Page-locked result arrays, recycled (nw_host_alloc).
 
@@ -612,6 +676,81 @@ class Plan:
         L.check(L.lib().nw_execute_conn(self._h, x.ctypes.data_as(P), nep, nchan, *ip, npairs, cross.ctypes.data_as(P),
                                         None if plv else power.ctypes.data_as(P), kind, L.NW_MEM_HOST))
         return cross if plv else (cross, power)
+
+    def execute_conn_time(self, x, indices=None, window=None, step: int = 1, out=None, out_kind: str = 'cross_sum'):
+        """Over-time connectivity sums (nw_execute_conn_time): x (E, C, n) as in execute_conn, every
+        signal transformed once and reduced on the device along the samples t0, t0 + step, ... < t1
+        of ``window`` = (t0, t1), in the plan's OUTPUT samples (None: (0, n_out)), into one value per
+        epoch, pair of ``indices`` and scale.  ``cross_sum`` -> (sums complex128 (E, P, nfreq), power
+        float64 (E, C, nfreq)); ``plv_sum`` -> complex128 (E, P, nfreq); ``lag_sum`` -> float64
+        (E, P, nfreq, 4); see finalize_conn_time.  numpy arrays: synchronous, ``out`` optional.  Device
+        tensors: asynchronous on the plan stream, ``out`` required ((sums, power) for cross_sum, power
+        may be None: not formed).  The plan needs max_batch >= C."""
+        import operator
+        if out_kind not in CONN_KINDS and out_kind not in LAG_KINDS:
+            raise ValueError(f"out_kind must be one of {', '.join({**CONN_KINDS, **LAG_KINDS})}; got {out_kind!r}")
+        kind = {**CONN_KINDS, **LAG_KINDS}[out_kind]
+        lag = out_kind == 'lag_sum'
+        plv = out_kind == 'plv_sum' or lag          # one output, no power sums
+        if getattr(x, 'ndim', 0) != 3:
+            raise ValueError(f'x must be (epochs, channels, n), got shape {tuple(getattr(x, "shape", ()))}')
+        nep, nchan = int(x.shape[0]), int(x.shape[1])
+        ia, ib = check_indices(indices, nchan)
+        npairs = int(ia.size)
+        try:
+            t0, t1 = (0, self.n_out) if window is None else window
+            t0, t1, step = operator.index(t0), operator.index(t1), operator.index(step)
+        except (TypeError, ValueError):
+            raise ValueError(f'window must be a pair (t0, t1) of integers and step an integer, got {window!r} and '
+                             f'{step!r}') from None
+        if step < 1:
+            raise ValueError(f'step must be >= 1, got {step}')
+        if not 0 <= t0 <= t1 <= self.n_out:
+            raise ValueError(f'window must satisfy 0 <= t0 <= t1 <= n_out = {self.n_out}, got ({t0}, {t1})')
+        P = ctypes.c_void_p
+        ip = (ia.ctypes.data_as(P), ib.ctypes.data_as(P))
+        if _is_device_tensor(x):
+            import torch
+            if out is None:
+                raise ValueError('device execute needs output tensors')
+            if self._check_device_input(x) != nep * nchan:
+                raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
+            sums, power = (out, None) if plv else out
+            for t, dt, count, name in ((sums, torch.float64 if lag else torch.complex128,
+                                        nep * npairs * self.nfreq * (4 if lag else 1), 'sums'),
+                                       (power, torch.float64, nep * nchan * self.nfreq, 'power')):
+                if t is None and name == 'power':
+                    continue
+                if not _is_device_tensor(t) or t.dtype != dt:
+                    raise ValueError(f'device output {name} must be a {dt} tensor on device {self.device}')
+                if not t.is_contiguous() or t.numel() != count:
+                    raise ValueError(f'device output {name} must be contiguous and hold {count} values')
+                if t.device.index != self.device:
+                    raise ValueError(f'device buffers must live on device {self.device}')
+            with self._ordered_with_torch(x.device):
+                L.check(L.lib().nw_execute_conn_time(self._h, P(x.data_ptr()), nep, nchan, *ip, npairs, t0, t1, step,
+                                                     P(sums.data_ptr()),
+                                                     P(power.data_ptr()) if power is not None else None, kind,
+                                                     L.NW_MEM_DEVICE))
+            return out
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        if x.shape[-1] != self.n:
+            raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
+        sums, power = (out, None) if plv or out is None else out
+        shapes = (((nep, npairs, self.nfreq, 4), np.float64) if lag else
+                  ((nep, npairs, self.nfreq), np.complex128), ((nep, nchan, self.nfreq), np.float64))
+        if sums is None:
+            sums = np.empty(*shapes[0])
+        if power is None and not plv:
+            power = np.empty(*shapes[1])
+        for a, (shape, dt) in zip((sums, power), shapes):
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous
+                                  or a.size != int(np.prod(shape))):
+                raise ValueError('out must be C-contiguous arrays of the right dtype and size')
+        L.check(L.lib().nw_execute_conn_time(self._h, x.ctypes.data_as(P), nep, nchan, *ip, npairs, t0, t1, step,
+                                             sums.ctypes.data_as(P), None if plv else power.ctypes.data_as(P), kind,
+                                             L.NW_MEM_HOST))
+        return sums if plv else (sums, power)
 
     def stream_ptr(self) -> int:
         """The hipStream_t the plan launches on."""

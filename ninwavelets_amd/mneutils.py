@@ -98,6 +98,26 @@ class EpochsWavelet:
         waves = self.epochs.get_data()[:, idx, :]
         return self.wavelet.lag_connectivity_batch(waves, freqs, reuse=True, out=method, indices=indices, decim=decim)
 
+    # -- over-time connectivity: one value per epoch, pair and scale, the sums taken over the samples
+    #    of each epoch on the device (WaveletBase.connectivity_time_batch) -------------------------
+    def connectivity_time(self, ch_names, freqs, method: str = 'coherence', indices=None, padding: float = 0.,
+                          decim: int = 1, average: bool = False):
+        """``method`` (connectivity's and lag_connectivity's) per epoch, (E, P, F): what
+        mne-connectivity's spectral_connectivity_time returns.  ``padding`` in seconds, as there: with
+        k = round(padding * sfreq) the samples [k, N - k) of every epoch are summed (ValueError if
+        that window is empty).  ``average=True``: the mean over the epochs, (P, F)."""
+        ch_names = list(ch_names)
+        idx = [self.epochs.ch_names.index(c) for c in ch_names]
+        waves = self.epochs.get_data()[:, idx, :]
+        n = waves.shape[-1]
+        if not padding >= 0:
+            raise ValueError(f'padding must be >= 0 seconds, got {padding!r}')
+        k = int(round(padding * self.epochs.info['sfreq']))
+        if k >= n - k:
+            raise ValueError(f'padding of {padding} s ({k} samples on each side) leaves no sample of the {n}')
+        return self.wavelet.connectivity_time_batch(waves, freqs, reuse=True, out=method, indices=indices,
+                                                    window=(k, n - k), decim=decim, average=average)
+
     # -- connectivity between many channels: one transform per epoch and channel, every pair's
     #    sums from it (WaveletBase.connectivity_batch; no reference counterpart) ---------------
     def connectivity(self, ch_names, freqs, method: str = 'coherence', indices=None, decim: int = 1):

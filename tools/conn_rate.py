@@ -16,7 +16,13 @@ C  the phase-lag sums (out_kind lag_sum), no gate: at A's fp32 n = 4096 shapes o
    execute_pair(lag_sum) calls; at B's shapes the kernel's lag mode per launch against its algorithmic
    bytes, the chunk's rows read once plus 2 P F n 32 B of accumulators (recorded in
    profiles/r14_lag_rate.txt).
-    [EC="2 8 32"] python tools/conn_rate.py [output file, default profiles/r12_conn_rate.txt] [A|B|AB|C]"""
+D  over-time connectivity (Plan.execute_conn_time, recorded in profiles/r15_conn_time_rate.txt), no gate:
+   at A's shapes, fp32 and fp64 n = 4096, one execute_conn_time(cross_sum) and one execute_conn_time(lag_sum)
+   against (a) execute_conn of the same kind on the same plan, which reads the same rows -- device, epilogue
+   stage (the reduction kernels alone) and wall ms -- and (b) the host route the call replaces: execute(...,
+   'cwt') to host memory plus the numpy reduction over the samples (wall, one run).  Then the reduction
+   kernels alone at 2 epochs per chunk (a grid of only ec F ntiles blocks) against A's 16.
+    [EC="2 8 32"] python tools/conn_rate.py [output file, default profiles/r12_conn_rate.txt] [A|B|AB|C|D]"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -195,6 +201,97 @@ def part_c_kernel(ec):
             (rows + accs) / ms / 1e9, 100 * (rows + accs) / (ms * 1e-3) / HBM))
 
 
+def part_d(dt):
+    n, E, C, F, batch = 4096, 64, 8, 64, 128
+    tdt = torch.float32 if dt == 'float32' else torch.float64
+    ia, ib = all_pairs(C)
+    P = len(ia)
+    plan = nw.Plan(n, F, dt, max_batch=batch, timing=True)
+    plan.set_wavelet('morse', [17.5, 3.], np.arange(1., F + 1), L.trans_grid(n / 1000., 1000., False))
+    common = torch.randn((E, 1, n), device='cuda', dtype=tdt)
+    x = (0.6 * common + 0.8 * torch.randn((E, C, n), device='cuda', dtype=tdt)).contiguous()
+    oc = torch.empty((P, F, n), device='cuda', dtype=torch.complex128)
+    opw = torch.empty((C, F, n), device='cuda', dtype=torch.float64)
+    ol = torch.empty((P, F, n, 4), device='cuda', dtype=torch.float64)
+    ts = torch.empty((E, P, F), device='cuda', dtype=torch.complex128)
+    tp = torch.empty((E, C, F), device='cuda', dtype=torch.float64)
+    tl = torch.empty((E, P, F, 4), device='cuda', dtype=torch.float64)
+
+    def once(arm):
+        kind, how = arm.split('/')
+        if how == 'time':
+            plan.execute_conn_time(x, (ia, ib), out=(ts, tp) if kind == 'cross_sum' else tl, out_kind=kind)
+        else:
+            plan.execute_conn(x, (ia, ib), out=(oc, opw) if kind == 'cross_sum' else ol, out_kind=kind)
+
+    arms = ('cross_sum/time', 'cross_sum/conn', 'lag_sum/time', 'lag_sum/conn')
+    dev, epi, wall = ({k: [] for k in arms} for _ in range(3))
+    for k in arms:
+        once(k); plan.sync(); torch.cuda.synchronize()
+    for _ in range(7):
+        for k in arms:
+            plan.reset_stats()
+            t0 = time.perf_counter(); once(k); plan.sync(); torch.cuda.synchronize()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+            st = plan.stats()
+            dev[k].append(sum(st[s] for s in STAGES))
+            epi[k].append(st['ms_epilogue'])
+    chunks = st['chunks']
+    for kind in ('cross_sum', 'lag_sum'):
+        t, c = kind + '/time', kind + '/conn'
+        say('D %s n=%d C=%d P=%d E=%d F=%d %-9s one execute_conn_time: device %.3f ms (median %.3f), of it the reduction '
+            '(epilogue stage, %d launches) %.3f ms (median %.3f), wall %.3f ms (median %.3f) | (a) one execute_conn: device '
+            '%.3f ms (median %.3f), reduction %.3f ms (median %.3f), wall %.3f ms (median %.3f) | time / conn: device '
+            '%.3fx reduction %.3fx wall %.3fx' % (
+                dt, n, C, P, E, F, kind, min(dev[t]), np.median(dev[t]), chunks, min(epi[t]), np.median(epi[t]),
+                min(wall[t]), np.median(wall[t]), min(dev[c]), np.median(dev[c]), min(epi[c]), np.median(epi[c]),
+                min(wall[c]), np.median(wall[c]), min(dev[t]) / min(dev[c]), min(epi[t]) / min(epi[c]),
+                min(wall[t]) / min(wall[c])))
+    # (b) the host route: every row over PCIe, then numpy sums over the samples (one warm transform, one timed run)
+    xh = x.cpu().numpy()
+    plan.execute(xh.reshape(E * C, n), out_kind='cwt')
+    for kind in ('cross_sum', 'lag_sum'):
+        t0 = time.perf_counter()
+        y = plan.execute(xh.reshape(E * C, n), out_kind='cwt').reshape(E, C, F, n)
+        t1 = time.perf_counter()
+        if kind == 'cross_sum':
+            res = [np.stack([np.einsum('eft,eft->ef', y[:, a], np.conj(y[:, b])) for a, b in zip(ia, ib)], axis=1),
+                   np.einsum('ecft,ecft->ecf', y.real, y.real) + np.einsum('ecft,ecft->ecf', y.imag, y.imag)]
+        else:
+            res = []
+            for a, b in zip(ia, ib):
+                m = y[:, a].imag * y[:, b].real - y[:, a].real * y[:, b].imag
+                res.append(np.stack([m.sum(-1), np.abs(m).sum(-1), (m * m).sum(-1), np.sign(m).sum(-1)], axis=-1))
+        t2 = time.perf_counter()
+        del y, res
+        say('D %s n=%d C=%d P=%d E=%d F=%d %-9s (b) the host route: execute(cwt) to host %.1f ms + numpy reduction %.1f ms = '
+            'wall %.1f ms | host route / execute_conn_time: wall %.0fx' % (
+                dt, n, C, P, E, F, kind, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t2 - t0) * 1e3,
+                (t2 - t0) * 1e3 / min(wall[kind + '/time'])))
+    plan.close()
+    # the reduction kernels alone per launch: 16 epochs per chunk (above) and 2
+    per16 = {k: min(epi[k + '/time']) / chunks for k in ('cross_sum', 'lag_sum')}
+    small = nw.Plan(n, F, dt, max_batch=2 * C, timing=True)
+    small.set_wavelet('morse', [17.5, 3.], np.arange(1., F + 1), L.trans_grid(n / 1000., 1000., False))
+    x4 = x[:4].contiguous()
+    for kind in ('cross_sum', 'lag_sum'):
+        best = []
+        for rep in range(6):
+            small.reset_stats()
+            small.execute_conn_time(x4, (ia, ib), out=(ts[:4], None) if kind == 'cross_sum' else tl[:4], out_kind=kind)
+            small.sync()
+            st = small.stats()
+            if rep:
+                best.append(st['ms_epilogue'] / st['chunks'])
+        rows = 2 * C * F * n * 2 * (4 if dt == 'float32' else 8)
+        say('D %s n=%d C=%d P=%d F=%d %-9s nw_conn_time_kernel alone, ec=2 (%d blocks): %.4f ms per launch, %.4f ms per '
+            'epoch, rows %.4f GB -> %.2f TB/s | ec=16 (%d blocks, with the power kernel for cross_sum): %.4f ms per launch, '
+            '%.4f ms per epoch' % (dt, n, C, P, F, kind, 2 * F * L.conn_tiles(C, ia, ib)[1], min(best), min(best) / 2,
+                                   rows / 1e9, rows / min(best) / 1e9, 16 * F * L.conn_tiles(C, ia, ib)[1], per16[kind],
+                                   per16[kind] / 16))
+    small.close()
+
+
 say('# tools/conn_rate.py on %s, %s' % (torch.cuda.get_device_name(0), os.environ.get('NINWAVE_LIB', 'libninwave.so')))
 gate = True
 if 'A' in parts:
@@ -208,6 +305,9 @@ if 'C' in parts:
     part_c_calls()
     for ec in [int(v) for v in os.environ.get('EC', '2 8 32').split()]:
         part_c_kernel(ec)
+if 'D' in parts:
+    part_d('float32')
+    part_d('float64')
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, 'w') as f:
     f.write('\n'.join(lines) + '\n')
