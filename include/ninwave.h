@@ -158,6 +158,9 @@ typedef struct nw_stats {
                                   added in epoch order by nw_conn_accumulate_kernel            */
 #define NW_REDUCE_CONN_TIME 4  /* nw_execute_conn_time: per-signal rows per chunk, every (epoch,
                                   pair, scale) summed over the window by nw_conn_time_kernel    */
+#define NW_REDUCE_PAC      5   /* nw_execute_pac: per-signal rows per chunk, every (epoch, pair,
+                                  phase scale, amplitude scale) summed over the window by
+                                  nw_pac_kernel                                                 */
 
 /* nw_stats.kernel: which kernel wrote the output rows (the dominant kernel of a step) */
 #define NW_K_NONE        0
@@ -333,6 +336,32 @@ int nw_execute_conn_time(nw_plan* plan, const void* x, int64_t nepochs, int32_t 
                          const int32_t* ia, const int32_t* ib, int64_t npairs,
                          int64_t t0, int64_t t1, int64_t step,
                          void* out_sum, void* out_power, int out_kind, int mem);
+
+/* Phase-amplitude coupling: per epoch and channel pair the sums from which a comodulogram over
+ * (phase scale, amplitude scale) is formed, reduced on the device along the samples of a window.
+ * x, nchan, chunking (max_batch / nchan epochs, max_batch >= nchan), mem, every engine form, the
+ * window (t0, t1, step) in the plan's OUTPUT samples and T are nw_execute_conn_time's.
+ * ip, ia: HOST arrays [npairs], the phase and the amplitude channel of each pair (any list: repeats,
+ * ip == ia).  fph [nph], fam [nam]: HOST arrays of positions into the plan's scale list (any lists:
+ * repeats, a scale in both); a position outside [0, nfreq) is NW_E_INVALID.  With, in fp64,
+ *   A = hypot(re, im)            of y_{e, ia[p]}[fam[k], s_j]   (amp: of channel c)
+ *   u = (re / h, im / h), h = hypot(re, im)   of y_{e, ip[p]}[fph[i], s_j]   (phase: of channel c; the
+ *       unit phasor of NW_OUT_PLV_SUM, NaN where |y| = 0)
+ * the outputs are epoch-major:
+ *   out_m     complex128 (nepochs, npairs, nph, nam) = sum_j A u
+ *   out_amp   float64    (nepochs, nchan, nam, 2)    = {sum_j A, sum_j (re^2 + im^2)}   (may be NULL)
+ *   out_phase complex128 (nepochs, nchan, nph)       = sum_j u                            (may be NULL)
+ * Every product (A u.re, A u.im, re re, im im) and every term is rounded on its own, and every sum
+ * runs in nw_execute_conn_time's SUMMATION ORDER, so a result depends only on its rows and on
+ * (t0, t1, step): not on the pair list, the scale lists, their tiling or the chunks; the second
+ * value of out_amp is bit-identical to nw_execute_conn_time's out_power of the same row and window.
+ * nepochs = 0, npairs = 0 or an empty list: empty outputs; t0 == t1: zero sums.  The sums of all
+ * epochs live in the plan (nw_stats.device_bytes); NW_E_NOMEM if they do not fit. */
+int nw_execute_pac(nw_plan* plan, const void* x, int64_t nepochs, int32_t nchan,
+                   const int32_t* ip, const int32_t* ia, int64_t npairs,
+                   const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam,
+                   int64_t t0, int64_t t1, int64_t step,
+                   void* out_m, void* out_amp, void* out_phase, int mem);
 
 /* Shard nsig host signals over nplans plans (one per device, identical config),
  * one host thread per plan; balanced contiguous blocks (nsig / nplans signals, one

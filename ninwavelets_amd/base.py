@@ -26,8 +26,9 @@ import numpy as np
 from scipy.fftpack import fft, ifft
 
 from . import _lib as L
-from .engine import (CONN_OUTS, LAG_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim, check_indices, execute_multi,
-                     finalize_conn, finalize_conn_time, finalize_lag, finalize_pair, np_dtype, time_window)
+from .engine import (CONN_OUTS, LAG_OUTS, PAC_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim, check_indices,
+                     check_pac_indices, check_scales, execute_multi, finalize_conn, finalize_conn_time, finalize_lag,
+                     finalize_pac, finalize_pair, np_dtype, time_window)
 from .engine import make_wavelets as _make_wavelets_dev
 
 # Device working-set budget per plan chunk (bytes); signals are streamed through it.
@@ -629,6 +630,49 @@ class WaveletBase:
                 self._evict_plans(keep=1)
         sums, power = sums if need == 'cross_sum' else (sums, None)
         res = finalize_conn_time(out, sums, power, ia, ib, count)
+        return res.mean(axis=0) if average else res
+
+    def pac_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, phase=None, amp=None,
+                  out: str = 'direct_pac', indices=None, window=None, decim: int = 1, average: bool = False):
+        """Phase-amplitude coupling of ``waves`` (E, C, N): how the amplitude of the scales ``amp``
+        follows the phase of the scales ``phase`` (both lists of positions into the scale list; any
+        lists), one comodulogram per epoch and pair: (E, P, Fp, Fa) float64.  ``indices`` = (ip, ia),
+        the phase and the amplitude channel of each pair (None: every channel with itself, P = C).
+        Every signal is transformed once and reduced on the device; the (E, C, F, N) rows never leave
+        it.  ``out``: mvl, mvl_norm, direct_pac or debiased_pac (engine.finalize_pac); ``pac_sum``
+        returns the sums (M (E, P, Fp, Fa), amp (E, C, Fa, 2), phase (E, C, Fp)).  ``window``, ``decim``
+        and ``average`` (the mean over the epochs, (P, Fp, Fa); ValueError for ``pac_sum``) as in
+        connectivity_time_batch; an empty window is a ValueError for the finalised kinds.  Cache
+        semantics, device choice and plan eviction as in connectivity_batch."""
+        decim = check_decim(decim)
+        if out not in PAC_OUTS:
+            raise ValueError(f"out must be one of {', '.join(sorted(PAC_OUTS))}; got {out!r}")
+        if average and out == 'pac_sum':
+            raise ValueError(f'average=True takes a finalised measure, not the sums {out!r}')
+        waves = np.asarray(waves)
+        if waves.ndim != 3:
+            raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
+        nep, nchan, n = waves.shape
+        ip, ia = check_pac_indices(indices, nchan)
+        rebuild = (not reuse) or self._cache is None
+        nfreq = len(list(freqs)) if rebuild else len(self._cache.freqs)     # the scale list the call will use
+        fph, fam = check_scales('phase', phase, nfreq), check_scales('amp', amp, nfreq)
+        count = time_window(n, decim, window, False)[3]     # the same count on either kind of plan
+        if out != 'pac_sum' and count < 1:
+            raise ValueError(f'{out} needs at least 1 sample in the window, got {count}')
+        if rebuild:
+            self._build_cache(freqs, n / self.sfreq)
+        on_device = self._device_decim(n, decim)
+        t0, t1, step, count = time_window(n, decim, window, on_device)
+        self._used = 1
+        try:
+            plan = self._plan(n, nep * nchan, (self.devices or [self.device])[0],
+                              decim=decim if on_device else 1, min_batch=nchan)
+            sums = plan.execute_pac(waves, (ip, ia), fph, fam, (t0, t1), step)
+        finally:
+            if len(self._plans) > 1:
+                self._evict_plans(keep=1)
+        res = finalize_pac(out, *sums, ip, ia, count)
         return res.mean(axis=0) if average else res
 
     def plan_stats(self) -> list:

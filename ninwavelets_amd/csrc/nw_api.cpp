@@ -268,6 +268,7 @@ struct nw_plan {
     DevBuf d_acc;                    // epoch reductions: fp64 (F, n) sums (x2 for phases); nw_execute_conn:
                                      // complex (npairs, F, n) | (nchan, F, n) | the pair tiles
     std::vector<nw::ConnTile> conn_tiles;   // nw_execute_conn: the last call's tiles (the upload's source)
+    std::vector<int32_t> pac_lists;         // nw_execute_pac: the last call's ip | ia | fph | fam (likewise)
     // nw_execute_multi_device reductions: this device's fp64 partial sums, and (device 0's
     // plan) the peer-copy landing buffer; kept across calls (a hipFree per call would
     // synchronise the device on every epoch-loop iteration)
@@ -1094,6 +1095,96 @@ int execute_conn_time(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nep
     return NW_OK;
 }
 
+// Phase-amplitude coupling (nw_execute_pac): the chunks, the scratch and the window of
+// execute_conn_time; per chunk nw_pac_kernel reduces every pair's |y_a| u_p products along the
+// window's `count` samples for every listed (phase, amplitude) scale and writes the chunk's epochs'
+// slice of the (E, P, nph, nam) sums, nw_pac_rows_kernel the per-channel sums.  The sums live in d_acc
+// with the pair and scale lists.  Every value is written by exactly one block of one launch: no memset.
+int execute_pac(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ip,
+                const int32_t* ia, int64_t npairs, const int32_t* fph, int nph, const int32_t* fam, int nam,
+                int64_t t0, int64_t t1, int64_t step, void* out_m, void* out_amp, void* out_phase, bool host) {
+    const int64_t count = nw::conn_time_count(t0, t1, step);
+    const int64_t fn = (int64_t)p->nfreq * p->n_out();
+    const size_t m_epoch = (size_t)npairs * nph * nam * 2 * sizeof(double);        // of one epoch
+    const size_t amp_epoch = (size_t)nchan * nam * 2 * sizeof(double);
+    const size_t phase_epoch = (size_t)nchan * nph * 2 * sizeof(double);
+    const size_t m_bytes = (size_t)nepochs * m_epoch;
+    const size_t amp_bytes = out_amp ? (size_t)nepochs * amp_epoch : 0;
+    const size_t phase_bytes = out_phase ? (size_t)nepochs * phase_epoch : 0;
+    const size_t acc_bytes = m_bytes + amp_bytes + phase_bytes;   // multiples of 16
+    std::vector<int32_t>& lists = p->pac_lists;                   // ip, ia, fph, fam
+    lists.clear();
+    lists.insert(lists.end(), ip, ip + npairs);
+    lists.insert(lists.end(), ia, ia + npairs);
+    lists.insert(lists.end(), fph, fph + nph);
+    lists.insert(lists.end(), fam, fam + nam);
+    const size_t list_bytes = lists.size() * sizeof(int32_t);
+    const int got = p->d_acc.ensure(acc_bytes + list_bytes + 16);
+    if (got != NW_OK && got != NW_E_NOMEM) return got;
+    if (got == NW_E_NOMEM)
+        return fail(NW_E_NOMEM, "nw_execute_pac: the fp64 sums of " + std::to_string(nepochs) + " epochs, " +
+                                    std::to_string(npairs) + " pairs and " + std::to_string(nph) + " x " +
+                                    std::to_string(nam) + " scales need " + std::to_string(acc_bytes + list_bytes + 16) +
+                                    " bytes of device memory: " + g_last_error);
+    char* const m = p->d_acc.at(0);
+    char* const amp = out_amp ? p->d_acc.at(m_bytes) : nullptr;
+    char* const phase = out_phase ? p->d_acc.at(m_bytes + amp_bytes) : nullptr;
+    const int32_t* const d_ip = (const int32_t*)p->d_acc.at(acc_bytes);
+    const int32_t* const d_ia = d_ip + npairs;
+    const int32_t* const d_fph = d_ia + npairs;
+    const int32_t* const d_fam = d_fph + nph;
+    if (list_bytes) NW_HIP(hipMemcpyAsync((void*)d_ip, lists.data(), list_bytes, hipMemcpyHostToDevice, p->stream));
+    const bool xcd = !std::getenv("NW_CONN_PLAIN_ORDER");
+    const int64_t per = p->max_batch / nchan;
+    nw_logf(1, "plan %p: pac sums, %lld epochs x %d channels, %lld pairs, %d phase x %d amplitude scales in %lld tiles "
+               "(%lld epochs per chunk), window [%lld, %lld) step %lld of %lld samples, %s buffers: per-signal rows per "
+               "chunk, every (epoch, pair, phase scale, amplitude scale) summed over its %lld samples in fp64 in lane "
+               "order",
+            (void*)p, (long long)nepochs, nchan, (long long)npairs, nph, nam, (long long)nw::pac_tiles(nph, nam),
+            (long long)per, (long long)t0, (long long)t1, (long long)step, (long long)p->n_out(),
+            host ? "host" : "device", (long long)count);
+    p->stats.reduce_path = NW_REDUCE_PAC;
+    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
+    if (p->form == FORM_ROCFFT) {
+        NW_TRY(need_Y(p, p->nfreq));
+        scratch = p->d_Y.ptr;
+    } else {
+        NW_TRY(p->d_out.ensure((size_t)p->max_batch * fn * 2 * p->esz));
+        scratch = p->d_out.ptr;
+    }
+    const size_t epoch_bytes = (size_t)nchan * p->n * p->esz;
+    for (int64_t e0 = 0; e0 < nepochs; e0 += per) {
+        const int64_t ec = std::min<int64_t>(per, nepochs - e0);
+        const void* xs = (const char*)x + (size_t)e0 * epoch_bytes;
+        if (host) {
+            NW_TRY(staged(p, ST_COPY, [&] {
+                NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, (size_t)ec * epoch_bytes, hipMemcpyHostToDevice, p->stream));
+                return NW_OK;
+            }));
+            xs = p->d_x.ptr;
+        }
+        NW_TRY(run_chunk(p, d, xs, ec * nchan, scratch, NW_OUT_CWT, false));
+        // chained: run_chunk ends with a stage
+        if (acc_bytes)
+            NW_TRY(NW_KERNEL_STAGE(
+                p, ST_EPI, true,
+                nw::launch_pac(p->dtype, scratch, m + (size_t)e0 * m_epoch, amp ? amp + (size_t)e0 * amp_epoch : nullptr,
+                               phase ? phase + (size_t)e0 * phase_epoch : nullptr, d_ip, d_ia, d_fph, d_fam, ec, nchan,
+                               p->nfreq, p->n_out(), npairs, nph, nam, t0, count, step, xcd, p->stream)));
+        p->stats.chunks++;
+    }
+    const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (m_bytes) NW_HIP(hipMemcpyAsync(out_m, m, m_bytes, back, p->stream));
+    if (amp_bytes) NW_HIP(hipMemcpyAsync(out_amp, amp, amp_bytes, back, p->stream));
+    if (phase_bytes) NW_HIP(hipMemcpyAsync(out_phase, phase, phase_bytes, back, p->stream));
+    p->stats.executes++;
+    if (host) {
+        NW_HIP(hipStreamSynchronize(p->stream));
+        NW_TRY(resolve_timing(p));
+    }
+    return NW_OK;
+}
+
 // the pair list of nw_conn_tiles / nw_execute_conn: indices inside [0, nchan)
 int check_pairs(const char* who, int32_t nchan, const int32_t* ia, const int32_t* ib, int64_t npairs) {
     if (nchan < 1) return fail(NW_E_INVALID, std::string(who) + ": nchan < 1");
@@ -1653,6 +1744,48 @@ int nw_execute_conn_time(nw_plan* p, const void* x, int64_t nepochs, int32_t nch
     if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
     NW_TRY(execute_conn_time(p, d, x, nepochs, nchan, ia, ib, npairs, t0, t1, step, out_sum, out_power, out_kind,
                              mem == NW_MEM_HOST));
+    return dcheck_collect(p->stream);
+}
+
+int nw_execute_pac(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ip, const int32_t* ia,
+                   int64_t npairs, const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam, int64_t t0,
+                   int64_t t1, int64_t step, void* out_m, void* out_amp, void* out_phase, int mem) {
+    if (!p || (!x && nepochs > 0) || (!out_m && npairs > 0 && nepochs > 0 && nph > 0 && nam > 0))
+        return fail(NW_E_INVALID, "nw_execute_pac: null argument");
+    if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_pac: nw_plan_set_wavelet first");
+    if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_pac: bad mem");
+    if (nepochs < 0) return fail(NW_E_INVALID, "nw_execute_pac: nepochs < 0");
+    NW_TRY(check_pairs("nw_execute_pac", nchan, ip, ia, npairs));
+    if (nph < 0 || nam < 0) return fail(NW_E_INVALID, "nw_execute_pac: nph < 0 or nam < 0");
+    if ((nph > 0 && !fph) || (nam > 0 && !fam)) return fail(NW_E_INVALID, "nw_execute_pac: null scale list");
+    for (int which = 0; which < 2; ++which) {
+        const int32_t* const f = which ? fam : fph;
+        for (int32_t i = 0; i < (which ? nam : nph); ++i)
+            if (f[i] < 0 || f[i] >= p->nfreq)
+                return fail(NW_E_INVALID, std::string("nw_execute_pac: ") + (which ? "amplitude" : "phase") +
+                                              " scale " + std::to_string(i) + " = " + std::to_string(f[i]) +
+                                              " is outside [0, " + std::to_string(p->nfreq) + ")");
+    }
+    if (p->max_batch < nchan)
+        return fail(NW_E_INVALID, "nw_execute_pac: the plan's max_batch (" + std::to_string(p->max_batch) +
+                                      ") must be >= nchan (" + std::to_string(nchan) +
+                                      "): a chunk holds max_batch / nchan epochs");
+    if (step < 1) return fail(NW_E_INVALID, "nw_execute_pac: step (" + std::to_string(step) + ") must be >= 1");
+    if (t0 < 0 || t0 > t1 || t1 > p->n_out())
+        return fail(NW_E_INVALID, "nw_execute_pac: the window [" + std::to_string(t0) + ", " + std::to_string(t1) +
+                                      ") must satisfy 0 <= t0 <= t1 <= n_out (" + std::to_string(p->n_out()) + ")");
+    // the grid of one chunk's launch (block indices are 32-bit)
+    const int64_t blocks = nw::pac_blocks(std::max<int64_t>(p->max_batch / nchan, 1), npairs, nw::pac_tiles(nph, nam), true);
+    if (blocks < 0 || blocks > 0x7fffffff)
+        return fail(NW_E_INVALID, "nw_execute_pac: " + std::to_string(npairs) + " pairs x " + std::to_string(nph) + " x " +
+                                      std::to_string(nam) + " scales per chunk need more than 2^31 - 1 blocks");
+    DeviceGuard guard(p->device);
+    p->executed = true;
+    const nw::WDesc d = exec_rows(p);
+    // settle the form of a tentative length before any buffer choice
+    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
+    NW_TRY(execute_pac(p, d, x, nepochs, nchan, ip, ia, npairs, fph, nph, fam, nam, t0, t1, step, out_m, out_amp,
+                       out_phase, mem == NW_MEM_HOST));
     return dcheck_collect(p->stream);
 }
 

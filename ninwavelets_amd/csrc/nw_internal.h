@@ -257,6 +257,15 @@ hipError_t launch_conn_accumulate(int dtype, int mode, const void* src, void* cr
 hipError_t launch_conn_time(int dtype, int mode, const void* src, void* sum, double* power, const ConnTile* tiles,
                             int ntiles, int64_t ec, int nchan, int nfreq, int64_t n_out, int64_t npairs, int64_t t0,
                             int64_t count, int64_t step, bool xcd, hipStream_t s);
+// phase-amplitude coupling (nw_pac.hip): src as above; m (ec, npairs, nph, nam) complex fp64 = the sums
+// over the samples t0 + j * step, j < count, of A u (A: |y| of channel ia[p]'s row fam[k], u: the unit
+// phasor of channel ip[p]'s row fph[i]), in the order of conn_time_lane; amp (ec, nchan, nam, 2) fp64 =
+// {sum A, sum |y|^2} and phase (ec, nchan, nph) complex fp64 = sum u per channel (null: not formed).
+// ip, ia [npairs], fph [nph], fam [nam]: device arrays.  Every value is written, none is read.
+hipError_t launch_pac(int dtype, const void* src, void* m, void* amp, void* phase, const int32_t* ip, const int32_t* ia,
+                      const int32_t* fph, const int32_t* fam, int64_t ec, int nchan, int nfreq, int64_t n_out,
+                      int64_t npairs, int nph, int nam, int64_t t0, int64_t count, int64_t step, bool xcd,
+                      hipStream_t s);
 hipError_t launch_finalize(int dtype, bool itc, const double* acc, void* out, int64_t fn, int64_t nsig,
                            hipStream_t s);
 hipError_t launch_add_f64(double* acc, const double* src, int64_t count, hipStream_t s);

@@ -11,6 +11,8 @@
 //   - the connectivity kernel (nw_conn.hip): its pair tile, sample tile and block order;
 //   - the over-time connectivity kernel (nw_conn_time.hip): its block -> (epoch, scale, pair tile)
 //     map, block count, the sample count of a window and the lane of a sample (the order contract);
+//   - the phase-amplitude coupling kernel (nw_pac.hip): its scale tile, the tile counts and its
+//     block -> (epoch, pair, phase tile, amplitude tile) map;
 //   - the two-pass engine (nw_large.hip): the (N1, N2) split and its visitor, the row pass's
 //     elements per thread, rows per block, pass-0 ladder and LDS-DMA rule, the column pass's
 //     block shape, the scale chunk and the support buffer's layout (mode `large` prints them);
@@ -407,6 +409,48 @@ static_assert(conn_time_count(0, 0, 1) == 0 && conn_time_count(37, 1001, 1) == 9
 static_assert(conn_time_lane(0) == 0 && conn_time_lane(63) == 63 && conn_time_lane(64) == 0 && conn_time_tiles(65) == 2,
               "lane of a sample");
 static_assert(conn_time_blocks(2, 9, 3, false) == 54 && conn_time_blocks(2, 9, 3, true) == 72, "block count");
+
+// ---- phase-amplitude coupling (nw_pac.hip) ----------------------------------------------------
+
+// nw_pac_kernel: a block owns one epoch e of the chunk, one channel pair and one scale tile of at
+// most kPacPh listed phase scales x kPacAm listed amplitude scales; wave w of its kPacWaves keeps the
+// amplitude scales w * kPacAmWave .. of the tile against all kPacPh phase scales in registers
+// (kPacAmWave * kPacPh complex fp64 accumulators), lane = sample of a kConnTileN-sample tile, and the
+// sums run in conn_time_lane's order.  Per sample tile every wave stages kPacStagePh phase rows (as
+// unit phasors) and kPacStageAm amplitude rows (as magnitudes) in LDS.
+constexpr int kPacPh = 8;
+constexpr int kPacAm = 16;
+constexpr int kPacWaves = 4;
+constexpr int kPacAmWave = kPacAm / kPacWaves;
+constexpr int kPacStagePh = kPacPh / kPacWaves;
+constexpr int kPacStageAm = kPacAm / kPacWaves;
+static_assert(kPacAm % kPacWaves == 0 && kPacPh % kPacWaves == 0, "pac geometry");
+static_assert(2 * (2 * kPacPh + kPacAm) * kConnTileN * 8 <= 64 * 1024, "double-buffered staging fits the LDS of a block");
+constexpr int64_t pac_tiles_ph(int64_t nph) { return (nph + kPacPh - 1) / kPacPh; }
+constexpr int64_t pac_tiles_am(int64_t nam) { return (nam + kPacAm - 1) / kPacAm; }
+// The scale tiles of one (epoch, pair), amplitude tile fastest (pac_blocks is -1 where their count does
+// not fit conn_slot's 32-bit tile index).
+constexpr int64_t pac_tiles(int64_t nph, int64_t nam) { return pac_tiles_ph(nph) * pac_tiles_am(nam); }
+// block -> (epoch, pair, phase tile, amplitude tile).  The unit of conn_slot is e * npairs + pair: in the
+// XCD order the scale tiles of one (epoch, pair) -- which read the same two channels' rows -- are
+// neighbours on one XCD, and the units are padded to a multiple of 8 (a slot with e >= ec is padding
+// and its block returns).  ntiles = pac_tiles(nph, nam) >= 1, nta = pac_tiles_am(nam), npairs >= 1.
+struct PacSlot {
+    int64_t e;   // epoch of the chunk; >= ec: padding of the XCD order
+    int pair, tp, ta;
+};
+NW_SHAPE_HD NW_INLINE PacSlot pac_slot(int64_t b, int npairs, int ntiles, int nta, bool xcd) {
+    const ConnSlot sl = conn_slot(b, ntiles, xcd);
+    return {sl.unit / npairs, (int)(sl.unit % npairs), sl.tile / nta, sl.tile % nta};
+}
+constexpr int64_t pac_blocks(int64_t ec, int64_t npairs, int64_t ntiles, bool xcd) {
+    return ntiles > 0x7fffffff ? -1 : conn_blocks(ec * npairs, (int)ntiles, xcd);
+}
+static_assert(pac_tiles_ph(8) == 1 && pac_tiles_ph(9) == 2 && pac_tiles_am(16) == 1 && pac_tiles_am(17) == 2 &&
+                  pac_tiles(9, 17) == 4 && pac_tiles(0, 5) == 0,
+              "scale tile counts");
+static_assert(pac_blocks(2, 5, 4, false) == 40 && pac_blocks(2, 5, 4, true) == 64 && pac_blocks(0, 5, 4, true) == 0,
+              "block count");
 
 // ---- the two-pass engine (nw_large.hip) -----------------------------------------------------
 

@@ -38,6 +38,8 @@ CONN_OUTS = {'cross_sum': 'cross_sum', 'plv_sum': 'plv_sum', 'csd': 'cross_sum',
 LAG_KINDS = {'lag_sum': L.NW_OUT_LAG_SUM}
 LAG_OUTS = {'lag_sum': 'lag_sum', 'pli': 'lag_sum', 'pli2_unbiased': 'lag_sum', 'dpli': 'lag_sum',
             'wpli': 'lag_sum', 'wpli2_debiased': 'lag_sum', 'ciplv': 'plv_sum', 'ppc': 'plv_sum'}
+# phase-amplitude coupling (Plan.execute_pac): what finalize_pac forms from its sums (M, amp, phase)
+PAC_OUTS = {'pac_sum', 'mvl', 'mvl_norm', 'direct_pac', 'debiased_pac'}
 KINDS = {'morse': L.NW_MORSE, 'morlet': L.NW_MORLET, 'shannon': L.NW_SHANNON, 'table': L.NW_TABLE,
          # WaveletMode.Normal tables built on the device (base.py:249-256)
          'mexican_hat': L.NW_MEXICAN_HAT, 'haar': L.NW_HAAR}
@@ -236,6 +238,65 @@ def finalize_conn_time(kind: str, sums, power, ia, ib, nsamples: int):
             four = np.stack([sums[:, p].real, sums[:, p].imag, power[:, ia[p]], power[:, ib[p]]], axis=-1)
             out[:, p] = finalize_pair(kind, four, T)
     return out
+
+
+def check_pac_indices(indices, nchan: int):
+    """The pair list of the phase-amplitude calls: ``indices`` = (ip, ia), the phase and the amplitude
+    channel of each pair, checked as check_indices checks its lists; None: every channel with itself."""
+    if indices is None:
+        own = np.arange(int(nchan), dtype=np.int32)
+        return own, own.copy()
+    return check_indices(indices, nchan)
+
+
+def check_scales(name: str, positions, nfreq: int) -> np.ndarray:
+    """``positions``, a non-empty 1-D list of integer positions in [0, nfreq) into a plan's scale list
+    (any list: repeats, any order), as a contiguous int32 array; ValueError naming ``name`` otherwise."""
+    try:
+        pos = np.asarray(positions)
+    except (TypeError, ValueError):
+        raise ValueError(f'{name} must be a list of scale positions, got {positions!r}') from None
+    if pos.ndim != 1 or pos.size == 0:
+        raise ValueError(f'{name} must be a non-empty 1-D list of scale positions, got shape {pos.shape}')
+    if not np.issubdtype(pos.dtype, np.integer):
+        raise ValueError(f'{name} must hold integer scale positions, got {pos.dtype}')
+    if pos.min() < 0 or pos.max() >= nfreq:
+        raise ValueError(f'{name} positions must lie in [0, {nfreq}): got {int(pos.min())} .. {int(pos.max())}')
+    return np.ascontiguousarray(pos, dtype=np.int32)
+
+
+def finalize_pac(kind: str, M, amp, phase, ip, ia, nsamples: int):
+    """The phase-amplitude coupling measure ``kind`` per epoch, pair and (phase scale, amplitude scale)
+    from the sums of Plan.execute_pac over T = ``nsamples`` window samples: ``M`` complex128
+    (E, P, Fp, Fa) = sum A u, ``amp`` float64 (E, C, Fa, 2) = {sum A, sum A^2} and ``phase`` complex128
+    (E, C, Fp) = sum u, with A the amplitude of channel ia[p] and u the unit phasor of channel ip[p]:
+      mvl           |M| / T                              (Canolty et al. 2006)
+      mvl_norm      |M| / sum A
+      direct_pac    |M| / sqrt(T sum A^2)                (Ozkurt & Schnitzler 2011)
+      debiased_pac  |M - (sum u)(sum A) / T| / T         (van Driel et al. 2015)
+    float64 (E, P, Fp, Fa); a zero denominator gives 0, not NaN (the wpli convention).  ``pac_sum``
+    returns (M, amp, phase) unchanged.  The finalised kinds need T >= 1 (ValueError)."""
+    if kind not in PAC_OUTS:
+        raise ValueError(f"out must be one of {', '.join(sorted(PAC_OUTS))}; got {kind!r}")
+    if kind == 'pac_sum':
+        return M, amp, phase
+    T = int(nsamples)
+    if T < 1:
+        raise ValueError(f'{kind} needs at least 1 sample in the window, got {T}')
+    M = np.asarray(M, dtype=np.complex128)
+    if M.ndim != 4:
+        raise ValueError(f'M must be (epochs, pairs, phase scales, amplitude scales), got shape {M.shape}')
+    ip, ia = np.asarray(ip, dtype=np.intp), np.asarray(ia, dtype=np.intp)
+    if kind == 'mvl':
+        return np.abs(M) / T
+    amp = np.asarray(amp, dtype=np.float64)
+    if kind == 'debiased_pac':
+        phase = np.asarray(phase, dtype=np.complex128)
+        return np.abs(M - phase[:, ip][:, :, :, None] * amp[:, ia][:, :, None, :, 0] / T) / T
+    den = amp[:, ia][:, :, None, :, 0] if kind == 'mvl_norm' else np.sqrt(T * amp[:, ia][:, :, None, :, 1])
+    den = np.broadcast_to(den, M.shape)
+    zero = den == 0
+    return np.where(zero, 0., np.abs(M) / np.where(zero, 1., den))
 
 
 def time_window(n: int, decim: int, window, on_device: bool):
@@ -751,6 +812,85 @@ class Plan:
                                              sums.ctypes.data_as(P), None if plv else power.ctypes.data_as(P), kind,
                                              L.NW_MEM_HOST))
         return sums if plv else (sums, power)
+
+    def execute_pac(self, x, indices=None, phase=None, amp=None, window=None, step: int = 1, out=None):
+        """Phase-amplitude coupling sums (nw_execute_pac): x (E, C, n) as in execute_conn_time, every
+        signal transformed once and reduced on the device along the samples t0, t0 + step, ... < t1 of
+        ``window`` (the plan's OUTPUT samples; None: (0, n_out)).  ``indices`` = (ip, ia): the phase and
+        the amplitude channel of each pair (None: every channel with itself); ``phase`` / ``amp``:
+        positions into the plan's scale list (any lists: repeats, a scale in both).  Returns (M
+        complex128 (E, P, Fp, Fa) = sum |y_a| u_p, amp float64 (E, C, Fa, 2) = {sum |y|, sum |y|^2}, phase
+        complex128 (E, C, Fp) = sum u); see finalize_pac.  numpy arrays: synchronous, ``out`` optional.
+        Device tensors: asynchronous on the plan stream, ``out`` = (M, amp, phase) required (amp and
+        phase may be None: not formed).  The plan needs max_batch >= C."""
+        import operator
+        if getattr(x, 'ndim', 0) != 3:
+            raise ValueError(f'x must be (epochs, channels, n), got shape {tuple(getattr(x, "shape", ()))}')
+        nep, nchan = int(x.shape[0]), int(x.shape[1])
+        ip, ia = check_pac_indices(indices, nchan)
+        npairs = int(ip.size)
+        fph, fam = check_scales('phase', phase, self.nfreq), check_scales('amp', amp, self.nfreq)
+        nph, nam = int(fph.size), int(fam.size)
+        try:
+            t0, t1 = (0, self.n_out) if window is None else window
+            t0, t1, step = operator.index(t0), operator.index(t1), operator.index(step)
+        except (TypeError, ValueError):
+            raise ValueError(f'window must be a pair (t0, t1) of integers and step an integer, got {window!r} and '
+                             f'{step!r}') from None
+        if step < 1:
+            raise ValueError(f'step must be >= 1, got {step}')
+        if not 0 <= t0 <= t1 <= self.n_out:
+            raise ValueError(f'window must satisfy 0 <= t0 <= t1 <= n_out = {self.n_out}, got ({t0}, {t1})')
+        P = ctypes.c_void_p
+        lists = (ip.ctypes.data_as(P), ia.ctypes.data_as(P), npairs, fph.ctypes.data_as(P), nph, fam.ctypes.data_as(P),
+                 nam, t0, t1, step)
+        shapes = (((nep, npairs, nph, nam), np.complex128), ((nep, nchan, nam, 2), np.float64),
+                  ((nep, nchan, nph), np.complex128))
+        if _is_device_tensor(x):
+            import torch
+            if out is None:
+                raise ValueError('device execute needs output tensors')
+            if self._check_device_input(x) != nep * nchan:
+                raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
+            try:
+                tm, ta, tp = out
+            except (TypeError, ValueError):
+                raise ValueError('device output must be (M, amp, phase) tensors (amp and phase may be None)') from None
+            for t, (shape, dt), name in zip((tm, ta, tp), shapes, ('M', 'amp', 'phase')):
+                if t is None and name != 'M':
+                    continue
+                dt = torch.complex128 if dt is np.complex128 else torch.float64
+                if not _is_device_tensor(t) or t.dtype != dt:
+                    raise ValueError(f'device output {name} must be a {dt} tensor on device {self.device}')
+                if not t.is_contiguous() or t.numel() != int(np.prod(shape)):
+                    raise ValueError(f'device output {name} must be contiguous and hold {int(np.prod(shape))} values')
+                if t.device.index != self.device:
+                    raise ValueError(f'device buffers must live on device {self.device}')
+            with self._ordered_with_torch(x.device):
+                L.check(L.lib().nw_execute_pac(self._h, P(x.data_ptr()), nep, nchan, *lists, P(tm.data_ptr()),
+                                               P(ta.data_ptr()) if ta is not None else None,
+                                               P(tp.data_ptr()) if tp is not None else None, L.NW_MEM_DEVICE))
+            return out
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        if x.shape[-1] != self.n:
+            raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
+        if out is None:
+            out = (None, None, None)
+        try:
+            outs = list(out)
+            if len(outs) != 3:
+                raise TypeError
+        except TypeError:
+            raise ValueError('out must be (M, amp, phase) arrays') from None
+        for k, (shape, dt) in enumerate(shapes):
+            if outs[k] is None:
+                outs[k] = np.empty(shape, dtype=dt)
+            a = outs[k]
+            if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or a.size != int(np.prod(shape)):
+                raise ValueError('out must be C-contiguous arrays of the right dtype and size')
+        L.check(L.lib().nw_execute_pac(self._h, x.ctypes.data_as(P), nep, nchan, *lists,
+                                       *(a.ctypes.data_as(P) for a in outs), L.NW_MEM_HOST))
+        return tuple(outs)
 
     def stream_ptr(self) -> int:
         """The hipStream_t the plan launches on."""

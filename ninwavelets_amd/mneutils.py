@@ -118,6 +118,28 @@ class EpochsWavelet:
         return self.wavelet.connectivity_time_batch(waves, freqs, reuse=True, out=method, indices=indices,
                                                     window=(k, n - k), decim=decim, average=average)
 
+    # -- phase-amplitude coupling: one comodulogram per epoch and pair (WaveletBase.pac_batch) ------
+    def pac(self, ch_names, phase_freqs, amp_freqs, method: str = 'direct_pac', indices=None, padding: float = 0.,
+            decim: int = 1, average: bool = False):
+        """``method`` (pac_batch's outs: mvl, mvl_norm, direct_pac, debiased_pac, pac_sum) between the
+        phase at ``phase_freqs`` and the amplitude at ``amp_freqs``, (E, P, Fp, Fa): the concatenated
+        frequency list is transformed once.  ``indices`` = (phase channels, amplitude channels),
+        positions in ``ch_names`` (default: every channel with itself); ``padding`` as in
+        connectivity_time; ``average=True``: the mean over the epochs, (P, Fp, Fa)."""
+        ch_names = list(ch_names)
+        idx = [self.epochs.ch_names.index(c) for c in ch_names]
+        waves = self.epochs.get_data()[:, idx, :]
+        n = waves.shape[-1]
+        if not padding >= 0:
+            raise ValueError(f'padding must be >= 0 seconds, got {padding!r}')
+        k = int(round(padding * self.epochs.info['sfreq']))
+        if k >= n - k:
+            raise ValueError(f'padding of {padding} s ({k} samples on each side) leaves no sample of the {n}')
+        pf, af = list(phase_freqs), list(amp_freqs)
+        return self.wavelet.pac_batch(waves, pf + af, reuse=False, phase=np.arange(len(pf)),
+                                      amp=np.arange(len(pf), len(pf) + len(af)), out=method, indices=indices,
+                                      window=(k, n - k), decim=decim, average=average)
+
     # -- connectivity between many channels: one transform per epoch and channel, every pair's
     #    sums from it (WaveletBase.connectivity_batch; no reference counterpart) ---------------
     def connectivity(self, ch_names, freqs, method: str = 'coherence', indices=None, decim: int = 1):
