@@ -276,6 +276,9 @@ struct nw_plan {
     DevBuf d_wtab;                   // fused engine: W[f, k] (pad_to + 1/n applied); n > 16384: kmax[f]
     bool wtab_valid = false;
     int64_t chirp_counts[5] = {0, 0, 0, 0, 0};   // rows per M class (M = 1024 << c)
+    // execute_reduce, chirp-z partial sums: the chunk being run continues the signal group of the
+    // one before it, whose partial row the kernel adds to (chirp_psum_chunk, nw_shape.h)
+    bool chirp_carry = false;
     // chirp-z rows of a tentative length wider than the largest on-chip transform: computed
     // by the rocFFT path on a view of just those rows into d_oscr and scattered to their
     // scales (k_expand_rows), the other rows stay on chip
@@ -750,7 +753,12 @@ int run_chirp(nw_plan* p, const nw::WDesc& d, const void* xs_dev, int64_t c, voi
     p->stats.kernel = NW_K_CHIRP;
     NW_TRY(NW_KERNEL_STAGE(p, ST_FUSED, false,
                            nw::launch_chirp(d, p->dtype, out_kind, p->d_X.ptr, p->d_wtab.ptr, dst, c, p->chirp_counts,
-                                            p->stream)));
+                                            p->chirp_carry, p->stream)));
+    // launches_fused counts kernel launches: launch_chirp made one per M class that holds rows,
+    // the stage counted one
+    int64_t classes = 0;
+    for (int64_t cnt : p->chirp_counts) classes += cnt != 0;
+    if (classes > 1) p->stats.launches_fused += classes - 1;
     return p->over.U ? run_overflow_rows(p, d.nfreq, c, dst, out_kind) : NW_OK;
 }
 
@@ -835,8 +843,11 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
         NW_TRY(p->d_out.ensure(sb));
         scratch = p->d_out.ptr;
     }
-    for (int64_t s0 = 0; s0 < nsig; s0 += p->max_batch) {
-        const int64_t c = std::min<int64_t>(p->max_batch, nsig - s0);
+    // The chirp-z partial rows are those of the call's signal groups 0-7, 8-15, ... whatever
+    // max_batch (chirp_psum_chunk), so the sums do not depend on it: a chunk shorter than a group
+    // carries the group's row on, and the row is added once the group is complete.
+    for (int64_t s0 = 0, c = 0; s0 < nsig; s0 += c) {
+        c = chirp_psum ? nw::chirp_psum_chunk(s0, nsig, p->max_batch) : std::min<int64_t>(p->max_batch, nsig - s0);
         const void* xs = (const char*)x + (size_t)s0 * p->n * p->esz;
         if (host) {
             NW_TRY(staged(p, ST_COPY, [&] {
@@ -845,13 +856,17 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
             }));
             xs = p->d_x.ptr;
         }
-        NW_TRY(run_chunk(p, d, xs, c, scratch, sig_kind, false));
+        p->chirp_carry = chirp_psum && s0 % nw::kPsumGroup != 0;
+        const int rc = run_chunk(p, d, xs, c, scratch, sig_kind, false);
+        p->chirp_carry = false;
+        NW_TRY(rc);
+        p->stats.chunks++;
+        if (chirp_psum && (s0 + c) % nw::kPsumGroup != 0 && s0 + c < nsig) continue;   // the group goes on
         const int64_t rows = psum ? nw::fused_psum_groups(c) : c;
         // chained: run_chunk ends with a stage
         NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, true,
                                nw::launch_accumulate(psum ? NW_F64 : p->dtype, src_kind, scratch, acc,
                                                      psum && phase ? 2 * fn : fn, rows, p->stream)));
-        p->stats.chunks++;
     }
     const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (out_kind == NW_OUT_POWER_SUM || out_kind == NW_OUT_PHASE_SUM) {

@@ -120,7 +120,7 @@ template <typename T, int M, int E, int OUT, bool REALW>
 __global__ __launch_bounds__(M / E, (kChirpWps<T, M, E, OUT>)) void nw_chirp_kernel(
     WDesc d, const cplx<T>* __restrict__ X, const void* __restrict__ wtab, void* __restrict__ out,
     const C2<T>* __restrict__ tw, const C2<T>* __restrict__ bh, const C2<T>* __restrict__ ct, int64_t nsig,
-    int nsg_pad, const int* __restrict__ rowmap, int nrows, const int* __restrict__ ksup) {
+    int nsg_pad, const int* __restrict__ rowmap, int nrows, const int* __restrict__ ksup, int carry) {
     using G = Geometry<M, E>;
     constexpr int TT = G::T;
     constexpr int LP = G::npass() - 1;
@@ -196,11 +196,13 @@ __global__ __launch_bounds__(M / E, (kChirpWps<T, M, E, OUT>)) void nw_chirp_ker
         O* orow = reinterpret_cast<O*>(out) + (s * d.nfreq + fi) * (int64_t)n;
         // epoch partial sums (kOutPSum / kOutPhSum): the block's fp64 row (group sg, scale fi)
         // of the (groups, F, n) partial buffer, read-modify-written by the lane that owns each
-        // point (the same lane for every signal), in signal order -- no accumulator registers
+        // point (the same lane for every signal), in signal order -- no accumulator registers.
+        // carry: the launch continues the signal group of the one before it (a chunk shorter than
+        // a group: chirp_psum_chunk, nw_shape.h), whose partial row it adds to
         constexpr bool PS = OUT == kOutPSum || OUT == kOutPhSum;
         constexpr int NACC = OUT == kOutPhSum ? 2 : 1;
         double* prow = reinterpret_cast<double*>(out) + ((int64_t)sg * d.nfreq + fi) * (int64_t)n * NACC;
-        const bool first = s == s_begin;
+        const bool first = s == s_begin && !carry;
 #pragma unroll
         for (int q = 0; q < IL::Q; ++q) {
             // outputs n_j = n0 + j*NS in natural j order (register i = bitrev(j)); |y| and
@@ -363,7 +365,7 @@ hipError_t chirp_tables(int64_t n, int64_t m, int dtype, void** out) {
 
 template <typename T, int M, int E, bool REALW>
 hipError_t launch_m_e(const WDesc& d, int out_kind, const void* X, const void* wtab, void* out, int64_t nsig,
-                      const int* rowmap, int nrows, const int* ksup, hipStream_t s) {
+                      const int* rowmap, int nrows, const int* ksup, bool carry, hipStream_t s) {
     constexpr int threads = M / E;
     const int lds = kLdsBytes<T, M, E>;
     void* tw = nullptr;
@@ -380,7 +382,7 @@ hipError_t launch_m_e(const WDesc& d, int out_kind, const void* X, const void* w
     const C2<T>* twc = reinterpret_cast<const C2<T>*>(tw);
     auto go = [&](auto kern) {
         return nw_launch_lds(kern, (unsigned)g.blocks, threads, lds, s, d, Xc, wtab, out, twc, bh, ct, nsig,
-                             (int)g.groups_pad, rowmap, nrows, ksup);
+                             (int)g.groups_pad, rowmap, nrows, ksup, (int)carry);
     };
     if (out_kind == kOutPSum || out_kind == kOutPhSum) {
         // partial sums at E = 16 only (chirp_psum_ok: the classes whose kernels do not spill)
@@ -396,13 +398,13 @@ hipError_t launch_m_e(const WDesc& d, int out_kind, const void* X, const void* w
 // |y| and |y|^2 at kChirpAbsE (nw_shape.h: E = 32 at fp32 M = 8192), the other kinds at E
 template <typename T, int M, int E, bool REALW>
 hipError_t launch_m(const WDesc& d, int out_kind, const void* X, const void* wtab, void* out, int64_t nsig,
-                    const int* rowmap, int nrows, const int* ksup, hipStream_t s) {
+                    const int* rowmap, int nrows, const int* ksup, bool carry, hipStream_t s) {
     constexpr int EP = kChirpAbsE<T, M, E>;
     if constexpr (EP != E) {
         if (out_kind == NW_OUT_POWER || out_kind == NW_OUT_ABS)
-            return launch_m_e<T, M, EP, REALW>(d, out_kind, X, wtab, out, nsig, rowmap, nrows, ksup, s);
+            return launch_m_e<T, M, EP, REALW>(d, out_kind, X, wtab, out, nsig, rowmap, nrows, ksup, carry, s);
     }
-    return launch_m_e<T, M, E, REALW>(d, out_kind, X, wtab, out, nsig, rowmap, nrows, ksup, s);
+    return launch_m_e<T, M, E, REALW>(d, out_kind, X, wtab, out, nsig, rowmap, nrows, ksup, carry, s);
 }
 
 }  // namespace
@@ -459,8 +461,10 @@ hipError_t build_chirp_wtable(const WDesc& d, int dtype, void* wtab, hipStream_t
 }
 
 hipError_t launch_chirp(const WDesc& d, int dtype, int out_kind, const void* X, const void* wtab, void* out,
-                        int64_t nsig, const int64_t* counts, hipStream_t s) {
+                        int64_t nsig, const int64_t* counts, bool carry, hipStream_t s) {
     if (!chirp_possible(d.n, dtype)) return hipErrorNotSupported;
+    // a carried partial row is the one group of a chunk inside a signal group
+    if (carry && (nsig > kGroupC || (out_kind != kOutPSum && out_kind != kOutPhSum))) return hipErrorInvalidValue;
     const int* ksup = reinterpret_cast<const int*>(reinterpret_cast<const char*>(wtab) +
                                                    chirp_w_bytes(d.n, d.nfreq, dtype, d.kind));
     const int* rowmap = ksup + d.nfreq;
@@ -472,7 +476,7 @@ hipError_t launch_chirp(const WDesc& d, int dtype, int out_kind, const void* X, 
                                             [&]<typename T, int M, int E>(ChirpSize<T, M, E>) {
             return for_bool(d.kind != NW_TABLE, [&](auto rw) {
                 return launch_m<T, M, E, decltype(rw)::value>(d, out_kind, X, wtab, out, nsig, rowmap + off, (int)cnt,
-                                                               ksup, s);
+                                                               ksup, carry, s);
             });
         });
         if (e != hipSuccess) return e;

@@ -365,8 +365,9 @@ size_t     chirp_wtable_bytes(int64_t n, int nfreq, int dtype, int kind);
 // false and (overflow non-null) their indices are listed; counts[] covers the others
 hipError_t build_chirp_wtable(const WDesc& d, int dtype, void* wtab, hipStream_t s, int64_t* counts, bool* fits,
                               std::vector<int>* overflow);
+// carry (partial sums, nsig <= kPsumGroup): add to the partial row the launch before left in `out`
 hipError_t launch_chirp(const WDesc& d, int dtype, int out_kind, const void* X, const void* wtab, void* out,
-                        int64_t nsig, const int64_t* counts, hipStream_t s);
+                        int64_t nsig, const int64_t* counts, bool carry, hipStream_t s);
 
 // two-pass engine for long signals (nw_large.hip): power-of-two 2^15 <= n <= 2^24, fp32 or
 // fp64.  scratch = Xt (n complex) + B (large_fchunk scales x n complex); support = kmax[nfreq]

@@ -658,5 +658,24 @@ constexpr bool chirp_psum_ok(int dtype, bool phase, const int64_t* counts) {
     }
     return true;
 }
+// The chunk of such a reduction that starts at signal s0 of nsig (chunks of at most max_batch >= 1
+// signals).  The kernel sums a block's signals in order into one partial row and the rows are added
+// in order, so for the sums not to depend on max_batch the blocks must be the groups
+// kPsumGroup g .. kPsumGroup g + kPsumGroup - 1 of the whole call: a chunk is whole groups (the
+// call's last one ragged) or, where max_batch is shorter than a group, lies inside one group,
+// whose partial row the next chunk carries on (s0 % kPsumGroup != 0) and which is added once
+// complete.
+constexpr int64_t chirp_psum_chunk(int64_t s0, int64_t nsig, int64_t max_batch) {
+    const int64_t left = nsig - s0, in_group = s0 % kPsumGroup;
+    if (in_group == 0 && left <= max_batch) return left;
+    if (in_group == 0 && max_batch >= kPsumGroup) return max_batch / kPsumGroup * kPsumGroup;
+    const int64_t to_end = kPsumGroup - in_group;
+    const int64_t c = max_batch < to_end ? max_batch : to_end;
+    return c < left ? c : left;
+}
+static_assert(chirp_psum_chunk(0, 11, 11) == 11 && chirp_psum_chunk(0, 30, 11) == 8 && chirp_psum_chunk(24, 30, 11) == 6 &&
+                  chirp_psum_chunk(0, 11, 4) == 4 && chirp_psum_chunk(8, 11, 4) == 3 && chirp_psum_chunk(6, 19, 3) == 2 &&
+                  chirp_psum_chunk(16, 17, 3) == 1,
+              "chunks of the chirp-z partial sums");
 
 }  // namespace nw

@@ -6,6 +6,8 @@
 //                         two-pass splits and grids, the chirp-z lengths and M classes
 //   host_asan large     : the two-pass rules (split, row E, pass-0 ladder, rows per block, need,
 //                         LDS-DMA rule) per dtype, n and row kind, one line each
+//   host_asan chirp     : the chirp-z rules (lengths, a row's M class around every class boundary,
+//                         E per dtype, M and output, partial sums per class), one line each
 //   host_asan grid      : stdin "real_length sfreq interpolate" -> "len_valid len_full delta"
 //   host_asan shapes    : the size table's rules (E, pass-0 ladders, support rounding, partial
 //                         sums, decimated lengths), one line each
@@ -376,6 +378,23 @@ static void chirp_checks() {
     const int64_t one_big[kChirpClasses] = {0, 0, 0, 0, 1}, small[kChirpClasses] = {3, 1, 0, 0, 0}, mid[kChirpClasses] = {0, 0, 1, 1, 0};
     CHECK(!chirp_psum_ok(NW_F32, false, one_big) && chirp_psum_ok(NW_F32, true, mid) && chirp_psum_ok(NW_F64, false, mid));
     CHECK(!chirp_psum_ok(NW_F64, true, mid) && chirp_psum_ok(NW_F64, true, small));
+    // chirp_psum_chunk: the chunks tile the call, none longer than max_batch, and each is whole
+    // signal groups from a group's start (only the call's last group ragged) or lies inside one group
+    for (int64_t nsig = 0; nsig <= 70; ++nsig)
+        for (int64_t mb = 1; mb <= 40; ++mb) {
+            int64_t s0 = 0;
+            while (s0 < nsig) {
+                const int64_t c = chirp_psum_chunk(s0, nsig, mb);
+                CHECK(c >= 1 && c <= mb && s0 + c <= nsig);
+                if (c < 1) break;
+                const bool whole = s0 % kPsumGroup == 0 && (c % kPsumGroup == 0 || s0 + c == nsig);
+                const bool inside = s0 / kPsumGroup == (s0 + c - 1) / kPsumGroup;
+                CHECK(whole || inside);
+                CHECK(mb < kPsumGroup || whole);
+                s0 += c;
+            }
+            CHECK(s0 == nsig);
+        }
 }
 
 static const char* out_name(int out) { return out == NW_OUT_CWT ? "cwt" : out == NW_OUT_POWER ? "power" : "abs"; }
@@ -471,10 +490,58 @@ static void print_large() {
             });
 }
 
+// the chirp-z rules, one line each, for tests/test_host_asan.py to compare with
+// tests/chirp_variants.py
+static const int64_t kChirpLengths[] = {1, 300, 511, 513, 712, 1201, 2047, 2049, 4095, 4096, 4097, 8191, 8193, 14001, 16383};
+static void print_chirp() {
+    using namespace nw;
+    for (int dtype : {NW_F32, NW_F64}) {
+        const char* dt = dtype == NW_F32 ? "float32" : "float64";
+        for (int64_t n : kChirpLengths) {
+            std::printf("len %s %lld supported %d possible %d m %lld\n", dt, (long long)n, (int)chirp_supported(n, dtype),
+                        (int)chirp_possible(n, dtype), (long long)chirp_m(n));
+            // K = 0, 1, 2, 3, n / 2, n - 1, n and the K either side of every class boundary
+            // (2K <= M and n + K - 1 <= M), ascending
+            std::vector<int64_t> ks = {0, 1, 2, 3, n / 2, n - 1, n};
+            for (int c = 0; c < kChirpClasses; ++c) {
+                const int64_t m = int64_t(1024) << c;
+                for (int64_t k : {m / 2, m / 2 + 1, m - n + 1, m - n + 2}) ks.push_back(k);
+            }
+            std::sort(ks.begin(), ks.end());
+            ks.erase(std::unique(ks.begin(), ks.end()), ks.end());
+            std::printf("class %s %lld", dt, (long long)n);
+            for (int64_t k : ks) {
+                if (k < 0 || k > n) continue;
+                const int c = chirp_class(n, k, dtype);
+                std::printf(" %lld:%lld", (long long)k, c < 0 ? -1LL : (long long)(int64_t(1024) << c));
+            }
+            std::printf("\n");
+        }
+        for (int c = 0; c < kChirpClasses; ++c) {
+            const int64_t m = int64_t(1024) << c;
+            const int abs_e = for_chirp_size(m, dtype, 0, []<typename T, int M, int E>(ChirpSize<T, M, E>) {
+                return (int)kChirpAbsE<T, M, E>;
+            });
+            std::printf("e %s %lld %d abs %d\n", dt, (long long)m, chirp_e(m, dtype), abs_e);
+        }
+        for (int phase = 0; phase < 2; ++phase)
+            for (int c = 0; c < kChirpClasses; ++c) {
+                int64_t counts[kChirpClasses] = {0, 0, 0, 0, 0};
+                counts[c] = 1;
+                std::printf("psum %s %s %lld %d\n", dt, phase ? "phase" : "power", (long long)(int64_t(1024) << c),
+                            (int)chirp_psum_ok(dtype, phase != 0, counts));
+            }
+    }
+}
+
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "self";
     if (mode == "large") {
         print_large();
+        return 0;
+    }
+    if (mode == "chirp") {
+        print_chirp();
         return 0;
     }
     if (mode == "shapes") {

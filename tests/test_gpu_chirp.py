@@ -9,10 +9,13 @@ Tolerances against the fp64 oracle (numpy + scipy.fftpack, the reference's arith
 fp64 1e-12 of max|ref| (|.|^2 twice that), fp32 2e-5 (the chirp factors and two M-point
 FFTs add round-off over the power-of-two kernels' 1e-5; |.|^2 twice that), plus the 1e-30
 floor for outputs below fp32 range (test_gpu_parity.py).
+
+Per row, at every transform size, pass-0 variant and corner of chirp_class: tests/test_gpu_chirp_rows.py.
 """
 import numpy as np
 import pytest
 
+import chirp_variants as V
 from oracle import nw_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -62,7 +65,12 @@ def test_chirp_lengths_against_oracle(dtype, n):
         ref = oracle('morse', x, freqs, out)
         assert within(got, ref, dtype, out), (out, np.max(np.abs(got - ref)) / np.max(np.abs(ref)))
     st = p.stats()
-    assert st['engine'] == 'fused' and st['launches_fused'] == 3 * 1 and st['launches_multiply'] == 0
+    # one launch per execute and transform size M that holds rows (n = 1000: the lowest rows, K <= 25,
+    # run at M = 1024 beside the others at 2048; every other length here has one M)
+    rows = O.fft_wavelets('morse', freqs, 1000., n / 1000., False)
+    sizes = {V.chirp_class(n, V.table_support(O.pad_to(r, n).astype(dtype)), dtype) for r in rows}
+    assert len(sizes) == (2 if n == 1000 else 1)
+    assert st['engine'] == 'fused' and st['launches_fused'] == 3 * len(sizes) and st['launches_multiply'] == 0
 
 
 @pytest.mark.parametrize('dtype', ['float32', 'float64'])

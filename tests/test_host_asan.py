@@ -119,6 +119,42 @@ def test_large_variants_matches_the_shape_header(host_asan):
         assert g == w
 
 
+CHIRP_LENGTHS = [1, 300, 511, 513, 712, 1201, 2047, 2049, 4095, 4096, 4097, 8191, 8193, 14001, 16383]   # kChirpLengths
+
+
+def test_chirp_variants_matches_the_shape_header(host_asan):
+    """tests/chirp_variants.py (chirp_m, chirp_supported / chirp_possible, chirp_class, chirp_e with
+    kChirpAbsE, psum_ok: the rules the GPU tests use to steer rows of the chirp-z form into every
+    transform size) line by line against what nw_shape.h gives for both dtypes: every length of
+    CHIRP_LENGTHS with its M class at K = 0, 1, 2, 3, n / 2, n - 1, n and either side of every
+    class boundary, E per (dtype, M), and the partial-sum rule per single class."""
+    import chirp_variants as V
+    r = subprocess.run([host_asan, 'chirp'], capture_output=True, text=True, env=ENV, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    want = []
+    for dtype in ('float32', 'float64'):
+        for n in CHIRP_LENGTHS:
+            want.append(f'len {dtype} {n} supported {int(V.chirp_supported(n, dtype))} '
+                        f'possible {int(V.chirp_possible(n, dtype))} m {V.chirp_m(n)}')
+            ks = {0, 1, 2, 3, n // 2, n - 1, n}
+            for m in V.CLASSES:
+                ks |= {m // 2, m // 2 + 1, m - n + 1, m - n + 2}
+            want.append(f'class {dtype} {n} ' + ' '.join(f'{k}:{V.chirp_class(n, k, dtype)}'
+                                                         for k in sorted(ks) if 0 <= k <= n))
+        for m in V.CLASSES:
+            assert V.chirp_e(m, dtype, 'abs') == V.chirp_e(m, dtype, 'power')
+            want.append(f'e {dtype} {m} {V.chirp_e(m, dtype, "cwt")} abs {V.chirp_e(m, dtype, "abs")}')
+        for phase in (False, True):
+            for m in V.CLASSES:
+                want.append(f'psum {dtype} {"phase" if phase else "power"} {m} {int(V.psum_ok(dtype, phase, [m]))}')
+    got = r.stdout.splitlines()
+    assert len(got) == len(want) == 2 * (2 * len(CHIRP_LENGTHS) + 5 + 10)
+    for g, w in zip(got, want):
+        assert g == w
+    # the boundaries are really crossed: some length shows every class and the off-chip answer
+    assert all(any(f':{m}' in ln for ln in got if ln.startswith('class')) for m in V.CLASSES + [-1])
+
+
 def test_trans_grid_under_asan_matches_numpy(host_asan):
     """nw::host::trans_grid (the nw_trans_grid body) against numpy's arange length
     (base.py:191-194, 238-245) on random (N, sfreq, interpolate)."""
