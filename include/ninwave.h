@@ -162,6 +162,8 @@ typedef struct nw_stats {
 #define NW_REDUCE_PAC      5   /* nw_execute_pac: per-signal rows per chunk, every (epoch, pair,
                                   phase scale, amplitude scale) summed over the window by
                                   nw_pac_kernel                                                 */
+#define NW_REDUCE_ENV      6   /* nw_execute_env_time: per-signal rows per chunk, every (epoch,
+                                  pair, scale) summed over the window by nw_env_time_kernel    */
 
 /* nw_stats.kernel: which kernel wrote the output rows (the dominant kernel of a step) */
 #define NW_K_NONE        0
@@ -363,6 +365,37 @@ int nw_execute_pac(nw_plan* plan, const void* x, int64_t nepochs, int32_t nchan,
                    const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam,
                    int64_t t0, int64_t t1, int64_t step,
                    void* out_m, void* out_amp, void* out_phase, int mem);
+
+/* Envelope correlation (Hipp et al. 2012; mne-connectivity's envelope_correlation): per epoch, channel
+ * pair and scale the sums from which the Pearson correlation over time of two amplitude envelopes is
+ * formed, plain or with each signal first orthogonalised against the other sample by sample, reduced
+ * on the device along the samples of a window.  x, ia, ib, nchan, chunking (max_batch / nchan epochs,
+ * max_batch >= nchan), mem, every engine form, decimated plans, the window (t0, t1, step) in the
+ * plan's OUTPUT samples and T are nw_execute_conn_time's.  Per channel c and sample s_j, in fp64, with
+ * (re, im) the row value converted to double:
+ *   h = hypot(re, im),  A = h,  (ur, ui) = (re / h, im / h)
+ * (the unit phasor of NW_OUT_PLV_SUM and nw_execute_pac, NaN where |y| = 0).  Outputs are epoch-major:
+ * NW_ENV_PLAIN: out_pair float64 (nepochs, npairs, F)    = sum_j A_a A_b.
+ * NW_ENV_ORTH:  out_pair float64 (nepochs, npairs, F, 6) = {sum u, sum u u, sum u A_b,
+ *                                                           sum v, sum v v, sum v A_a} over j, with
+ *   s = ua_i ub_r + (-(ua_r ub_i)),  q = |s|,  u = A_a q,  v = A_b q:
+ *   u = |Im(y_a conj(y_b) / |y_b|)| is a orthogonalised against b, v is b against a.
+ * both:         out_chan float64 (nepochs, nchan, F, 2)  = {sum_j A, sum_j (re re + im im)} (may be NULL).
+ * Every product and every term is rounded on its own (no fma into a sum), and every sum runs in
+ * nw_execute_conn_time's SUMMATION ORDER, each of the six components on its own, so a result depends
+ * only on its two rows and on (t0, t1, step): not on the pair list, on its tiling or on how the epochs
+ * are chunked.  The first value of out_chan is bit-identical to nw_execute_pac's out_amp[..., 0] of the
+ * same row and window, the second to nw_execute_conn_time's out_power.  A sample with |y| = 0 in
+ * either row makes the NW_ENV_ORTH sums of that (epoch, pair, scale) NaN, as for NW_OUT_PLV_SUM.  A
+ * self pair a == b has s = 0 exactly, so its six sums are +0.0.
+ * nepochs = 0 or npairs = 0: empty outputs; t0 == t1: zero sums.  The sums of all epochs live in the
+ * plan (nw_stats.device_bytes); NW_E_NOMEM if they do not fit.  nw_stats.reduce_path: NW_REDUCE_ENV. */
+#define NW_ENV_PLAIN 0
+#define NW_ENV_ORTH  1
+int nw_execute_env_time(nw_plan* plan, const void* x, int64_t nepochs, int32_t nchan,
+                        const int32_t* ia, const int32_t* ib, int64_t npairs,
+                        int64_t t0, int64_t t1, int64_t step,
+                        void* out_pair, void* out_chan, int env_kind, int mem);
 
 /* Shard nsig host signals over nplans plans (one per device, identical config),
  * one host thread per plan; balanced contiguous blocks (nsig / nplans signals, one

@@ -13,10 +13,10 @@ from .base import WaveletBase, WaveletMode, pad_to, interpolate_alias
 from .wavelets import Morse, MorseMNE, Morlet, Haar, MexicanHat, Shannon
 from .mneutils import EpochsWavelet
 from .baseline import Baseline, baseline_of
-from .engine import Plan, execute_multi, execute_multi_device, finalize_lag, finalize_conn_time, finalize_pac
+from .engine import Plan, execute_multi, execute_multi_device, finalize_lag, finalize_conn_time, finalize_pac, finalize_env
 from . import _lib
 
 __all__ = ['Baseline', 'baseline_of', 'WaveletBase', 'WaveletMode', 'Morse', 'MorseMNE', 'Morlet', 'Haar', 'MexicanHat',
-           'Shannon', 'EpochsWavelet', 'Plan', 'execute_multi', 'execute_multi_device', 'finalize_lag', 'finalize_conn_time', 'finalize_pac', 'pad_to',
+           'Shannon', 'EpochsWavelet', 'Plan', 'execute_multi', 'execute_multi_device', 'finalize_lag', 'finalize_conn_time', 'finalize_pac', 'finalize_env', 'pad_to',
            'interpolate_alias']
 __version__ = '0.1.0'

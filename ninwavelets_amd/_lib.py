@@ -44,6 +44,8 @@ NW_REDUCE_NONE, NW_REDUCE_ROWS, NW_REDUCE_PARTIALS = 0, 1, 2   # nw_stats.reduce
 NW_REDUCE_CONN = 3                                              # ... of nw_execute_conn
 NW_REDUCE_CONN_TIME = 4                                         # ... of nw_execute_conn_time
 NW_REDUCE_PAC = 5                                               # ... of nw_execute_pac
+NW_REDUCE_ENV = 6                                               # ... of nw_execute_env_time
+NW_ENV_PLAIN, NW_ENV_ORTH = 0, 1                                # nw_execute_env_time's env_kind
 NW_MEM_HOST, NW_MEM_DEVICE = 0, 1
 # nw_stats.kernel -> the kernel name rocprofv3 shows
 KERNEL_NAMES = {0: None, 1: 'nw_fused_kernel', 2: 'nw_fused_pair_kernel', 3: 'nw_chirp_kernel',
@@ -101,6 +103,8 @@ SIGNATURES = [
     ('nw_conn_time_count', ctypes.c_int, [_I64, _I64, _I64, _I64, ctypes.POINTER(_I64)]),
     ('nw_execute_conn_time', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _I64, _I64, _I64, _P, _P,
                                             ctypes.c_int, ctypes.c_int]),
+    ('nw_execute_env_time', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _I64, _I64, _I64, _P, _P,
+                                           ctypes.c_int, ctypes.c_int]),
     ('nw_execute_pac', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _P, ctypes.c_int32, _P, ctypes.c_int32,
                                       _I64, _I64, _I64, _P, _P, _P, ctypes.c_int]),
     ('nw_execute_multi',ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _I64, _P, ctypes.c_int]),

@@ -26,8 +26,9 @@ import numpy as np
 from scipy.fftpack import fft, ifft
 
 from . import _lib as L
-from .engine import (CONN_OUTS, LAG_OUTS, PAC_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim, check_indices,
-                     check_pac_indices, check_scales, execute_multi, finalize_conn, finalize_conn_time, finalize_lag,
+from .engine import (CONN_OUTS, ENV_OUTS, LAG_OUTS, PAC_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim, check_indices,
+                     check_pac_indices, check_scales, execute_multi, finalize_conn, finalize_conn_time, finalize_env,
+                     finalize_lag,
                      finalize_pac, finalize_pair, np_dtype, time_window)
 from .engine import make_wavelets as _make_wavelets_dev
 
@@ -630,6 +631,47 @@ class WaveletBase:
                 self._evict_plans(keep=1)
         sums, power = sums if need == 'cross_sum' else (sums, None)
         res = finalize_conn_time(out, sums, power, ia, ib, count)
+        return res.mean(axis=0) if average else res
+
+    def envelope_correlation_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, out: str = 'aec_orth',
+                                   indices=None, window=None, decim: int = 1, average: bool = False):
+        """Envelope correlation of ``waves`` (E, C, N) (Hipp et al. 2012; mne-connectivity's
+        envelope_correlation): per epoch, pair and scale the Pearson correlation over time of the two
+        channels' amplitude envelopes |cwt|, (E, P, F) float64.  Every signal is transformed once and
+        reduced on the device; the (E, C, F, N) rows never leave it.  ``out`` (engine.finalize_env):
+        ``aec_orth`` (mne's default: each signal orthogonalised against the other sample by sample, so
+        that zero-lag field spread gives no correlation; the mean of the two directions' |r|),
+        ``aec_orth_signed`` (absolute=False), ``aec_directed`` ((E, P, F, 2): both directions), ``aec``
+        (no orthogonalisation); ``env_sum`` / ``env_orth_sum`` return the sums (pair, chan).
+        ``window``, ``decim`` and ``average`` (the mean over the epochs, (P, F); ValueError for the
+        ``*_sum`` kinds) as in connectivity_time_batch; the finalised kinds need T >= 2 window samples.
+        Pair lists, cache semantics, device choice and plan eviction as in connectivity_batch."""
+        decim = check_decim(decim)
+        if out not in ENV_OUTS:
+            raise ValueError(f"out must be one of {', '.join(ENV_OUTS)}; got {out!r}")
+        if average and out.endswith('_sum'):
+            raise ValueError(f'average=True takes a finalised measure, not the sums {out!r}')
+        waves = np.asarray(waves)
+        if waves.ndim != 3:
+            raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
+        nep, nchan, n = waves.shape
+        ia, ib = check_indices(indices, nchan)
+        count = time_window(n, decim, window, False)[3]     # the same count on either kind of plan
+        if not out.endswith('_sum') and count < 2:
+            raise ValueError(f'{out} needs at least 2 samples in the window, got {count}')
+        if (not reuse) or self._cache is None:
+            self._build_cache(freqs, n / self.sfreq)
+        on_device = self._device_decim(n, decim)
+        t0, t1, step, count = time_window(n, decim, window, on_device)
+        self._used = 1
+        try:
+            plan = self._plan(n, nep * nchan, (self.devices or [self.device])[0],
+                              decim=decim if on_device else 1, min_batch=nchan)
+            pair, chan = plan.execute_env_time(waves, (ia, ib), (t0, t1), step, out_kind=ENV_OUTS[out])
+        finally:
+            if len(self._plans) > 1:
+                self._evict_plans(keep=1)
+        res = finalize_env(out, pair, chan, ia, ib, count)
         return res.mean(axis=0) if average else res
 
     def pac_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, phase=None, amp=None,

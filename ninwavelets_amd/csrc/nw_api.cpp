@@ -1035,15 +1035,21 @@ int execute_conn(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs,
 // t0 + j * step and writes the chunk's epochs' slice of the (E, P, F) sums, which live in d_acc with
 // the (E, C, F) power sums and the tile descriptors.  Every value is written by exactly one block of
 // one launch: no memset.  One copy back at the end.
+// env >= 0: envelope correlation (nw_execute_env_time) through the same chunks -- nw_env_time_kernel
+// in the place of nw_conn_time_kernel, env = NW_ENV_*, out_sum = its pair sums (1 or 6 fp64 per (e, p, f))
+// and out_power = its per-channel sums (2 fp64 per (e, c, f)); out_kind is unused.
 int execute_conn_time(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ia,
                       const int32_t* ib, int64_t npairs, int64_t t0, int64_t t1, int64_t step, void* out_sum,
-                      void* out_power, int out_kind, bool host) {
+                      void* out_power, int out_kind, bool host, int env = -1) {
+    const char* const who = env >= 0 ? "nw_execute_env_time" : "nw_execute_conn_time";
     const int mode = nw::sum_mode(out_kind);
     const int64_t count = nw::conn_time_count(t0, t1, step);
     const int64_t fn = (int64_t)p->nfreq * p->n_out();
-    const size_t pair_bytes = (size_t)p->nfreq * (mode == nw::SUM_LAG ? 4 : 2) * sizeof(double);   // of one (e, p)
+    const int pair_vals = env >= 0 ? nw::env_pair_values(env) : mode == nw::SUM_LAG ? 4 : 2;   // fp64 per (e, p, f)
+    const int chan_vals = env >= 0 ? 2 : 1;                                                    // fp64 per (e, c, f)
+    const size_t pair_bytes = (size_t)p->nfreq * pair_vals * sizeof(double);   // of one (e, p)
     const size_t sum_bytes = (size_t)nepochs * npairs * pair_bytes;
-    const size_t power_bytes = out_power ? (size_t)nepochs * nchan * p->nfreq * sizeof(double) : 0;
+    const size_t power_bytes = out_power ? (size_t)nepochs * nchan * p->nfreq * chan_vals * sizeof(double) : 0;
     p->conn_tiles = nw::host::conn_tiles(ia, ib, npairs, nullptr);
     const size_t tile_bytes = p->conn_tiles.size() * sizeof(nw::ConnTile);
     const size_t acc_bytes = sum_bytes + power_bytes;   // multiples of 8: the tiles start 16-aligned below
@@ -1051,7 +1057,7 @@ int execute_conn_time(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nep
     const int got = p->d_acc.ensure(tile_at + tile_bytes + 16);
     if (got != NW_OK && got != NW_E_NOMEM) return got;
     if (got == NW_E_NOMEM)
-        return fail(NW_E_NOMEM, "nw_execute_conn_time: the fp64 sums of " + std::to_string(nepochs) + " epochs, " +
+        return fail(NW_E_NOMEM, std::string(who) + ": the fp64 sums of " + std::to_string(nepochs) + " epochs, " +
                                     std::to_string(npairs) + " pairs and " + std::to_string(out_power ? nchan : 0) +
                                     " channels need " + std::to_string(tile_at + tile_bytes + 16) +
                                     " bytes of device memory: " + g_last_error);
@@ -1065,10 +1071,11 @@ int execute_conn_time(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nep
     nw_logf(1, "plan %p: %s over time, %lld epochs x %d channels, %lld pairs in %lld tiles (%lld epochs per chunk), "
                "window [%lld, %lld) step %lld of %lld samples, %s buffers: per-signal rows per chunk, every (epoch, "
                "pair, scale) summed over its %lld samples in fp64 in lane order",
-            (void*)p, out_name(out_kind), (long long)nepochs, nchan, (long long)npairs, (long long)p->conn_tiles.size(),
+            (void*)p, env == NW_ENV_ORTH ? "env_orth_sum" : env == NW_ENV_PLAIN ? "env_sum" : out_name(out_kind),
+            (long long)nepochs, nchan, (long long)npairs, (long long)p->conn_tiles.size(),
             (long long)per, (long long)t0, (long long)t1, (long long)step, (long long)p->n_out(),
             host ? "host" : "device", (long long)count);
-    p->stats.reduce_path = NW_REDUCE_CONN_TIME;
+    p->stats.reduce_path = env >= 0 ? NW_REDUCE_ENV : NW_REDUCE_CONN_TIME;
     void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
     if (p->form == FORM_ROCFFT) {
         NW_TRY(need_Y(p, p->nfreq));
@@ -1090,11 +1097,17 @@ int execute_conn_time(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nep
         }
         NW_TRY(run_chunk(p, d, xs, ec * nchan, scratch, NW_OUT_CWT, false));
         // chained: run_chunk ends with a stage
-        if (npairs > 0 || power)
+        double* const chunk_power = power ? (double*)power + e0 * nchan * p->nfreq * chan_vals : nullptr;
+        if (env >= 0 && (npairs > 0 || power))
             NW_TRY(NW_KERNEL_STAGE(
                 p, ST_EPI, true,
-                nw::launch_conn_time(p->dtype, mode, scratch, sums + (size_t)e0 * npairs * pair_bytes,
-                                     power ? (double*)power + e0 * nchan * p->nfreq : nullptr, tiles,
+                nw::launch_env_time(p->dtype, env, scratch, sums + (size_t)e0 * npairs * pair_bytes, chunk_power, tiles,
+                                    (int)p->conn_tiles.size(), ec, nchan, p->nfreq, p->n_out(), npairs, t0, count, step,
+                                    xcd, p->stream)));
+        else if (npairs > 0 || power)
+            NW_TRY(NW_KERNEL_STAGE(
+                p, ST_EPI, true,
+                nw::launch_conn_time(p->dtype, mode, scratch, sums + (size_t)e0 * npairs * pair_bytes, chunk_power, tiles,
                                      (int)p->conn_tiles.size(), ec, nchan, p->nfreq, p->n_out(), npairs, t0, count, step,
                                      xcd, p->stream)));
         p->stats.chunks++;
@@ -1759,6 +1772,35 @@ int nw_execute_conn_time(nw_plan* p, const void* x, int64_t nepochs, int32_t nch
     if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
     NW_TRY(execute_conn_time(p, d, x, nepochs, nchan, ia, ib, npairs, t0, t1, step, out_sum, out_power, out_kind,
                              mem == NW_MEM_HOST));
+    return dcheck_collect(p->stream);
+}
+
+int nw_execute_env_time(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ia, const int32_t* ib,
+                        int64_t npairs, int64_t t0, int64_t t1, int64_t step, void* out_pair, void* out_chan,
+                        int env_kind, int mem) {
+    if (!p || (!x && nepochs > 0) || (!out_pair && npairs > 0 && nepochs > 0))
+        return fail(NW_E_INVALID, "nw_execute_env_time: null argument");
+    if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_env_time: nw_plan_set_wavelet first");
+    if (env_kind != NW_ENV_PLAIN && env_kind != NW_ENV_ORTH)
+        return fail(NW_E_INVALID, "nw_execute_env_time: env_kind must be NW_ENV_PLAIN or NW_ENV_ORTH");
+    if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_env_time: bad mem");
+    if (nepochs < 0) return fail(NW_E_INVALID, "nw_execute_env_time: nepochs < 0");
+    NW_TRY(check_pairs("nw_execute_env_time", nchan, ia, ib, npairs));
+    if (p->max_batch < nchan)
+        return fail(NW_E_INVALID, "nw_execute_env_time: the plan's max_batch (" + std::to_string(p->max_batch) +
+                                      ") must be >= nchan (" + std::to_string(nchan) +
+                                      "): a chunk holds max_batch / nchan epochs");
+    if (step < 1) return fail(NW_E_INVALID, "nw_execute_env_time: step (" + std::to_string(step) + ") must be >= 1");
+    if (t0 < 0 || t0 > t1 || t1 > p->n_out())
+        return fail(NW_E_INVALID, "nw_execute_env_time: the window [" + std::to_string(t0) + ", " + std::to_string(t1) +
+                                      ") must satisfy 0 <= t0 <= t1 <= n_out (" + std::to_string(p->n_out()) + ")");
+    DeviceGuard guard(p->device);
+    p->executed = true;
+    const nw::WDesc d = exec_rows(p);
+    // settle the form of a tentative length before any buffer choice
+    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
+    NW_TRY(execute_conn_time(p, d, x, nepochs, nchan, ia, ib, npairs, t0, t1, step, out_pair, out_chan, NW_OUT_CROSS_SUM,
+                             mem == NW_MEM_HOST, env_kind));
     return dcheck_collect(p->stream);
 }
 

@@ -257,6 +257,15 @@ hipError_t launch_conn_accumulate(int dtype, int mode, const void* src, void* cr
 hipError_t launch_conn_time(int dtype, int mode, const void* src, void* sum, double* power, const ConnTile* tiles,
                             int ntiles, int64_t ec, int nchan, int nfreq, int64_t n_out, int64_t npairs, int64_t t0,
                             int64_t count, int64_t step, bool xcd, hipStream_t s);
+// envelope correlation (nw_env.hip): src, tiles and the window as launch_conn_time; env = NW_ENV_PLAIN:
+// pair (ec, npairs, F) fp64 = sum A_a A_b, NW_ENV_ORTH: pair (ec, npairs, F, 6) fp64 = {sum u, sum u u,
+// sum u A_b, sum v, sum v v, sum v A_a} (ninwave.h: nw_execute_env_time), in the order of conn_time_lane;
+// chan (ec, nchan, F, 2) fp64 = {sum A, sum |y|^2} per row (null: not formed).  Every value is written,
+// none is read.
+constexpr int env_pair_values(int env) { return env == NW_ENV_ORTH ? 6 : 1; }
+hipError_t launch_env_time(int dtype, int env, const void* src, void* pair, double* chan, const ConnTile* tiles,
+                           int ntiles, int64_t ec, int nchan, int nfreq, int64_t n_out, int64_t npairs, int64_t t0,
+                           int64_t count, int64_t step, bool xcd, hipStream_t s);
 // phase-amplitude coupling (nw_pac.hip): src as above; m (ec, npairs, nph, nam) complex fp64 = the sums
 // over the samples t0 + j * step, j < count, of A u (A: |y| of channel ia[p]'s row fam[k], u: the unit
 // phasor of channel ip[p]'s row fph[i]), in the order of conn_time_lane; amp (ec, nchan, nam, 2) fp64 =

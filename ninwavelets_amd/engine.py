@@ -40,6 +40,12 @@ LAG_OUTS = {'lag_sum': 'lag_sum', 'pli': 'lag_sum', 'pli2_unbiased': 'lag_sum', 
             'wpli': 'lag_sum', 'wpli2_debiased': 'lag_sum', 'ciplv': 'plv_sum', 'ppc': 'plv_sum'}
 # phase-amplitude coupling (Plan.execute_pac): what finalize_pac forms from its sums (M, amp, phase)
 PAC_OUTS = {'pac_sum', 'mvl', 'mvl_norm', 'direct_pac', 'debiased_pac'}
+# envelope correlation (Plan.execute_env_time): the Pearson sums of two amplitude envelopes, plain
+# (float64 (E, P, F)) or pairwise orthogonalised (float64 (E, P, F, 6)), each with the per-channel sums
+# float64 (E, C, F, 2); and what finalize_env forms, name -> the sums it needs
+ENV_KINDS = {'env_sum': L.NW_ENV_PLAIN, 'env_orth_sum': L.NW_ENV_ORTH}
+ENV_OUTS = {'env_sum': 'env_sum', 'env_orth_sum': 'env_orth_sum', 'aec': 'env_sum',
+            'aec_directed': 'env_orth_sum', 'aec_orth': 'env_orth_sum', 'aec_orth_signed': 'env_orth_sum'}
 KINDS = {'morse': L.NW_MORSE, 'morlet': L.NW_MORLET, 'shannon': L.NW_SHANNON, 'table': L.NW_TABLE,
          # WaveletMode.Normal tables built on the device (base.py:249-256)
          'mexican_hat': L.NW_MEXICAN_HAT, 'haar': L.NW_HAAR}
@@ -297,6 +303,60 @@ def finalize_pac(kind: str, M, amp, phase, ip, ia, nsamples: int):
     den = np.broadcast_to(den, M.shape)
     zero = den == 0
     return np.where(zero, 0., np.abs(M) / np.where(zero, 1., den))
+
+
+def _pearson(sxy, sx, sy, sxx, syy, T: int):
+    """Pearson's r from the sums over T samples: cov = sxy - sx sy / T, var = sxx - sx^2 / T,
+    r = cov / sqrt(var_x var_y), and 0 where a variance is <= 0 (mne's std == 0 -> 1); NaN sums stay NaN."""
+    cov = sxy - sx * sy / T
+    vx, vy = sxx - sx * sx / T, syy - sy * sy / T
+    flat = (vx <= 0) | (vy <= 0)
+    return np.where(flat, 0., cov / np.sqrt(np.where(flat, 1., vx * vy)))
+
+
+def finalize_env(kind: str, pair, chan, ia, ib, nsamples: int):
+    """The envelope correlation ``kind`` (Hipp et al. 2012; mne-connectivity's envelope_correlation)
+    per epoch, pair p = (a, b) = (ia[p], ib[p]) and scale from the sums of Plan.execute_env_time over
+    T = ``nsamples`` window samples: ``chan`` float64 (E, C, F, 2) = {sum A, sum A^2} with A = |y|, and
+    ``pair`` float64 (E, P, F) = sum A_a A_b (``env_sum``) or (E, P, F, 6) = {sum u, sum u^2, sum u A_b,
+    sum v, sum v^2, sum v A_a} (``env_orth_sum``), u = |Im(y_a conj(y_b) / |y_b|)| being a orthogonalised
+    against b and v the reverse.  With r the Pearson correlation over the samples,
+      aec              r(A_a, A_b)                      from env_sum        (E, P, F)
+      aec_directed     [r(u, A_b), r(v, A_a)]           from env_orth_sum   (E, P, F, 2)
+      aec_orth         (|r(u, A_b)| + |r(v, A_a)|) / 2  mne's default (orthogonalize='pairwise', absolute=True)
+      aec_orth_signed  (r(u, A_b) + r(v, A_a)) / 2      absolute=False
+    r = 0 where a variance is <= 0 (mne's std == 0 -> 1; the wpli convention), and the orthogonalised
+    kinds are exactly 0 where ia[p] == ib[p], whatever the sums hold (mne's diagonal).  ``env_sum`` and
+    ``env_orth_sum`` return (pair, chan) unchanged.  Plain numpy, float64; the finalised kinds need
+    T >= 2 (ValueError)."""
+    if kind not in ENV_OUTS:
+        raise ValueError(f"out must be one of {', '.join(ENV_OUTS)}; got {kind!r}")
+    if kind in ENV_KINDS:
+        return pair, chan
+    T = int(nsamples)
+    if T < 2:
+        raise ValueError(f'{kind} needs at least 2 samples in the window, got {T}')
+    pair, chan = np.asarray(pair, dtype=np.float64), np.asarray(chan, dtype=np.float64)
+    ia, ib = np.asarray(ia, dtype=np.intp), np.asarray(ib, dtype=np.intp)
+    if chan.ndim != 4 or chan.shape[-1] != 2:
+        raise ValueError(f'chan must be (epochs, channels, scales, 2), got shape {chan.shape}')
+    want = 3 if kind == 'aec' else 4
+    if pair.ndim != want or (want == 4 and pair.shape[-1] != 6) or pair.shape[1] != ia.size or ia.shape != ib.shape:
+        raise ValueError(f"the pair sums of {kind} must be (epochs, {ia.size} pairs, scales{', 6' if want == 4 else ''}), "
+                         f'got shape {pair.shape}')
+    ca, cb = chan[:, ia], chan[:, ib]                   # (E, P, F, 2): the sums of the pairs' channels
+    sa, saa, sb, sbb = ca[..., 0], ca[..., 1], cb[..., 0], cb[..., 1]
+    if kind == 'aec':
+        return _pearson(pair, sa, sb, saa, sbb, T)
+    r_ab = _pearson(pair[..., 2], pair[..., 0], sb, pair[..., 1], sbb, T)
+    r_ba = _pearson(pair[..., 5], pair[..., 3], sa, pair[..., 4], saa, T)
+    own = (ia == ib)[None, :, None]
+    r_ab, r_ba = np.where(own, 0., r_ab), np.where(own, 0., r_ba)
+    if kind == 'aec_directed':
+        return np.stack([r_ab, r_ba], axis=-1)
+    if kind == 'aec_orth':
+        return (np.abs(r_ab) + np.abs(r_ba)) / 2
+    return (r_ab + r_ba) / 2
 
 
 def time_window(n: int, decim: int, window, on_device: bool):
@@ -812,6 +872,81 @@ class Plan:
                                              sums.ctypes.data_as(P), None if plv else power.ctypes.data_as(P), kind,
                                              L.NW_MEM_HOST))
         return sums if plv else (sums, power)
+
+    def execute_env_time(self, x, indices=None, window=None, step: int = 1, out=None, out_kind: str = 'env_orth_sum'):
+        """Envelope-correlation sums (nw_execute_env_time): x (E, C, n), ``indices``, ``window`` (the
+        plan's OUTPUT samples; None: (0, n_out)) and ``step`` as in execute_conn_time, every signal
+        transformed once and reduced on the device.  Returns (pair, chan): ``env_sum`` -> pair float64
+        (E, P, nfreq) = sum A_a A_b, ``env_orth_sum`` -> pair float64 (E, P, nfreq, 6) = {sum u, sum u^2,
+        sum u A_b, sum v, sum v^2, sum v A_a}; chan float64 (E, C, nfreq, 2) = {sum A, sum A^2}; see
+        finalize_env.  numpy arrays: synchronous, ``out`` optional.  Device tensors: asynchronous on the
+        plan stream, ``out`` = (pair, chan) required (chan may be None: not formed).  The plan needs
+        max_batch >= C."""
+        import operator
+        if out_kind not in ENV_KINDS:
+            raise ValueError(f"out_kind must be one of {', '.join(ENV_KINDS)}; got {out_kind!r}")
+        kind = ENV_KINDS[out_kind]
+        if getattr(x, 'ndim', 0) != 3:
+            raise ValueError(f'x must be (epochs, channels, n), got shape {tuple(getattr(x, "shape", ()))}')
+        nep, nchan = int(x.shape[0]), int(x.shape[1])
+        ia, ib = check_indices(indices, nchan)
+        npairs = int(ia.size)
+        try:
+            t0, t1 = (0, self.n_out) if window is None else window
+            t0, t1, step = operator.index(t0), operator.index(t1), operator.index(step)
+        except (TypeError, ValueError):
+            raise ValueError(f'window must be a pair (t0, t1) of integers and step an integer, got {window!r} and '
+                             f'{step!r}') from None
+        if step < 1:
+            raise ValueError(f'step must be >= 1, got {step}')
+        if not 0 <= t0 <= t1 <= self.n_out:
+            raise ValueError(f'window must satisfy 0 <= t0 <= t1 <= n_out = {self.n_out}, got ({t0}, {t1})')
+        P = ctypes.c_void_p
+        ip = (ia.ctypes.data_as(P), ib.ctypes.data_as(P))
+        shapes = ((nep, npairs, self.nfreq) + ((6,) if kind == L.NW_ENV_ORTH else ()), (nep, nchan, self.nfreq, 2))
+        if _is_device_tensor(x):
+            import torch
+            if out is None:
+                raise ValueError('device execute needs output tensors')
+            if self._check_device_input(x) != nep * nchan:
+                raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
+            try:
+                pair, chan = out
+            except (TypeError, ValueError):
+                raise ValueError('device output must be (pair, chan) tensors (chan may be None)') from None
+            for t, shape, name in zip((pair, chan), shapes, ('pair', 'chan')):
+                if t is None and name == 'chan':
+                    continue
+                if not _is_device_tensor(t) or t.dtype != torch.float64:
+                    raise ValueError(f'device output {name} must be a {torch.float64} tensor on device {self.device}')
+                if not t.is_contiguous() or t.numel() != int(np.prod(shape)):
+                    raise ValueError(f'device output {name} must be contiguous and hold {int(np.prod(shape))} values')
+                if t.device.index != self.device:
+                    raise ValueError(f'device buffers must live on device {self.device}')
+            with self._ordered_with_torch(x.device):
+                L.check(L.lib().nw_execute_env_time(self._h, P(x.data_ptr()), nep, nchan, *ip, npairs, t0, t1, step,
+                                                    P(pair.data_ptr()),
+                                                    P(chan.data_ptr()) if chan is not None else None, kind,
+                                                    L.NW_MEM_DEVICE))
+            return out
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        if x.shape[-1] != self.n:
+            raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
+        try:
+            pair, chan = (None, None) if out is None else out
+        except (TypeError, ValueError):
+            raise ValueError('out must be (pair, chan) arrays') from None
+        if pair is None:
+            pair = np.empty(shapes[0], dtype=np.float64)
+        if chan is None:
+            chan = np.empty(shapes[1], dtype=np.float64)
+        for a, shape in zip((pair, chan), shapes):
+            if (not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.c_contiguous
+                    or a.size != int(np.prod(shape))):
+                raise ValueError('out must be C-contiguous arrays of the right dtype and size')
+        L.check(L.lib().nw_execute_env_time(self._h, x.ctypes.data_as(P), nep, nchan, *ip, npairs, t0, t1, step,
+                                            pair.ctypes.data_as(P), chan.ctypes.data_as(P), kind, L.NW_MEM_HOST))
+        return pair, chan
 
     def execute_pac(self, x, indices=None, phase=None, amp=None, window=None, step: int = 1, out=None):
         """Phase-amplitude coupling sums (nw_execute_pac): x (E, C, n) as in execute_conn_time, every

@@ -118,6 +118,27 @@ class EpochsWavelet:
         return self.wavelet.connectivity_time_batch(waves, freqs, reuse=True, out=method, indices=indices,
                                                     window=(k, n - k), decim=decim, average=average)
 
+    # -- envelope correlation: the amplitude-coupling counterpart, per epoch, pair and scale
+    #    (WaveletBase.envelope_correlation_batch) ------------------------------------------------
+    def envelope_correlation(self, ch_names, freqs, method: str = 'aec_orth', indices=None, padding: float = 0.,
+                             decim: int = 1, average: bool = False):
+        """``method`` (envelope_correlation_batch's outs: aec_orth, aec_orth_signed, aec_directed, aec,
+        env_sum, env_orth_sum) per epoch, (E, P, F): what mne-connectivity's envelope_correlation
+        returns per pair, with the wavelet rows as the analytic signals.  ``indices`` = (ia, ib),
+        positions in ``ch_names`` (default: every pair a < b); ``padding`` as in connectivity_time;
+        ``average=True``: the mean over the epochs, (P, F)."""
+        ch_names = list(ch_names)
+        idx = [self.epochs.ch_names.index(c) for c in ch_names]
+        waves = self.epochs.get_data()[:, idx, :]
+        n = waves.shape[-1]
+        if not padding >= 0:
+            raise ValueError(f'padding must be >= 0 seconds, got {padding!r}')
+        k = int(round(padding * self.epochs.info['sfreq']))
+        if k >= n - k:
+            raise ValueError(f'padding of {padding} s ({k} samples on each side) leaves no sample of the {n}')
+        return self.wavelet.envelope_correlation_batch(waves, freqs, reuse=True, out=method, indices=indices,
+                                                       window=(k, n - k), decim=decim, average=average)
+
     # -- phase-amplitude coupling: one comodulogram per epoch and pair (WaveletBase.pac_batch) ------
     def pac(self, ch_names, phase_freqs, amp_freqs, method: str = 'direct_pac', indices=None, padding: float = 0.,
             decim: int = 1, average: bool = False):
