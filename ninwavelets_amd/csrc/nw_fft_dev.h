@@ -43,6 +43,14 @@ __device__ __forceinline__ double mul_nocontract(double a, double b) {
 #pragma clang fp contract(off)
     return a * b;
 }
+__device__ __forceinline__ float mul_nocontract(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ f2 mul_nocontract(f2 a, f2 b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 __device__ __forceinline__ double add_nocontract(double a, double b) {
 #pragma clang fp contract(off)
     return a + b;
@@ -196,6 +204,23 @@ constexpr int kOutPlvSum = 1004;
 template <int OUT> constexpr int kPairAcc = OUT == kOutXSum ? 4 : OUT == kOutPlvSum ? 2 : 1;
 struct alignas(16) XHalfSlot { double a, b; };
 template <typename T> struct OutT<kOutXHalf, T> { using type = XHalfSlot; };
+// |y|^2 is written re * re + im * im and left to the compiler's contraction, which fuses either
+// product into the fma: fma(im, im, re * re) and fma(re, re, im * im) round differently, and
+// which one it picks depends on how the operands reach it.  PIN writes
+// the first form out -- the one the kernels of the lane images have always had -- so that their
+// outputs do not move with the scheduling of the reads that feed the last pass.  Two points at a
+// time, as the paired last pass holds them (v_pk_mul_f32, v_pk_fma_f32).
+template <bool RE_FUSED>
+__device__ __forceinline__ f2 norm2_pinned(C2<float> y0, C2<float> y1) {
+    const f2 re{y0.re, y1.re}, im{y0.im, y1.im};
+    if constexpr (RE_FUSED) return fma_t(re, re, mul_nocontract(im, im));
+    else return fma_t(im, im, mul_nocontract(re, re));
+}
+// register i of the paired last pass (radix 16, outputs bit-reversed): the plain sum and
+// difference of the last stage, registers 0 and 1, have had fma(re, re, im * im), the other
+// fourteen fma(im, im, re * re)
+constexpr int kPinNone = 0, kPinImFused = 1, kPinReFused = 2;
+constexpr int pin_of(int i) { return i <= 1 ? kPinReFused : kPinImFused; }
 template <int OUT, typename T>
 __device__ __forceinline__ typename OutT<OUT, T>::type out_value(C2<T> y) {
     if constexpr (OUT == NW_OUT_CWT) return y;
@@ -249,7 +274,7 @@ template <typename O> using StoreVec =
 // store outputs idx, idx+1 of the current row (orow: wave-uniform row base) as ONE
 // vector store (16 B for complex64, 8 B for float32, 2x16 B for complex128)
 // outputs lane_idx + c_idx (pair: and the next one) of the current row
-template <int OUT, typename T, int SP>
+template <int OUT, typename T, int SP, int PIN = kPinNone>
 __device__ __forceinline__ void store_pair(void* orow, uint32_t lane_idx, uint32_t c_idx, C2<T> y0, C2<T> y1) {
     using O = typename OutT<OUT, T>::type;
     struct alignas(2 * sizeof(O)) P2 { O a, b; };
@@ -260,7 +285,14 @@ __device__ __forceinline__ void store_pair(void* orow, uint32_t lane_idx, uint32
     using V = typename std::conditional<sizeof(P2) == 16, float __attribute__((ext_vector_type(4))),
               typename std::conditional<sizeof(P2) == 8, float __attribute__((ext_vector_type(2))),
                                         double __attribute__((ext_vector_type(4)))>::type>::type;
-    const P2 pv{out_value<OUT, T>(y0), out_value<OUT, T>(y1)};
+    P2 pv;
+    if constexpr (PIN != kPinNone && OUT != NW_OUT_CWT) {
+        static_assert(std::is_same<T, float>::value && (OUT == NW_OUT_POWER || OUT == NW_OUT_ABS), "the lane images' kernels");
+        const f2 p = norm2_pinned<PIN == kPinReFused>(y0, y1);
+        if constexpr (OUT == NW_OUT_POWER) pv = P2{p.x, p.y}; else pv = P2{(T)sqrt(p.x), (T)sqrt(p.y)};
+    } else {
+        pv = P2{out_value<OUT, T>(y0), out_value<OUT, T>(y1)};
+    }
     store_row<SP>(__builtin_bit_cast(V, pv), orow, lane_idx * (uint32_t)sizeof(O), c_idx * (uint32_t)sizeof(O));
 }
 template <int OUT, typename T, int SP>
@@ -365,6 +397,92 @@ __device__ __forceinline__ void addtid_store16(uint32_t m0, const float* d) {
         : "memory", "m0");
     if constexpr (WAIT) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
+
+// The sites of NW_LDS_ASM_READS (nw_shape.h) a kernel takes: the kernels of the lane images
+template <typename T, int N, int E, int OUT>
+constexpr int kAsmReads = kLaneImage<T, N, E, OUT> ? (NW_LDS_ASM_READS) : 0;
+
+// 8-byte LDS reads, one ds_read_b64 each: lane l reads the 8 bytes at its base + a compile-time
+// offset.  The outputs are early-clobber aligned VGPR pairs (none may take the base's register:
+// every read uses it).  The compiler does not count LDS operations issued from asm, so each
+// statement ends with lgkmcnt(0): its outputs are valid when it is left.
+typedef float lds_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const lds_void_t*)p; }
+#define NW_DSR(k, b) "ds_read_b64 %[o" #k "], %[" #b "] offset:%[f]+" #k "*%[st]\n\t"
+#define NW_DSR4(a, b, c, d, base) NW_DSR(a, base) NW_DSR(b, base) NW_DSR(c, base) NW_DSR(d, base)
+#define NW_DSO(k) [o##k] "=&v"(o[k])
+#define NW_DSO4(a, b, c, d) NW_DSO(a), NW_DSO(b), NW_DSO(c), NW_DSO(d)
+#define NW_DS_WAIT "s_waitcnt lgkmcnt(0)"
+// 16 reads from one base, STEP bytes apart from OFF0 (the 1 -> 2 image's pairs of one component)
+template <int OFF0, int STEP>
+__device__ __forceinline__ void ds_read_b64_16(uint32_t base, lds_f2* o) {
+    static_assert(OFF0 >= 0 && OFF0 % 8 == 0 && STEP % 8 == 0 && OFF0 + 15 * STEP < 65536, "16-bit offset field");
+    asm volatile(NW_DSR4(0, 1, 2, 3, bd) NW_DSR4(4, 5, 6, 7, bd) NW_DSR4(8, 9, 10, 11, bd) NW_DSR4(12, 13, 14, 15, bd) NW_DS_WAIT
+                 : NW_DSO4(0, 1, 2, 3), NW_DSO4(4, 5, 6, 7), NW_DSO4(8, 9, 10, 11), NW_DSO4(12, 13, 14, 15)
+                 : [bd] "v"(base), [f] "i"(OFF0), [st] "i"(STEP)
+                 : "memory");
+}
+// one batch of the pass-1 table: up to 8 entries of one column at their own offsets (F0 < 0: the
+// entry is not read -- batch 0 has no w^0)
+template <int F0, int F1, int F2, int F3, int F4, int F5, int F6, int F7>
+__device__ __forceinline__ void ds_read_b64_8(uint32_t base, lds_f2* o) {
+    static_assert(F0 < 65536 && F1 < 65536 && F2 < 65536 && F3 < 65536 && F4 < 65536 && F5 < 65536 && F6 < 65536 && F7 < 65536,
+                  "16-bit offset field");
+    static_assert((F0 < 0 || F0 % 8 == 0) && (F1 | F2 | F3 | F4 | F5 | F6 | F7) % 8 == 0 && F1 >= 0, "8-byte entries");
+    if constexpr (F0 >= 0) {
+        asm volatile("ds_read_b64 %[o0], %[bd] offset:%[f0]\n\tds_read_b64 %[o1], %[bd] offset:%[f1]\n\t"
+                     "ds_read_b64 %[o2], %[bd] offset:%[f2]\n\tds_read_b64 %[o3], %[bd] offset:%[f3]\n\t"
+                     "ds_read_b64 %[o4], %[bd] offset:%[f4]\n\tds_read_b64 %[o5], %[bd] offset:%[f5]\n\t"
+                     "ds_read_b64 %[o6], %[bd] offset:%[f6]\n\tds_read_b64 %[o7], %[bd] offset:%[f7]\n\t" NW_DS_WAIT
+                     : NW_DSO4(0, 1, 2, 3), NW_DSO4(4, 5, 6, 7)
+                     : [bd] "v"(base), [f0] "i"(F0), [f1] "i"(F1), [f2] "i"(F2), [f3] "i"(F3), [f4] "i"(F4), [f5] "i"(F5),
+                       [f6] "i"(F6), [f7] "i"(F7)
+                     : "memory");
+    } else {
+        asm volatile("ds_read_b64 %[o1], %[bd] offset:%[f1]\n\t"
+                     "ds_read_b64 %[o2], %[bd] offset:%[f2]\n\tds_read_b64 %[o3], %[bd] offset:%[f3]\n\t"
+                     "ds_read_b64 %[o4], %[bd] offset:%[f4]\n\tds_read_b64 %[o5], %[bd] offset:%[f5]\n\t"
+                     "ds_read_b64 %[o6], %[bd] offset:%[f6]\n\tds_read_b64 %[o7], %[bd] offset:%[f7]\n\t" NW_DS_WAIT
+                     : NW_DSO(1), NW_DSO(2), NW_DSO(3), NW_DSO4(4, 5, 6, 7)
+                     : [bd] "v"(base), [f1] "i"(F1), [f2] "i"(F2), [f3] "i"(F3), [f4] "i"(F4), [f5] "i"(F5), [f6] "i"(F6),
+                       [f7] "i"(F7)
+                     : "memory");
+    }
+}
+// (lo() hands out a type of its own: v * w of the DIT form is cmul's plain expression, whose
+// imaginary part the compiler contracts as fma(v.im, w.re, v.re * w.im) when w comes from its own
+// loads and as fma(v.re, w.im, v.im * w.re) when w comes from asm.  The overload below writes the
+// first form out -- both parts as the kernels have always had them -- DESIGN.md §4 Round 15.)
+struct TwEntry { float re, im; };
+__device__ __forceinline__ C2<float> cmul(C2<float> v, TwEntry w) {
+    return {fma_t(v.re, w.re, -mul_nocontract(v.im, w.im)), fma_t(v.im, w.re, mul_nocontract(v.re, w.im))};
+}
+template <int R, int NS> struct TwTableAsm {
+    using scalar = float;
+    static_assert(R == lane_image::kE && NS == lane_image::kE && lane_image::kTabBatch == 4 && !kUseDifTw<float, float, R>,
+                  "pass 1 of the fp32 n = 16384 kernels, DIT order");
+    uint32_t col;                  // LDS byte address of the butterfly's column of the table
+    mutable lds_f2 w[8];           // lo(4 b + i) at w[2 i], hi(4 b + i) at w[2 i + 1]
+    template <int B> __device__ __forceinline__ void batch() const {
+        namespace L = lane_image;
+        constexpr int r = 4 * B, h = R / 2;
+        ds_read_b64_8<B == 0 ? -1 : L::tab1_off(B == 0 ? 1 : r), L::tab1_off(r + h), L::tab1_off(r + 1), L::tab1_off(r + 1 + h),
+                      L::tab1_off(r + 2), L::tab1_off(r + 2 + h), L::tab1_off(r + 3), L::tab1_off(r + 3 + h)>(col, w);
+    }
+    __device__ __forceinline__ void first(int r) const {
+        if (r == 0) batch<0>(); else if (r == 4) batch<1>(); else if (r == 8) batch<2>(); else batch<3>();
+    }
+    __device__ __forceinline__ TwEntry lo(int r) const {
+        if (r % 4 == 0) first(r);
+        return {w[2 * (r % 4)].x, w[2 * (r % 4)].y};
+    }
+    __device__ __forceinline__ C2<float> hi(int r) const {
+        if (r == 0) first(r);
+        const C2<float> c{w[2 * (r % 4) + 1].x, w[2 * (r % 4) + 1].y};
+        if (r % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+        return c;
+    }
+};
 
 // one component of the pass-P outputs -> the lane-addressed image feeding pass P + 1
 template <typename T, int N, int E, int P, int COMP>
@@ -501,7 +619,7 @@ template <typename T, int N, int E> struct Tab1 {
     }
 };
 
-template <typename T, int N, int E, int P, int COMP, int OSZ, bool LN = false>
+template <typename T, int N, int E, int P, int COMP, int OSZ, bool LN = false, int AR = 0>
 __device__ __forceinline__ void lds_read(C2<T>* v, const T* lds, int t) {
     using I = PassInfo<N, E, P, OSZ, kIsPair<T>, LN>;
     constexpr int R = I::R, Q = I::Q;
@@ -516,15 +634,25 @@ __device__ __forceinline__ void lds_read(C2<T>* v, const T* lds, int t) {
         } else {
             static_assert(P == 2 && Q == 2 && I::PAIRED && I::STRIDE == 1024, "pass 2: pairs 2t, 2t + 1, slots j2 + 1024 r");
             const T* src = lds + L::rbase_12(I::bfly(t, 0));
-            // (the compiler merges these 16 reads, 128 B apart, into 8 ds_read2_b64.  Issued as 16
-            // ds_read_b64 from one asm statement C4 ran 3.142 against 3.166 ms per launch, but the
-            // |y| and |y|^2 outputs were then no longer the parent's bit for bit: not kept,
-            // profiles/r13_lane_image_ab.txt)
+            // (the compiler merges these 16 reads, 128 B apart, into 8 ds_read2_b64 of twice the LDS
+            // cycles each; kAsmReadImage issues them as 16 ds_read_b64)
+            if constexpr ((AR & L::kAsmReadImage) != 0) {
+                static_assert(R == 16 && L::rd12_off(1) * 15 == L::rd12_off(15), "16 reads, evenly spaced");
+                NW_DCHECK_H(L::rd12_base(t) == (int)((const char*)src - (const char*)lds));
+                lds_f2 pr[R];
+                ds_read_b64_16<L::rd12_off(0), L::rd12_off(1)>(lds_addr(src), pr);
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const Pair<T> pr = *reinterpret_cast<const Pair<T>*>(src + L::roff_12(r));
-                comp<COMP>(v[r]) = pr.a;
-                comp<COMP>(v[R + r]) = pr.b;
+                for (int r = 0; r < R; ++r) {
+                    comp<COMP>(v[r]) = pr[r].x;
+                    comp<COMP>(v[R + r]) = pr[r].y;
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const Pair<T> pr = *reinterpret_cast<const Pair<T>*>(src + L::roff_12(r));
+                    comp<COMP>(v[r]) = pr.a;
+                    comp<COMP>(v[R + r]) = pr.b;
+                }
             }
         }
     } else if constexpr (I::PAIRED) {
@@ -713,7 +841,7 @@ struct LastStores {
         constexpr uint32_t c = (uint32_t)((I::PAIRED ? q : q * Geometry<N, E>::T) + bitrev<R>(i) * I::NS);
         NW_DCHECK_H(lane + c + (I::PAIRED ? 1u : 0u) < (uint32_t)N);
         if constexpr (I::PAIRED)
-            store_pair<OUT, T, SP>(orow, lane, c, o[q * R + i], o[(q + 1) * R + i]);
+            store_pair<OUT, T, SP, kLaneImage<T, N, E, OUT> ? pin_of(i) : kPinNone>(orow, lane, c, o[q * R + i], o[(q + 1) * R + i]);
         else
             store_one<OUT, T, SP>(orow, lane, c, o[q * R + i]);
     }
@@ -788,6 +916,7 @@ __device__ __forceinline__ void passes_from(C2<T>* v, T* lds, int t, const C2<Sc
     constexpr bool PAIRSIG = !std::is_same<T, S>::value;
     constexpr int OSZ = (int)sizeof(typename OutT<OUT, S>::type);
     constexpr bool LN = kLaneImage<T, N, E, OUT>;
+    constexpr int AR = kAsmReads<T, N, E, OUT>;
     using I = PassInfo<N, E, P, OSZ, kIsPair<T>, LN>;
     if constexpr (P < Geometry<N, E>::npass()) {
         constexpr int R = I::R, Q = I::Q, LR = ilog2<R>();
@@ -812,11 +941,11 @@ __device__ __forceinline__ void passes_from(C2<T>* v, T* lds, int t, const C2<Sc
         lds_barrier();                         // earlier readers of the image are done
         lds_write<T, N, E, P - 1, 0, LN>(v, lds, t);
         lds_barrier();
-        lds_read<T, N, E, P, 0, OSZ, LN>(v, lds, t);
+        lds_read<T, N, E, P, 0, OSZ, LN, AR>(v, lds, t);
         lds_barrier();
         lds_write<T, N, E, P - 1, 1, LN>(v, lds, t);
         lds_barrier();
-        lds_read<T, N, E, P, 1, OSZ, LN>(v, lds, t);
+        lds_read<T, N, E, P, 1, OSZ, LN, AR>(v, lds, t);
 #else   // ablation (diagnostic builds only): no exchange, the registers stay live
 #pragma unroll
         for (int i = 0; i < E; ++i) asm volatile("" : "+v"(v[i].re), "+v"(v[i].im));
@@ -867,6 +996,11 @@ __device__ __forceinline__ void passes_from(C2<T>* v, T* lds, int t, const C2<Sc
                         reinterpret_cast<C2<float>*>(v)[(q + 1) * R + i] = hi(pv[i]);
                     }
                 }
+            } else if constexpr (TWIDDLED && TABLED && (AR & lane_image::kAsmReadTab1) != 0 && !kUseDifTw<T, S, R>) {
+                // (the DIF diagnostic build asks for the twiddles in another order: the plain loads)
+                static_assert(Q == 1 && kImgElems<T, N, E> * (int)sizeof(T) == lane_image::kBytes, "the table's place");
+                NW_DCHECK_H(lane_image::tab1_base(t) == (int)((const char*)(Tab1<T, N, E>::table(lds) + I::bfly(t, q) % I::NS) - (const char*)lds));
+                idft_br_tw<T, R>(v + q * R, TwTableAsm<R, I::NS>{lds_addr(Tab1<T, N, E>::table(lds) + I::bfly(t, q) % I::NS), {}});
             } else if constexpr (TWIDDLED && TABLED) {
                 idft_br_tw<T, R>(v + q * R, TwTable<S, R, I::NS, true>{Tab1<T, N, E>::table(lds) + I::bfly(t, q) % I::NS});
             } else if constexpr (TWIDDLED) {
@@ -896,8 +1030,18 @@ __device__ __forceinline__ void passes_from(C2<T>* v, T* lds, int t, const C2<Sc
                     }
                 }
             } else {
+                if constexpr (LN) {                 // the pinned form of store_pair, pair by pair
+                    static_assert(Q == 2, "the paired last pass");
+                    f2 p[R];
 #pragma unroll
-                for (int e = 0; e < Q * R; ++e) acc[e] += (double)(v[e].re * v[e].re + v[e].im * v[e].im);
+                    for (int e = 0; e < R; ++e)
+                        p[e] = pin_of(e) == kPinReFused ? norm2_pinned<true>(v[e], v[R + e]) : norm2_pinned<false>(v[e], v[R + e]);
+#pragma unroll
+                    for (int e = 0; e < Q * R; ++e) acc[e] += (double)(e < R ? p[e].x : p[e - R].y);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < Q * R; ++e) acc[e] += (double)(v[e].re * v[e].re + v[e].im * v[e].im);
+                }
             }
         } else if constexpr (I::LAST && OUT == kOutPhSum) {
             static_assert(!PAIRSIG, "partial sums run the single-signal kernel");

@@ -338,6 +338,29 @@ NW_SHAPE_HD constexpr int roff_12(int r) { return 32 * r; }
 static_assert(addr01(kN - 1) < kElems && addr12(kN - 1) < kElems, "both images inside the region");
 static_assert(off_01(kE - 1) < 65536 && off_12(kE - 1) < 65536, "16-bit offset field");
 static_assert(2 * (kBytes + kTab1Bytes) <= kCuLdsBytes, "two blocks per CU");
+
+// 8-byte LDS reads of these kernels issued one ds_read_b64 each from inline asm (nw_fft_dev.h,
+// ds_read_b64_*): left to the compiler, neighbouring reads are merged into ds_read2_b64 /
+// ds_read2st64_b64, which take twice the LDS cycles of the two reads they replace.
+// NW_LDS_ASM_READS is a mask of the sites: 1 the 1 -> 2 image's paired reads, 2 the pass-1
+// twiddle table.  0: the compiler's loads.  (A third site, the pass-0 X image that the LDS-DMA
+// fills, measured -0.5 % per launch at best and is not built: DESIGN.md §4 Round 15.)
+#ifndef NW_LDS_ASM_READS
+#define NW_LDS_ASM_READS 3
+#endif
+constexpr int kAsmReadImage = 1, kAsmReadTab1 = 2;
+// Every read is (one byte base per lane) + (a compile-time byte offset, the instruction's
+// unsigned 16-bit field); bases count from the start of the block's LDS.
+// 1 -> 2 image: thread t reads the pairs (2t, 2t + 1) of elements r < 16
+NW_SHAPE_HD constexpr int rd12_base(int t) { return 4 * rbase_12(2 * t); }
+NW_SHAPE_HD constexpr int rd12_off(int r) { return 4 * roff_12(r); }
+// pass-1 table (behind the image; power r = 1 .. 31 of column jj at entry (r - 1) * 32 + jj, 8 B
+// each): butterfly t reads column t % 32, in batches b = 0 .. 3 of the pairs (w^r, w^(r + 16)),
+// r = 4 b .. 4 b + 3 (w^0 is not stored: batch 0 has 7 entries)
+constexpr int kTabBatch = 4;
+NW_SHAPE_HD constexpr int tab1_base(int t) { return kBytes + 8 * (t % kE); }
+NW_SHAPE_HD constexpr int tab1_off(int r) { return 8 * kE * (r - 1); }
+static_assert(rd12_off(15) < 65536 && tab1_off(kE - 1) < 65536, "16-bit offset field");
 }  // namespace lane_image
 
 // ---- multi-channel connectivity (nw_conn.hip) -------------------------------------------------
