@@ -79,6 +79,14 @@ class _Cache:
         self.row_len = row_len
 
 
+def _epochs(waves):
+    """``waves`` as an (E, C, N) array, with E, C and N."""
+    waves = np.asarray(waves)
+    if waves.ndim != 3:
+        raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
+    return (waves, *waves.shape)
+
+
 class WaveletBase:
     """Base class of the wavelets (base.py:145-443).
 
@@ -497,22 +505,13 @@ class WaveletBase:
         decim = check_decim(decim)
         if out not in CONN_OUTS:
             raise ValueError(f"out must be one of {', '.join(CONN_OUTS)}; got {out!r}")
-        waves = np.asarray(waves)
-        if waves.ndim != 3:
-            raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
-        nep, nchan, n = waves.shape
+        waves, nep, nchan, n = _epochs(waves)
         ia, ib = check_indices(indices, nchan)
         if (not reuse) or self._cache is None:
             self._build_cache(freqs, n / self.sfreq)
         on_device = self._device_decim(n, decim)
-        self._used = 1
-        try:
-            plan = self._plan(n, nep * nchan, (self.devices or [self.device])[0],
-                              decim=decim if on_device else 1, min_batch=nchan)
-            sums = plan.execute_conn(waves, (ia, ib), out_kind=CONN_OUTS[out])
-        finally:
-            if len(self._plans) > 1:
-                self._evict_plans(keep=1)
+        sums = self._on_plan(n, nep * nchan, decim if on_device else 1, nchan,
+                             lambda plan: plan.execute_conn(waves, (ia, ib), out_kind=CONN_OUTS[out]))
         cross, power = sums if CONN_OUTS[out] == 'cross_sum' else (sums, None)
         if decim > 1 and not on_device:
             cross = np.ascontiguousarray(cross[..., ::decim])
@@ -567,24 +566,15 @@ class WaveletBase:
         decim = check_decim(decim)
         if out not in LAG_OUTS:
             raise ValueError(f"out must be one of {', '.join(LAG_OUTS)}; got {out!r}")
-        waves = np.asarray(waves)
-        if waves.ndim != 3:
-            raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
-        nep, nchan, n = waves.shape
-        ia, ib = check_indices(indices, nchan)
+        waves, nep, nchan, n = _epochs(waves)
+        pairs = check_indices(indices, nchan)
         if out in ('pli2_unbiased', 'ppc') and nep < 2:
             raise ValueError(f'{out} needs at least 2 epochs, got {nep}')
         if (not reuse) or self._cache is None:
             self._build_cache(freqs, n / self.sfreq)
         on_device = self._device_decim(n, decim)
-        self._used = 1
-        try:
-            plan = self._plan(n, nep * nchan, (self.devices or [self.device])[0],
-                              decim=decim if on_device else 1, min_batch=nchan)
-            sums = plan.execute_conn(waves, (ia, ib), out_kind=LAG_OUTS[out])
-        finally:
-            if len(self._plans) > 1:
-                self._evict_plans(keep=1)
+        sums = self._on_plan(n, nep * nchan, decim if on_device else 1, nchan,
+                             lambda plan: plan.execute_conn(waves, pairs, out_kind=LAG_OUTS[out]))
         if decim > 1 and not on_device:
             sums = np.ascontiguousarray(sums[:, :, ::decim])
         return finalize_lag(out, sums, nep)
@@ -603,35 +593,54 @@ class WaveletBase:
         the finalised measure, (P, F) (ValueError for the ``*_sum`` kinds).  pli2_unbiased and ppc
         need T >= 2.  Pair lists, cache semantics, device choice and plan eviction as in
         connectivity_batch."""
+        outs = {**CONN_OUTS, **LAG_OUTS}
+
+        def finalize(sums, *a):
+            return finalize_conn_time(out, *(sums if outs[out] == 'cross_sum' else (sums, None)), *a)
+        return self._time_sums(waves, freqs, reuse, out, outs, check_indices, indices, window, decim, average,
+                               2 if out in ('pli2_unbiased', 'ppc') else 0,
+                               lambda plan, *a: plan.execute_conn_time(*a, out_kind=outs[out]), finalize)
+
+    def _time_sums(self, waves, freqs, reuse, out, names, check_pairs, indices, window, decim, average, min_count,
+                   execute, finalize, scales=None):
+        """The over-time measures of (E, C, N) epochs: the argument checks (``out`` one of ``names``,
+        the pair list by ``check_pairs``, at least ``min_count`` window samples; ``scales``: pac_batch's
+        (phase, amp) lists), the cache, the plan of the first device with max_batch >= C and its
+        eviction, sums = execute(plan, waves, pairs, *scales, window, step) and
+        finalize(sums, *pairs, count), averaged over the epochs where asked."""
         decim = check_decim(decim)
-        if out not in CONN_OUTS and out not in LAG_OUTS:
-            raise ValueError(f"out must be one of {', '.join({**CONN_OUTS, **LAG_OUTS})}; got {out!r}")
+        if out not in names:
+            raise ValueError(f"out must be one of {', '.join(names)}; got {out!r}")
         if average and out.endswith('_sum'):
             raise ValueError(f'average=True takes a finalised measure, not the sums {out!r}')
-        waves = np.asarray(waves)
-        if waves.ndim != 3:
-            raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
-        nep, nchan, n = waves.shape
-        ia, ib = check_indices(indices, nchan)
+        waves, nep, nchan, n = _epochs(waves)
+        pairs = check_pairs(indices, nchan)
+        rebuild = (not reuse) or self._cache is None
+        if scales is not None:
+            nfreq = len(list(freqs)) if rebuild else len(self._cache.freqs)     # the scale list the call will use
+            scales = check_scales('phase', scales[0], nfreq), check_scales('amp', scales[1], nfreq)
         count = time_window(n, decim, window, False)[3]     # the same count on either kind of plan
-        if out in ('pli2_unbiased', 'ppc') and count < 2:
-            raise ValueError(f'{out} needs at least 2 samples in the window, got {count}')
-        if (not reuse) or self._cache is None:
+        if count < min_count:
+            raise ValueError(f'{out} needs at least {min_count} sample{"s" if min_count > 1 else ""} in the window, '
+                             f'got {count}')
+        if rebuild:
             self._build_cache(freqs, n / self.sfreq)
         on_device = self._device_decim(n, decim)
         t0, t1, step, count = time_window(n, decim, window, on_device)
-        need = CONN_OUTS[out] if out in CONN_OUTS else LAG_OUTS[out]
+        sums = self._on_plan(n, nep * nchan, decim if on_device else 1, nchan,
+                             lambda plan: execute(plan, waves, pairs, *(scales or ()), (t0, t1), step))
+        res = finalize(sums, *pairs, count)
+        return res.mean(axis=0) if average else res
+
+    def _on_plan(self, n, nsig, decim, min_batch, call):
+        """call(plan) on the first device's plan for nsig signals (max_batch >= min_batch); the other
+        plans are evicted afterwards."""
         self._used = 1
         try:
-            plan = self._plan(n, nep * nchan, (self.devices or [self.device])[0],
-                              decim=decim if on_device else 1, min_batch=nchan)
-            sums = plan.execute_conn_time(waves, (ia, ib), (t0, t1), step, out_kind=need)
+            return call(self._plan(n, nsig, (self.devices or [self.device])[0], decim=decim, min_batch=min_batch))
         finally:
             if len(self._plans) > 1:
                 self._evict_plans(keep=1)
-        sums, power = sums if need == 'cross_sum' else (sums, None)
-        res = finalize_conn_time(out, sums, power, ia, ib, count)
-        return res.mean(axis=0) if average else res
 
     def envelope_correlation_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, out: str = 'aec_orth',
                                    indices=None, window=None, decim: int = 1, average: bool = False):
@@ -646,33 +655,10 @@ class WaveletBase:
         ``window``, ``decim`` and ``average`` (the mean over the epochs, (P, F); ValueError for the
         ``*_sum`` kinds) as in connectivity_time_batch; the finalised kinds need T >= 2 window samples.
         Pair lists, cache semantics, device choice and plan eviction as in connectivity_batch."""
-        decim = check_decim(decim)
-        if out not in ENV_OUTS:
-            raise ValueError(f"out must be one of {', '.join(ENV_OUTS)}; got {out!r}")
-        if average and out.endswith('_sum'):
-            raise ValueError(f'average=True takes a finalised measure, not the sums {out!r}')
-        waves = np.asarray(waves)
-        if waves.ndim != 3:
-            raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
-        nep, nchan, n = waves.shape
-        ia, ib = check_indices(indices, nchan)
-        count = time_window(n, decim, window, False)[3]     # the same count on either kind of plan
-        if not out.endswith('_sum') and count < 2:
-            raise ValueError(f'{out} needs at least 2 samples in the window, got {count}')
-        if (not reuse) or self._cache is None:
-            self._build_cache(freqs, n / self.sfreq)
-        on_device = self._device_decim(n, decim)
-        t0, t1, step, count = time_window(n, decim, window, on_device)
-        self._used = 1
-        try:
-            plan = self._plan(n, nep * nchan, (self.devices or [self.device])[0],
-                              decim=decim if on_device else 1, min_batch=nchan)
-            pair, chan = plan.execute_env_time(waves, (ia, ib), (t0, t1), step, out_kind=ENV_OUTS[out])
-        finally:
-            if len(self._plans) > 1:
-                self._evict_plans(keep=1)
-        res = finalize_env(out, pair, chan, ia, ib, count)
-        return res.mean(axis=0) if average else res
+        return self._time_sums(waves, freqs, reuse, out, ENV_OUTS, check_indices, indices, window, decim, average,
+                               0 if str(out).endswith('_sum') else 2,
+                               lambda plan, *a: plan.execute_env_time(*a, out_kind=ENV_OUTS[out]),
+                               lambda sums, *a: finalize_env(out, *sums, *a))
 
     def pac_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, phase=None, amp=None,
                   out: str = 'direct_pac', indices=None, window=None, decim: int = 1, average: bool = False):
@@ -686,36 +672,10 @@ class WaveletBase:
         and ``average`` (the mean over the epochs, (P, Fp, Fa); ValueError for ``pac_sum``) as in
         connectivity_time_batch; an empty window is a ValueError for the finalised kinds.  Cache
         semantics, device choice and plan eviction as in connectivity_batch."""
-        decim = check_decim(decim)
-        if out not in PAC_OUTS:
-            raise ValueError(f"out must be one of {', '.join(sorted(PAC_OUTS))}; got {out!r}")
-        if average and out == 'pac_sum':
-            raise ValueError(f'average=True takes a finalised measure, not the sums {out!r}')
-        waves = np.asarray(waves)
-        if waves.ndim != 3:
-            raise ValueError(f'waves must be (epochs, channels, N); got shape {waves.shape}')
-        nep, nchan, n = waves.shape
-        ip, ia = check_pac_indices(indices, nchan)
-        rebuild = (not reuse) or self._cache is None
-        nfreq = len(list(freqs)) if rebuild else len(self._cache.freqs)     # the scale list the call will use
-        fph, fam = check_scales('phase', phase, nfreq), check_scales('amp', amp, nfreq)
-        count = time_window(n, decim, window, False)[3]     # the same count on either kind of plan
-        if out != 'pac_sum' and count < 1:
-            raise ValueError(f'{out} needs at least 1 sample in the window, got {count}')
-        if rebuild:
-            self._build_cache(freqs, n / self.sfreq)
-        on_device = self._device_decim(n, decim)
-        t0, t1, step, count = time_window(n, decim, window, on_device)
-        self._used = 1
-        try:
-            plan = self._plan(n, nep * nchan, (self.devices or [self.device])[0],
-                              decim=decim if on_device else 1, min_batch=nchan)
-            sums = plan.execute_pac(waves, (ip, ia), fph, fam, (t0, t1), step)
-        finally:
-            if len(self._plans) > 1:
-                self._evict_plans(keep=1)
-        res = finalize_pac(out, *sums, ip, ia, count)
-        return res.mean(axis=0) if average else res
+        return self._time_sums(waves, freqs, reuse, out, dict.fromkeys(sorted(PAC_OUTS)), check_pac_indices, indices,
+                               window, decim, average, 0 if out == 'pac_sum' else 1,
+                               lambda plan, *a: plan.execute_pac(*a),
+                               lambda sums, *a: finalize_pac(out, *sums, *a), scales=(phase, amp))
 
     def plan_stats(self) -> list:
         """Per-plan device stage timings (nw_plan_stats)."""

@@ -139,9 +139,11 @@ int dcheck_collect(hipStream_t stream) {
         e = take(&fails, &site, &file);
         if (e != hipSuccess) return fail(NW_E_HIP, std::string("bounds-check readback: ") + hipGetErrorString(e));
         if (!fails) continue;
-        std::string where = site >= nw::kDcheckHeaderSite
-                                ? "nw_fft_dev.h:" + std::to_string(site - nw::kDcheckHeaderSite)
-                                : std::string(file) + ":" + std::to_string(site);
+        std::string where = site >= nw::kDcheckReduceSite
+                                ? "nw_reduce_dev.h:" + std::to_string(site - nw::kDcheckReduceSite)
+                                : site >= nw::kDcheckHeaderSite
+                                      ? "nw_fft_dev.h:" + std::to_string(site - nw::kDcheckHeaderSite)
+                                      : std::string(file) + ":" + std::to_string(site);
         msg += (msg.empty() ? "" : "; ") + std::to_string(fails) + " failing check(s), first at " + where;
     }
     return msg.empty() ? NW_OK : fail(NW_E_BOUNDS, "kernel bounds check: " + msg);
@@ -955,262 +957,233 @@ int execute_pair(nw_plan* p, const nw::WDesc& d, const void* xa, const void* xb,
     return NW_OK;
 }
 
-// Multi-channel connectivity (nw_execute_conn): per chunk of max_batch / nchan epochs the
-// (ec, nchan, n) block of x is staged as it lies (epoch-major), the complex rows of its ec * nchan
-// signals go to the scratch execute_pair uses (any form), and nw_conn_accumulate_kernel adds every
-// pair's products of the chunk into the fp64 accumulators, which it reads and writes once per
-// chunk; nw_conn_power_kernel adds |y|^2 per channel.  The accumulators and the tile descriptors
-// (built and uploaded once per call) share d_acc.
+// The epoch-chunk reductions (nw_execute_conn, _conn_time, _env_time, _pac) share one layout of d_acc
+// and one loop.  d_acc holds the call's fp64 output regions one after the other and then, 16-aligned,
+// one auxiliary blob (tile descriptors or index lists) that is built and uploaded once per call.
+struct SumRegion {
+    void* out;            // the caller's buffer
+    size_t bytes;         // of the whole call; an optional output that was not asked for has out = null, bytes = 0
+    size_t epoch;         // of one epoch (0: the region belongs to the call as a whole and is read-modify-written)
+    char* dev = nullptr;  // its place in d_acc (the first region always has one; a later one without `out`: null)
+    char* at(int64_t e0) const { return dev ? dev + (size_t)e0 * epoch : nullptr; }
+};
+
+// Places the regions and the blob and uploads the blob; zero: the regions start at 0 (sums that are
+// read-modify-written per chunk).  `what` completes the message of a failed allocation.
+int place_sums(nw_plan* p, SumRegion* r, int nr, const void* aux, size_t aux_bytes, const char** d_aux, bool zero,
+               const std::string& what) {
+    size_t acc_bytes = 0;
+    for (int i = 0; i < nr; ++i) acc_bytes += r[i].bytes;   // multiples of 8
+    const size_t aux_at = (acc_bytes + 15) / 16 * 16;
+    const int got = p->d_acc.ensure(aux_at + aux_bytes + 16);
+    if (got != NW_OK && got != NW_E_NOMEM) return got;
+    if (got == NW_E_NOMEM)
+        return fail(NW_E_NOMEM, what + " need " + std::to_string(aux_at + aux_bytes + 16) +
+                                    " bytes of device memory: " + g_last_error);
+    size_t at = 0;
+    for (int i = 0; i < nr; ++i) {
+        r[i].dev = i == 0 || r[i].out ? p->d_acc.at(at) : nullptr;
+        at += r[i].bytes;
+    }
+    *d_aux = p->d_acc.at(aux_at);
+    if (zero && acc_bytes) NW_HIP(hipMemsetAsync(p->d_acc.at(0), 0, acc_bytes, p->stream));
+    if (aux_bytes) NW_HIP(hipMemcpyAsync((void*)*d_aux, aux, aux_bytes, hipMemcpyHostToDevice, p->stream));
+    return NW_OK;
+}
+
+// block order: the blocks that share rows neighbours on one XCD (conn_slot, conn_time_slot, pac_slot);
+// NW_CONN_PLAIN_ORDER (diagnostics: the A/B of tools/conn_rate.py) keeps plain block order
+bool xcd_order() { return !std::getenv("NW_CONN_PLAIN_ORDER"); }
+
+// Per chunk of max_batch / nchan epochs the (ec, nchan, n) block of x is staged as it lies
+// (epoch-major), the complex rows of its ec * nchan signals go to the scratch execute_pair uses (any
+// form), and launch(e0, ec, rows) reduces them -- one kernel stage, chained: run_chunk ends with a
+// stage.  Then the regions are copied to the caller's buffers, once.
+template <typename F>
+int run_epoch_chunks(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const SumRegion* r,
+                     int nr, bool host, F&& launch) {
+    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
+    if (p->form == FORM_ROCFFT) {
+        NW_TRY(need_Y(p, p->nfreq));
+        scratch = p->d_Y.ptr;
+    } else {
+        NW_TRY(p->d_out.ensure((size_t)p->max_batch * p->nfreq * p->n_out() * 2 * p->esz));
+        scratch = p->d_out.ptr;
+    }
+    const int64_t per = p->max_batch / nchan;
+    const size_t epoch_bytes = (size_t)nchan * p->n * p->esz;
+    for (int64_t e0 = 0; e0 < nepochs; e0 += per) {
+        const int64_t ec = std::min<int64_t>(per, nepochs - e0);
+        const void* xs = (const char*)x + (size_t)e0 * epoch_bytes;
+        if (host) {
+            NW_TRY(staged(p, ST_COPY, [&] {
+                NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, (size_t)ec * epoch_bytes, hipMemcpyHostToDevice, p->stream));
+                return NW_OK;
+            }));
+            xs = p->d_x.ptr;
+        }
+        NW_TRY(run_chunk(p, d, xs, ec * nchan, scratch, NW_OUT_CWT, false));
+        NW_TRY(launch(e0, ec, scratch));
+        p->stats.chunks++;
+    }
+    const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    for (int i = 0; i < nr; ++i)
+        if (r[i].bytes) NW_HIP(hipMemcpyAsync(r[i].out, r[i].dev, r[i].bytes, back, p->stream));
+    p->stats.executes++;
+    if (host) {
+        NW_HIP(hipStreamSynchronize(p->stream));
+        NW_TRY(resolve_timing(p));
+    }
+    return NW_OK;
+}
+
+// Multi-channel connectivity (nw_execute_conn): per chunk nw_conn_accumulate_kernel adds every pair's
+// products of the chunk into the fp64 accumulators, which it reads and writes once per chunk;
+// nw_conn_power_kernel adds |y|^2 per channel.
 int execute_conn(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ia,
                  const int32_t* ib, int64_t npairs, void* out_cross, void* out_power, int out_kind, bool host) {
     const int mode = nw::sum_mode(out_kind);
     const int64_t fn = (int64_t)p->nfreq * p->n_out();
     // 16 B per pair and point (a complex fp64), NW_OUT_LAG_SUM: 32 B (its four sums)
-    const size_t cross_bytes = (size_t)npairs * fn * (mode == nw::SUM_LAG ? 4 : 2) * sizeof(double);
-    const size_t power_bytes = out_power ? (size_t)nchan * fn * sizeof(double) : 0;
+    SumRegion r[2] = {{out_cross, (size_t)npairs * fn * (mode == nw::SUM_LAG ? 4 : 2) * sizeof(double), 0},
+                      {out_power, out_power ? (size_t)nchan * fn * sizeof(double) : 0, 0}};
     p->conn_tiles = nw::host::conn_tiles(ia, ib, npairs, nullptr);
-    const size_t tile_bytes = p->conn_tiles.size() * sizeof(nw::ConnTile);
-    const size_t acc_bytes = cross_bytes + power_bytes;   // multiples of 16
-    const int got = p->d_acc.ensure(acc_bytes + tile_bytes + 16);
-    if (got != NW_OK && got != NW_E_NOMEM) return got;
-    if (got == NW_E_NOMEM)
-        return fail(NW_E_NOMEM, "nw_execute_conn: the fp64 accumulators of " + std::to_string(npairs) + " pairs and " +
-                                    std::to_string(out_power ? nchan : 0) + " channels need " +
-                                    std::to_string(acc_bytes + tile_bytes + 16) + " bytes of device memory: " + g_last_error);
-    char* const cross = p->d_acc.at(0);
-    double* const power = out_power ? (double*)p->d_acc.at(cross_bytes) : nullptr;
-    const nw::ConnTile* const tiles = (const nw::ConnTile*)p->d_acc.at(acc_bytes);
-    if (acc_bytes) NW_HIP(hipMemsetAsync(cross, 0, acc_bytes, p->stream));
-    if (tile_bytes)
-        NW_HIP(hipMemcpyAsync((void*)tiles, p->conn_tiles.data(), tile_bytes, hipMemcpyHostToDevice, p->stream));
-    // block order: pair tiles of one (scale, sample tile) neighbours on one XCD (conn_slot);
-    // NW_CONN_PLAIN_ORDER (diagnostics: the A/B of tools/conn_rate.py) keeps plain block order
-    const bool xcd = !std::getenv("NW_CONN_PLAIN_ORDER");
-    const int64_t per = p->max_batch / nchan;
+    const int ntiles = (int)p->conn_tiles.size();
+    const char* tiles = nullptr;
+    NW_TRY(place_sums(p, r, 2, p->conn_tiles.data(), ntiles * sizeof(nw::ConnTile), &tiles, true,
+                      "nw_execute_conn: the fp64 accumulators of " + std::to_string(npairs) + " pairs and " +
+                          std::to_string(out_power ? nchan : 0) + " channels"));
+    const bool xcd = xcd_order();
     nw_logf(1, "plan %p: %s over %lld epochs x %d channels, %lld pairs in %lld tiles (%lld epochs per chunk): "
                "per-signal rows per chunk, every pair added in epoch order in fp64",
-            (void*)p, out_name(out_kind), (long long)nepochs, nchan, (long long)npairs, (long long)p->conn_tiles.size(),
-            (long long)per);
+            (void*)p, out_name(out_kind), (long long)nepochs, nchan, (long long)npairs, (long long)ntiles,
+            (long long)(p->max_batch / nchan));
     p->stats.reduce_path = NW_REDUCE_CONN;
-    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
-    if (p->form == FORM_ROCFFT) {
-        NW_TRY(need_Y(p, p->nfreq));
-        scratch = p->d_Y.ptr;
-    } else {
-        NW_TRY(p->d_out.ensure((size_t)p->max_batch * fn * 2 * p->esz));
-        scratch = p->d_out.ptr;
-    }
-    const size_t epoch_bytes = (size_t)nchan * p->n * p->esz;
-    for (int64_t e0 = 0; e0 < nepochs; e0 += per) {
-        const int64_t ec = std::min<int64_t>(per, nepochs - e0);
-        const void* xs = (const char*)x + (size_t)e0 * epoch_bytes;
-        if (host) {
-            NW_TRY(staged(p, ST_COPY, [&] {
-                NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, (size_t)ec * epoch_bytes, hipMemcpyHostToDevice, p->stream));
-                return NW_OK;
-            }));
-            xs = p->d_x.ptr;
-        }
-        NW_TRY(run_chunk(p, d, xs, ec * nchan, scratch, NW_OUT_CWT, false));
-        // chained: run_chunk ends with a stage
-        NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, true,
-                               nw::launch_conn_accumulate(p->dtype, mode, scratch, cross, power, tiles,
-                                                          (int)p->conn_tiles.size(), ec, nchan, p->nfreq, p->n_out(),
-                                                          npairs, xcd, p->stream)));
-        p->stats.chunks++;
-    }
-    const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (cross_bytes) NW_HIP(hipMemcpyAsync(out_cross, cross, cross_bytes, back, p->stream));
-    if (power_bytes) NW_HIP(hipMemcpyAsync(out_power, power, power_bytes, back, p->stream));
-    p->stats.executes++;
-    if (host) {
-        NW_HIP(hipStreamSynchronize(p->stream));
-        NW_TRY(resolve_timing(p));
-    }
-    return NW_OK;
+    return run_epoch_chunks(p, d, x, nepochs, nchan, r, 2, host, [&](int64_t, int64_t ec, void* rows) {
+        return NW_KERNEL_STAGE(p, ST_EPI, true,
+                               nw::launch_conn_accumulate(p->dtype, mode, rows, r[0].dev, (double*)r[1].dev,
+                                                          (const nw::ConnTile*)tiles, ntiles, ec, nchan, p->nfreq,
+                                                          p->n_out(), npairs, xcd, p->stream));
+    });
 }
 
-// Over-time connectivity (nw_execute_conn_time): the chunks and the scratch of execute_conn; per
-// chunk nw_conn_time_kernel reduces every pair's products along the window's `count` samples
-// t0 + j * step and writes the chunk's epochs' slice of the (E, P, F) sums, which live in d_acc with
-// the (E, C, F) power sums and the tile descriptors.  Every value is written by exactly one block of
-// one launch: no memset.  One copy back at the end.
-// env >= 0: envelope correlation (nw_execute_env_time) through the same chunks -- nw_env_time_kernel
-// in the place of nw_conn_time_kernel, env = NW_ENV_*, out_sum = its pair sums (1 or 6 fp64 per (e, p, f))
-// and out_power = its per-channel sums (2 fp64 per (e, c, f)); out_kind is unused.
-int execute_conn_time(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ia,
-                      const int32_t* ib, int64_t npairs, int64_t t0, int64_t t1, int64_t step, void* out_sum,
-                      void* out_power, int out_kind, bool host, int env = -1) {
-    const char* const who = env >= 0 ? "nw_execute_env_time" : "nw_execute_conn_time";
-    const int mode = nw::sum_mode(out_kind);
-    const int64_t count = nw::conn_time_count(t0, t1, step);
-    const int64_t fn = (int64_t)p->nfreq * p->n_out();
-    const int pair_vals = env >= 0 ? nw::env_pair_values(env) : mode == nw::SUM_LAG ? 4 : 2;   // fp64 per (e, p, f)
-    const int chan_vals = env >= 0 ? 2 : 1;                                                    // fp64 per (e, c, f)
-    const size_t pair_bytes = (size_t)p->nfreq * pair_vals * sizeof(double);   // of one (e, p)
-    const size_t sum_bytes = (size_t)nepochs * npairs * pair_bytes;
-    const size_t power_bytes = out_power ? (size_t)nepochs * nchan * p->nfreq * chan_vals * sizeof(double) : 0;
-    p->conn_tiles = nw::host::conn_tiles(ia, ib, npairs, nullptr);
-    const size_t tile_bytes = p->conn_tiles.size() * sizeof(nw::ConnTile);
-    const size_t acc_bytes = sum_bytes + power_bytes;   // multiples of 8: the tiles start 16-aligned below
-    const size_t tile_at = (acc_bytes + 15) / 16 * 16;
-    const int got = p->d_acc.ensure(tile_at + tile_bytes + 16);
-    if (got != NW_OK && got != NW_E_NOMEM) return got;
-    if (got == NW_E_NOMEM)
-        return fail(NW_E_NOMEM, std::string(who) + ": the fp64 sums of " + std::to_string(nepochs) + " epochs, " +
-                                    std::to_string(npairs) + " pairs and " + std::to_string(out_power ? nchan : 0) +
-                                    " channels need " + std::to_string(tile_at + tile_bytes + 16) +
-                                    " bytes of device memory: " + g_last_error);
-    char* const sums = p->d_acc.at(0);
-    char* const power = out_power ? p->d_acc.at(sum_bytes) : nullptr;
-    const nw::ConnTile* const tiles = (const nw::ConnTile*)p->d_acc.at(tile_at);
-    if (tile_bytes)
-        NW_HIP(hipMemcpyAsync((void*)tiles, p->conn_tiles.data(), tile_bytes, hipMemcpyHostToDevice, p->stream));
-    const bool xcd = !std::getenv("NW_CONN_PLAIN_ORDER");
-    const int64_t per = p->max_batch / nchan;
+// the log line of the over-time pair sums (after place_time_sums: it counts the call's tiles)
+void log_time_sums(nw_plan* p, const char* name, int64_t nepochs, int nchan, int64_t npairs, int64_t t0, int64_t t1,
+                   int64_t step, bool host) {
     nw_logf(1, "plan %p: %s over time, %lld epochs x %d channels, %lld pairs in %lld tiles (%lld epochs per chunk), "
                "window [%lld, %lld) step %lld of %lld samples, %s buffers: per-signal rows per chunk, every (epoch, "
                "pair, scale) summed over its %lld samples in fp64 in lane order",
-            (void*)p, env == NW_ENV_ORTH ? "env_orth_sum" : env == NW_ENV_PLAIN ? "env_sum" : out_name(out_kind),
-            (long long)nepochs, nchan, (long long)npairs, (long long)p->conn_tiles.size(),
-            (long long)per, (long long)t0, (long long)t1, (long long)step, (long long)p->n_out(),
-            host ? "host" : "device", (long long)count);
-    p->stats.reduce_path = env >= 0 ? NW_REDUCE_ENV : NW_REDUCE_CONN_TIME;
-    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
-    if (p->form == FORM_ROCFFT) {
-        NW_TRY(need_Y(p, p->nfreq));
-        scratch = p->d_Y.ptr;
-    } else {
-        NW_TRY(p->d_out.ensure((size_t)p->max_batch * fn * 2 * p->esz));
-        scratch = p->d_out.ptr;
-    }
-    const size_t epoch_bytes = (size_t)nchan * p->n * p->esz;
-    for (int64_t e0 = 0; e0 < nepochs; e0 += per) {
-        const int64_t ec = std::min<int64_t>(per, nepochs - e0);
-        const void* xs = (const char*)x + (size_t)e0 * epoch_bytes;
-        if (host) {
-            NW_TRY(staged(p, ST_COPY, [&] {
-                NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, (size_t)ec * epoch_bytes, hipMemcpyHostToDevice, p->stream));
-                return NW_OK;
-            }));
-            xs = p->d_x.ptr;
-        }
-        NW_TRY(run_chunk(p, d, xs, ec * nchan, scratch, NW_OUT_CWT, false));
-        // chained: run_chunk ends with a stage
-        double* const chunk_power = power ? (double*)power + e0 * nchan * p->nfreq * chan_vals : nullptr;
-        if (env >= 0 && (npairs > 0 || power))
-            NW_TRY(NW_KERNEL_STAGE(
-                p, ST_EPI, true,
-                nw::launch_env_time(p->dtype, env, scratch, sums + (size_t)e0 * npairs * pair_bytes, chunk_power, tiles,
-                                    (int)p->conn_tiles.size(), ec, nchan, p->nfreq, p->n_out(), npairs, t0, count, step,
-                                    xcd, p->stream)));
-        else if (npairs > 0 || power)
-            NW_TRY(NW_KERNEL_STAGE(
-                p, ST_EPI, true,
-                nw::launch_conn_time(p->dtype, mode, scratch, sums + (size_t)e0 * npairs * pair_bytes, chunk_power, tiles,
-                                     (int)p->conn_tiles.size(), ec, nchan, p->nfreq, p->n_out(), npairs, t0, count, step,
-                                     xcd, p->stream)));
-        p->stats.chunks++;
-    }
-    const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (sum_bytes) NW_HIP(hipMemcpyAsync(out_sum, sums, sum_bytes, back, p->stream));
-    if (power_bytes) NW_HIP(hipMemcpyAsync(out_power, power, power_bytes, back, p->stream));
-    p->stats.executes++;
-    if (host) {
-        NW_HIP(hipStreamSynchronize(p->stream));
-        NW_TRY(resolve_timing(p));
-    }
-    return NW_OK;
+            (void*)p, name, (long long)nepochs, nchan, (long long)npairs, (long long)p->conn_tiles.size(),
+            (long long)(p->max_batch / nchan), (long long)t0, (long long)t1, (long long)step, (long long)p->n_out(),
+            host ? "host" : "device", (long long)nw::conn_time_count(t0, t1, step));
 }
 
-// Phase-amplitude coupling (nw_execute_pac): the chunks, the scratch and the window of
-// execute_conn_time; per chunk nw_pac_kernel reduces every pair's |y_a| u_p products along the
-// window's `count` samples for every listed (phase, amplitude) scale and writes the chunk's epochs'
-// slice of the (E, P, nph, nam) sums, nw_pac_rows_kernel the per-channel sums.  The sums live in d_acc
-// with the pair and scale lists.  Every value is written by exactly one block of one launch: no memset.
+// The regions of the over-time pair sums: pair_vals fp64 per (e, p, f) and, where out_chan is given,
+// chan_vals per (e, c, f); the blob is the call's tile descriptors (p->conn_tiles).
+int place_time_sums(nw_plan* p, const char* who, SumRegion (&r)[2], int64_t nepochs, int nchan, const int32_t* ia,
+                    const int32_t* ib, int64_t npairs, void* out_pair, int pair_vals, void* out_chan, int chan_vals,
+                    const nw::ConnTile** tiles) {
+    const size_t pair_epoch = (size_t)npairs * p->nfreq * pair_vals * sizeof(double);
+    const size_t chan_epoch = (size_t)nchan * p->nfreq * chan_vals * sizeof(double);
+    r[0] = {out_pair, (size_t)nepochs * pair_epoch, pair_epoch};
+    r[1] = {out_chan, out_chan ? (size_t)nepochs * chan_epoch : 0, chan_epoch};
+    p->conn_tiles = nw::host::conn_tiles(ia, ib, npairs, nullptr);
+    return place_sums(p, r, 2, p->conn_tiles.data(), p->conn_tiles.size() * sizeof(nw::ConnTile), (const char**)tiles, false,
+                      std::string(who) + ": the fp64 sums of " + std::to_string(nepochs) + " epochs, " +
+                          std::to_string(npairs) + " pairs and " + std::to_string(out_chan ? nchan : 0) + " channels");
+}
+
+// Over-time connectivity (nw_execute_conn_time): per chunk nw_conn_time_kernel reduces every pair's
+// products along the window's `count` samples t0 + j * step and writes the chunk's epochs' slice of the
+// (E, P, F) sums, nw_conn_time_power_kernel the (E, C, F) power sums.  Every value is written by exactly
+// one block of one launch: no memset.
+int execute_conn_time(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ia,
+                      const int32_t* ib, int64_t npairs, int64_t t0, int64_t t1, int64_t step, void* out_sum,
+                      void* out_power, int out_kind, bool host) {
+    const int mode = nw::sum_mode(out_kind);
+    const int64_t count = nw::conn_time_count(t0, t1, step);
+    SumRegion r[2];
+    const nw::ConnTile* tiles = nullptr;
+    NW_TRY(place_time_sums(p, "nw_execute_conn_time", r, nepochs, nchan, ia, ib, npairs, out_sum,
+                           mode == nw::SUM_LAG ? 4 : 2, out_power, 1, &tiles));
+    const bool xcd = xcd_order();
+    log_time_sums(p, out_name(out_kind), nepochs, nchan, npairs, t0, t1, step, host);
+    p->stats.reduce_path = NW_REDUCE_CONN_TIME;
+    return run_epoch_chunks(p, d, x, nepochs, nchan, r, 2, host, [&](int64_t e0, int64_t ec, void* rows) -> int {
+        if (npairs == 0 && !r[1].dev) return NW_OK;
+        return NW_KERNEL_STAGE(p, ST_EPI, true,
+                               nw::launch_conn_time(p->dtype, mode, rows, r[0].at(e0), (double*)r[1].at(e0), tiles,
+                                                    (int)p->conn_tiles.size(), ec, nchan, p->nfreq, p->n_out(), npairs,
+                                                    t0, count, step, xcd, p->stream));
+    });
+}
+
+// Envelope correlation (nw_execute_env_time): as execute_conn_time with nw_env_time_kernel's pair sums
+// (1 or 6 fp64 per (e, p, f)) and nw_env_chan_kernel's per-channel sums (2 fp64 per (e, c, f)).
+int execute_env_time(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ia,
+                     const int32_t* ib, int64_t npairs, int64_t t0, int64_t t1, int64_t step, void* out_pair,
+                     void* out_chan, int env, bool host) {
+    const int64_t count = nw::conn_time_count(t0, t1, step);
+    SumRegion r[2];
+    const nw::ConnTile* tiles = nullptr;
+    NW_TRY(place_time_sums(p, "nw_execute_env_time", r, nepochs, nchan, ia, ib, npairs, out_pair,
+                           nw::env_pair_values(env), out_chan, 2, &tiles));
+    const bool xcd = xcd_order();
+    log_time_sums(p, env == NW_ENV_ORTH ? "env_orth_sum" : "env_sum", nepochs, nchan, npairs, t0, t1, step, host);
+    p->stats.reduce_path = NW_REDUCE_ENV;
+    return run_epoch_chunks(p, d, x, nepochs, nchan, r, 2, host, [&](int64_t e0, int64_t ec, void* rows) -> int {
+        if (npairs == 0 && !r[1].dev) return NW_OK;
+        return NW_KERNEL_STAGE(p, ST_EPI, true,
+                               nw::launch_env_time(p->dtype, env, rows, r[0].at(e0), (double*)r[1].at(e0), tiles,
+                                                   (int)p->conn_tiles.size(), ec, nchan, p->nfreq, p->n_out(), npairs,
+                                                   t0, count, step, xcd, p->stream));
+    });
+}
+
+// Phase-amplitude coupling (nw_execute_pac): per chunk nw_pac_kernel reduces every pair's |y_a| u_p
+// products along the window's `count` samples for every listed (phase, amplitude) scale and writes the
+// chunk's epochs' slice of the (E, P, nph, nam) sums, nw_pac_rows_kernel the per-channel sums.  The blob is
+// the pair and scale lists.  Every value is written by exactly one block of one launch: no memset.
 int execute_pac(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ip,
                 const int32_t* ia, int64_t npairs, const int32_t* fph, int nph, const int32_t* fam, int nam,
                 int64_t t0, int64_t t1, int64_t step, void* out_m, void* out_amp, void* out_phase, bool host) {
     const int64_t count = nw::conn_time_count(t0, t1, step);
-    const int64_t fn = (int64_t)p->nfreq * p->n_out();
     const size_t m_epoch = (size_t)npairs * nph * nam * 2 * sizeof(double);        // of one epoch
     const size_t amp_epoch = (size_t)nchan * nam * 2 * sizeof(double);
     const size_t phase_epoch = (size_t)nchan * nph * 2 * sizeof(double);
-    const size_t m_bytes = (size_t)nepochs * m_epoch;
-    const size_t amp_bytes = out_amp ? (size_t)nepochs * amp_epoch : 0;
-    const size_t phase_bytes = out_phase ? (size_t)nepochs * phase_epoch : 0;
-    const size_t acc_bytes = m_bytes + amp_bytes + phase_bytes;   // multiples of 16
+    SumRegion r[3] = {{out_m, (size_t)nepochs * m_epoch, m_epoch},
+                      {out_amp, out_amp ? (size_t)nepochs * amp_epoch : 0, amp_epoch},
+                      {out_phase, out_phase ? (size_t)nepochs * phase_epoch : 0, phase_epoch}};
     std::vector<int32_t>& lists = p->pac_lists;                   // ip, ia, fph, fam
     lists.clear();
     lists.insert(lists.end(), ip, ip + npairs);
     lists.insert(lists.end(), ia, ia + npairs);
     lists.insert(lists.end(), fph, fph + nph);
     lists.insert(lists.end(), fam, fam + nam);
-    const size_t list_bytes = lists.size() * sizeof(int32_t);
-    const int got = p->d_acc.ensure(acc_bytes + list_bytes + 16);
-    if (got != NW_OK && got != NW_E_NOMEM) return got;
-    if (got == NW_E_NOMEM)
-        return fail(NW_E_NOMEM, "nw_execute_pac: the fp64 sums of " + std::to_string(nepochs) + " epochs, " +
-                                    std::to_string(npairs) + " pairs and " + std::to_string(nph) + " x " +
-                                    std::to_string(nam) + " scales need " + std::to_string(acc_bytes + list_bytes + 16) +
-                                    " bytes of device memory: " + g_last_error);
-    char* const m = p->d_acc.at(0);
-    char* const amp = out_amp ? p->d_acc.at(m_bytes) : nullptr;
-    char* const phase = out_phase ? p->d_acc.at(m_bytes + amp_bytes) : nullptr;
-    const int32_t* const d_ip = (const int32_t*)p->d_acc.at(acc_bytes);
+    const char* d_lists = nullptr;
+    NW_TRY(place_sums(p, r, 3, lists.data(), lists.size() * sizeof(int32_t), &d_lists, false,
+                      "nw_execute_pac: the fp64 sums of " + std::to_string(nepochs) + " epochs, " + std::to_string(npairs) +
+                          " pairs and " + std::to_string(nph) + " x " + std::to_string(nam) + " scales"));
+    const int32_t* const d_ip = (const int32_t*)d_lists;
     const int32_t* const d_ia = d_ip + npairs;
     const int32_t* const d_fph = d_ia + npairs;
     const int32_t* const d_fam = d_fph + nph;
-    if (list_bytes) NW_HIP(hipMemcpyAsync((void*)d_ip, lists.data(), list_bytes, hipMemcpyHostToDevice, p->stream));
-    const bool xcd = !std::getenv("NW_CONN_PLAIN_ORDER");
-    const int64_t per = p->max_batch / nchan;
+    const bool xcd = xcd_order();
     nw_logf(1, "plan %p: pac sums, %lld epochs x %d channels, %lld pairs, %d phase x %d amplitude scales in %lld tiles "
                "(%lld epochs per chunk), window [%lld, %lld) step %lld of %lld samples, %s buffers: per-signal rows per "
                "chunk, every (epoch, pair, phase scale, amplitude scale) summed over its %lld samples in fp64 in lane "
                "order",
             (void*)p, (long long)nepochs, nchan, (long long)npairs, nph, nam, (long long)nw::pac_tiles(nph, nam),
-            (long long)per, (long long)t0, (long long)t1, (long long)step, (long long)p->n_out(),
+            (long long)(p->max_batch / nchan), (long long)t0, (long long)t1, (long long)step, (long long)p->n_out(),
             host ? "host" : "device", (long long)count);
     p->stats.reduce_path = NW_REDUCE_PAC;
-    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
-    if (p->form == FORM_ROCFFT) {
-        NW_TRY(need_Y(p, p->nfreq));
-        scratch = p->d_Y.ptr;
-    } else {
-        NW_TRY(p->d_out.ensure((size_t)p->max_batch * fn * 2 * p->esz));
-        scratch = p->d_out.ptr;
-    }
-    const size_t epoch_bytes = (size_t)nchan * p->n * p->esz;
-    for (int64_t e0 = 0; e0 < nepochs; e0 += per) {
-        const int64_t ec = std::min<int64_t>(per, nepochs - e0);
-        const void* xs = (const char*)x + (size_t)e0 * epoch_bytes;
-        if (host) {
-            NW_TRY(staged(p, ST_COPY, [&] {
-                NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, (size_t)ec * epoch_bytes, hipMemcpyHostToDevice, p->stream));
-                return NW_OK;
-            }));
-            xs = p->d_x.ptr;
-        }
-        NW_TRY(run_chunk(p, d, xs, ec * nchan, scratch, NW_OUT_CWT, false));
-        // chained: run_chunk ends with a stage
-        if (acc_bytes)
-            NW_TRY(NW_KERNEL_STAGE(
-                p, ST_EPI, true,
-                nw::launch_pac(p->dtype, scratch, m + (size_t)e0 * m_epoch, amp ? amp + (size_t)e0 * amp_epoch : nullptr,
-                               phase ? phase + (size_t)e0 * phase_epoch : nullptr, d_ip, d_ia, d_fph, d_fam, ec, nchan,
-                               p->nfreq, p->n_out(), npairs, nph, nam, t0, count, step, xcd, p->stream)));
-        p->stats.chunks++;
-    }
-    const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (m_bytes) NW_HIP(hipMemcpyAsync(out_m, m, m_bytes, back, p->stream));
-    if (amp_bytes) NW_HIP(hipMemcpyAsync(out_amp, amp, amp_bytes, back, p->stream));
-    if (phase_bytes) NW_HIP(hipMemcpyAsync(out_phase, phase, phase_bytes, back, p->stream));
-    p->stats.executes++;
-    if (host) {
-        NW_HIP(hipStreamSynchronize(p->stream));
-        NW_TRY(resolve_timing(p));
-    }
-    return NW_OK;
+    return run_epoch_chunks(p, d, x, nepochs, nchan, r, 3, host, [&](int64_t e0, int64_t ec, void* rows) -> int {
+        if (!(r[0].bytes + r[1].bytes + r[2].bytes)) return NW_OK;
+        return NW_KERNEL_STAGE(p, ST_EPI, true,
+                               nw::launch_pac(p->dtype, rows, r[0].at(e0), r[1].at(e0), r[2].at(e0), d_ip, d_ia, d_fph,
+                                              d_fam, ec, nchan, p->nfreq, p->n_out(), npairs, nph, nam, t0, count, step,
+                                              xcd, p->stream));
+    });
 }
 
 // the pair list of nw_conn_tiles / nw_execute_conn: indices inside [0, nchan)
@@ -1223,6 +1196,55 @@ int check_pairs(const char* who, int32_t nchan, const int32_t* ia, const int32_t
         if (ia[q] < 0 || ia[q] >= nchan || ib[q] < 0 || ib[q] >= nchan)
             return fail(NW_E_INVALID, std::string(who) + ": pair " + std::to_string(q) + " = (" + std::to_string(ia[q]) +
                                           ", " + std::to_string(ib[q]) + ") is outside [0, " + std::to_string(nchan) + ")");
+    return NW_OK;
+}
+
+// the checks the epoch-chunk calls share, in the order they always had; null_arg and kind_error (the
+// call's complaint about its out_kind or env_kind, or null) are the caller's own findings
+int check_epoch_call(const char* who, const nw_plan* p, bool null_arg, const char* kind_error, int mem, int64_t nepochs,
+                     int32_t nchan, const int32_t* ia, const int32_t* ib, int64_t npairs) {
+    const std::string w = std::string(who) + ": ";
+    if (null_arg) return fail(NW_E_INVALID, w + "null argument");
+    if (!p->has_wavelet) return fail(NW_E_STATE, w + "nw_plan_set_wavelet first");
+    if (kind_error) return fail(NW_E_INVALID, w + kind_error);
+    if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, w + "bad mem");
+    if (nepochs < 0) return fail(NW_E_INVALID, w + "nepochs < 0");
+    return check_pairs(who, nchan, ia, ib, npairs);
+}
+
+// a chunk holds whole epochs
+int check_chunk(const char* who, const nw_plan* p, int32_t nchan) {
+    if (p->max_batch < nchan)
+        return fail(NW_E_INVALID, std::string(who) + ": the plan's max_batch (" + std::to_string(p->max_batch) +
+                                      ") must be >= nchan (" + std::to_string(nchan) +
+                                      "): a chunk holds max_batch / nchan epochs");
+    return NW_OK;
+}
+
+// the window [t0, t1) and its step of the over-time sums
+int check_window(const char* who, int64_t n_out, int64_t t0, int64_t t1, int64_t step) {
+    if (step < 1) return fail(NW_E_INVALID, std::string(who) + ": step (" + std::to_string(step) + ") must be >= 1");
+    if (t0 < 0 || t0 > t1 || t1 > n_out)
+        return fail(NW_E_INVALID, std::string(who) + ": the window [" + std::to_string(t0) + ", " + std::to_string(t1) +
+                                      ") must satisfy 0 <= t0 <= t1 <= n_out (" + std::to_string(n_out) + ")");
+    return NW_OK;
+}
+
+// the out_kind of nw_execute_conn and nw_execute_conn_time: null, or what is wrong with it
+const char* conn_kind_error(int out_kind, const void* out_power) {
+    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM && out_kind != NW_OUT_LAG_SUM)
+        return "out_kind must be NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM or NW_OUT_LAG_SUM";
+    if (out_kind == NW_OUT_PLV_SUM && out_power) return "NW_OUT_PLV_SUM forms no power sums: out_power must be NULL";
+    if (out_kind == NW_OUT_LAG_SUM && out_power) return "NW_OUT_LAG_SUM forms no power sums: out_power must be NULL";
+    return nullptr;
+}
+
+// the start of an execute call (under the caller's DeviceGuard): the rows of this call
+int begin_execute(nw_plan* p, nw::WDesc* d) {
+    p->executed = true;
+    *d = exec_rows(p);
+    // settle the form of a tentative length before any buffer choice
+    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, *d));
     return NW_OK;
 }
 
@@ -1703,28 +1725,12 @@ int nw_conn_tiles(int32_t nchan, const int32_t* ia, const int32_t* ib, int64_t n
 
 int nw_execute_conn(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ia, const int32_t* ib,
                     int64_t npairs, void* out_cross, void* out_power, int out_kind, int mem) {
-    if (!p || (!x && nepochs > 0) || (!out_cross && npairs > 0))
-        return fail(NW_E_INVALID, "nw_execute_conn: null argument");
-    if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_conn: nw_plan_set_wavelet first");
-    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM && out_kind != NW_OUT_LAG_SUM)
-        return fail(NW_E_INVALID,
-                    "nw_execute_conn: out_kind must be NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM or NW_OUT_LAG_SUM");
-    if (out_kind == NW_OUT_PLV_SUM && out_power)
-        return fail(NW_E_INVALID, "nw_execute_conn: NW_OUT_PLV_SUM forms no power sums: out_power must be NULL");
-    if (out_kind == NW_OUT_LAG_SUM && out_power)
-        return fail(NW_E_INVALID, "nw_execute_conn: NW_OUT_LAG_SUM forms no power sums: out_power must be NULL");
-    if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_conn: bad mem");
-    if (nepochs < 0) return fail(NW_E_INVALID, "nw_execute_conn: nepochs < 0");
-    NW_TRY(check_pairs("nw_execute_conn", nchan, ia, ib, npairs));
-    if (p->max_batch < nchan)
-        return fail(NW_E_INVALID, "nw_execute_conn: the plan's max_batch (" + std::to_string(p->max_batch) +
-                                      ") must be >= nchan (" + std::to_string(nchan) +
-                                      "): a chunk holds max_batch / nchan epochs");
+    NW_TRY(check_epoch_call("nw_execute_conn", p, !p || (!x && nepochs > 0) || (!out_cross && npairs > 0),
+                            conn_kind_error(out_kind, out_power), mem, nepochs, nchan, ia, ib, npairs));
+    NW_TRY(check_chunk("nw_execute_conn", p, nchan));
     DeviceGuard guard(p->device);
-    p->executed = true;
-    const nw::WDesc d = exec_rows(p);
-    // settle the form of a tentative length before any buffer choice
-    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
+    nw::WDesc d;
+    NW_TRY(begin_execute(p, &d));
     nw_logf(1, "plan %p: execute conn %s, %lld epochs x %d channels, %lld pairs, %s buffers", (void*)p, out_name(out_kind),
             (long long)nepochs, (int)nchan, (long long)npairs, mem == NW_MEM_HOST ? "host" : "device");
     NW_TRY(execute_conn(p, d, x, nepochs, nchan, ia, ib, npairs, out_cross, out_power, out_kind, mem == NW_MEM_HOST));
@@ -1733,10 +1739,7 @@ int nw_execute_conn(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, c
 
 int nw_conn_time_count(int64_t n_out, int64_t t0, int64_t t1, int64_t step, int64_t* count) {
     if (!count) return fail(NW_E_INVALID, "nw_conn_time_count: null argument");
-    if (step < 1) return fail(NW_E_INVALID, "nw_conn_time_count: step (" + std::to_string(step) + ") must be >= 1");
-    if (t0 < 0 || t0 > t1 || t1 > n_out)
-        return fail(NW_E_INVALID, "nw_conn_time_count: the window [" + std::to_string(t0) + ", " + std::to_string(t1) +
-                                      ") must satisfy 0 <= t0 <= t1 <= n_out (" + std::to_string(n_out) + ")");
+    NW_TRY(check_window("nw_conn_time_count", n_out, t0, t1, step));
     *count = nw::conn_time_count(t0, t1, step);
     return NW_OK;
 }
@@ -1744,32 +1747,14 @@ int nw_conn_time_count(int64_t n_out, int64_t t0, int64_t t1, int64_t step, int6
 int nw_execute_conn_time(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ia, const int32_t* ib,
                          int64_t npairs, int64_t t0, int64_t t1, int64_t step, void* out_sum, void* out_power,
                          int out_kind, int mem) {
-    if (!p || (!x && nepochs > 0) || (!out_sum && npairs > 0 && nepochs > 0))
-        return fail(NW_E_INVALID, "nw_execute_conn_time: null argument");
-    if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_conn_time: nw_plan_set_wavelet first");
-    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM && out_kind != NW_OUT_LAG_SUM)
-        return fail(NW_E_INVALID,
-                    "nw_execute_conn_time: out_kind must be NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM or NW_OUT_LAG_SUM");
-    if (out_kind == NW_OUT_PLV_SUM && out_power)
-        return fail(NW_E_INVALID, "nw_execute_conn_time: NW_OUT_PLV_SUM forms no power sums: out_power must be NULL");
-    if (out_kind == NW_OUT_LAG_SUM && out_power)
-        return fail(NW_E_INVALID, "nw_execute_conn_time: NW_OUT_LAG_SUM forms no power sums: out_power must be NULL");
-    if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_conn_time: bad mem");
-    if (nepochs < 0) return fail(NW_E_INVALID, "nw_execute_conn_time: nepochs < 0");
-    NW_TRY(check_pairs("nw_execute_conn_time", nchan, ia, ib, npairs));
-    if (p->max_batch < nchan)
-        return fail(NW_E_INVALID, "nw_execute_conn_time: the plan's max_batch (" + std::to_string(p->max_batch) +
-                                      ") must be >= nchan (" + std::to_string(nchan) +
-                                      "): a chunk holds max_batch / nchan epochs");
-    if (step < 1) return fail(NW_E_INVALID, "nw_execute_conn_time: step (" + std::to_string(step) + ") must be >= 1");
-    if (t0 < 0 || t0 > t1 || t1 > p->n_out())
-        return fail(NW_E_INVALID, "nw_execute_conn_time: the window [" + std::to_string(t0) + ", " + std::to_string(t1) +
-                                      ") must satisfy 0 <= t0 <= t1 <= n_out (" + std::to_string(p->n_out()) + ")");
+    const char* const who = "nw_execute_conn_time";
+    NW_TRY(check_epoch_call(who, p, !p || (!x && nepochs > 0) || (!out_sum && npairs > 0 && nepochs > 0),
+                            conn_kind_error(out_kind, out_power), mem, nepochs, nchan, ia, ib, npairs));
+    NW_TRY(check_chunk(who, p, nchan));
+    NW_TRY(check_window(who, p->n_out(), t0, t1, step));
     DeviceGuard guard(p->device);
-    p->executed = true;
-    const nw::WDesc d = exec_rows(p);
-    // settle the form of a tentative length before any buffer choice
-    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
+    nw::WDesc d;
+    NW_TRY(begin_execute(p, &d));
     NW_TRY(execute_conn_time(p, d, x, nepochs, nchan, ia, ib, npairs, t0, t1, step, out_sum, out_power, out_kind,
                              mem == NW_MEM_HOST));
     return dcheck_collect(p->stream);
@@ -1778,41 +1763,27 @@ int nw_execute_conn_time(nw_plan* p, const void* x, int64_t nepochs, int32_t nch
 int nw_execute_env_time(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ia, const int32_t* ib,
                         int64_t npairs, int64_t t0, int64_t t1, int64_t step, void* out_pair, void* out_chan,
                         int env_kind, int mem) {
-    if (!p || (!x && nepochs > 0) || (!out_pair && npairs > 0 && nepochs > 0))
-        return fail(NW_E_INVALID, "nw_execute_env_time: null argument");
-    if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_env_time: nw_plan_set_wavelet first");
-    if (env_kind != NW_ENV_PLAIN && env_kind != NW_ENV_ORTH)
-        return fail(NW_E_INVALID, "nw_execute_env_time: env_kind must be NW_ENV_PLAIN or NW_ENV_ORTH");
-    if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_env_time: bad mem");
-    if (nepochs < 0) return fail(NW_E_INVALID, "nw_execute_env_time: nepochs < 0");
-    NW_TRY(check_pairs("nw_execute_env_time", nchan, ia, ib, npairs));
-    if (p->max_batch < nchan)
-        return fail(NW_E_INVALID, "nw_execute_env_time: the plan's max_batch (" + std::to_string(p->max_batch) +
-                                      ") must be >= nchan (" + std::to_string(nchan) +
-                                      "): a chunk holds max_batch / nchan epochs");
-    if (step < 1) return fail(NW_E_INVALID, "nw_execute_env_time: step (" + std::to_string(step) + ") must be >= 1");
-    if (t0 < 0 || t0 > t1 || t1 > p->n_out())
-        return fail(NW_E_INVALID, "nw_execute_env_time: the window [" + std::to_string(t0) + ", " + std::to_string(t1) +
-                                      ") must satisfy 0 <= t0 <= t1 <= n_out (" + std::to_string(p->n_out()) + ")");
+    const char* const who = "nw_execute_env_time";
+    NW_TRY(check_epoch_call(who, p, !p || (!x && nepochs > 0) || (!out_pair && npairs > 0 && nepochs > 0),
+                            env_kind != NW_ENV_PLAIN && env_kind != NW_ENV_ORTH
+                                ? "env_kind must be NW_ENV_PLAIN or NW_ENV_ORTH" : nullptr,
+                            mem, nepochs, nchan, ia, ib, npairs));
+    NW_TRY(check_chunk(who, p, nchan));
+    NW_TRY(check_window(who, p->n_out(), t0, t1, step));
     DeviceGuard guard(p->device);
-    p->executed = true;
-    const nw::WDesc d = exec_rows(p);
-    // settle the form of a tentative length before any buffer choice
-    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
-    NW_TRY(execute_conn_time(p, d, x, nepochs, nchan, ia, ib, npairs, t0, t1, step, out_pair, out_chan, NW_OUT_CROSS_SUM,
-                             mem == NW_MEM_HOST, env_kind));
+    nw::WDesc d;
+    NW_TRY(begin_execute(p, &d));
+    NW_TRY(execute_env_time(p, d, x, nepochs, nchan, ia, ib, npairs, t0, t1, step, out_pair, out_chan, env_kind,
+                            mem == NW_MEM_HOST));
     return dcheck_collect(p->stream);
 }
 
 int nw_execute_pac(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ip, const int32_t* ia,
                    int64_t npairs, const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam, int64_t t0,
                    int64_t t1, int64_t step, void* out_m, void* out_amp, void* out_phase, int mem) {
-    if (!p || (!x && nepochs > 0) || (!out_m && npairs > 0 && nepochs > 0 && nph > 0 && nam > 0))
-        return fail(NW_E_INVALID, "nw_execute_pac: null argument");
-    if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_pac: nw_plan_set_wavelet first");
-    if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_pac: bad mem");
-    if (nepochs < 0) return fail(NW_E_INVALID, "nw_execute_pac: nepochs < 0");
-    NW_TRY(check_pairs("nw_execute_pac", nchan, ip, ia, npairs));
+    const char* const who = "nw_execute_pac";
+    NW_TRY(check_epoch_call(who, p, !p || (!x && nepochs > 0) || (!out_m && npairs > 0 && nepochs > 0 && nph > 0 && nam > 0),
+                            nullptr, mem, nepochs, nchan, ip, ia, npairs));
     if (nph < 0 || nam < 0) return fail(NW_E_INVALID, "nw_execute_pac: nph < 0 or nam < 0");
     if ((nph > 0 && !fph) || (nam > 0 && !fam)) return fail(NW_E_INVALID, "nw_execute_pac: null scale list");
     for (int which = 0; which < 2; ++which) {
@@ -1823,24 +1794,16 @@ int nw_execute_pac(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, co
                                               " scale " + std::to_string(i) + " = " + std::to_string(f[i]) +
                                               " is outside [0, " + std::to_string(p->nfreq) + ")");
     }
-    if (p->max_batch < nchan)
-        return fail(NW_E_INVALID, "nw_execute_pac: the plan's max_batch (" + std::to_string(p->max_batch) +
-                                      ") must be >= nchan (" + std::to_string(nchan) +
-                                      "): a chunk holds max_batch / nchan epochs");
-    if (step < 1) return fail(NW_E_INVALID, "nw_execute_pac: step (" + std::to_string(step) + ") must be >= 1");
-    if (t0 < 0 || t0 > t1 || t1 > p->n_out())
-        return fail(NW_E_INVALID, "nw_execute_pac: the window [" + std::to_string(t0) + ", " + std::to_string(t1) +
-                                      ") must satisfy 0 <= t0 <= t1 <= n_out (" + std::to_string(p->n_out()) + ")");
+    NW_TRY(check_chunk(who, p, nchan));
+    NW_TRY(check_window(who, p->n_out(), t0, t1, step));
     // the grid of one chunk's launch (block indices are 32-bit)
     const int64_t blocks = nw::pac_blocks(std::max<int64_t>(p->max_batch / nchan, 1), npairs, nw::pac_tiles(nph, nam), true);
     if (blocks < 0 || blocks > 0x7fffffff)
         return fail(NW_E_INVALID, "nw_execute_pac: " + std::to_string(npairs) + " pairs x " + std::to_string(nph) + " x " +
                                       std::to_string(nam) + " scales per chunk need more than 2^31 - 1 blocks");
     DeviceGuard guard(p->device);
-    p->executed = true;
-    const nw::WDesc d = exec_rows(p);
-    // settle the form of a tentative length before any buffer choice
-    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
+    nw::WDesc d;
+    NW_TRY(begin_execute(p, &d));
     NW_TRY(execute_pac(p, d, x, nepochs, nchan, ip, ia, npairs, fph, nph, fam, nam, t0, t1, step, out_m, out_amp,
                        out_phase, mem == NW_MEM_HOST));
     return dcheck_collect(p->stream);

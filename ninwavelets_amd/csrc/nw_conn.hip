@@ -26,36 +26,22 @@
 // nw_conn_power_kernel adds P_cc: one thread per (c, f, t).
 #include <algorithm>
 
-#include "nw_dcheck.h"
-#include "nw_internal.h"
+#include "nw_reduce_dev.h"
 
 namespace nw {
 namespace {
 
-// a rounded fp64 product that the compiler may not fuse into a following add (as nw_kernels.hip)
-__device__ __forceinline__ double mul_nc(double a, double b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ double add_nc(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-
-constexpr int kConnThreads = kConnWaves * 64;
-constexpr int kConnStage = kConnCh / kConnWaves;   // channels a wave stages per epoch
-
-// a pair's accumulators: S_p (Phi_p), or the four phase-lag sums
-struct ConnAcc2 { double re, im; };
-struct ConnAcc4 { double l0, l1, l2, l3; };
-
+// (the SUM_* staging, accumulators and per-pair terms are the policies of nw_reduce_dev.h, shared with
+// nw_conn_time_kernel; the epoch loop tiles otherwise than the over-time skeleton and stays here.  The
+// accumulators are an array of structs: two plain double[16] are rewritten into <16 x double> vectors
+// before the loops unroll and then live in 32-register tuples, 1412 B of scratch; tools/regs.py)
 template <typename T, int MODE>
 __global__ __launch_bounds__(kConnThreads) void nw_conn_accumulate_kernel(
     const cplx<T>* __restrict__ src, double2* __restrict__ cross, const ConnTile* __restrict__ tiles, int ntiles,
     int64_t ec, int nchan, int nfreq, int64_t n_out, int64_t npairs, int64_t nunits, int xcd) {
     static_assert(kConnTileN == 64, "lane = sample of the tile");
-    constexpr bool PLV = MODE == SUM_PLV, LAG = MODE == SUM_LAG;
-    constexpr int NV = LAG ? 2 : 1;   // double2 values per pair and point in `cross`
+    using P = SumPolicy<MODE>;
+    constexpr int NV = P::kOut;   // double2 values per pair and point in `cross`
     __shared__ double stage[2][kConnCh][2][kConnTileN];   // [buffer][slot][re, im][sample]: 32 KiB
 
     const ConnSlot sl = conn_slot((int64_t)blockIdx.x, ntiles, xcd != 0);
@@ -74,26 +60,17 @@ __global__ __launch_bounds__(kConnThreads) void nw_conn_accumulate_kernel(
     const int64_t fn = (int64_t)nfreq * n_out;
     const int64_t ft = (int64_t)f * n_out + t;
 
-    // (an array of structs: two plain double[16] are rewritten into <16 x double> vectors before the
-    // loops unroll and then live in 32-register tuples, 1412 B of scratch; tools/regs.py)
     // SUM_LAG: four doubles per pair, 128 accumulator registers a lane
-    std::conditional_t<LAG, ConnAcc4, ConnAcc2> acc[kConnPerWave];
+    typename P::Acc acc[kConnPerWave];
 #pragma unroll
     for (int k = 0; k < kConnPerWave; ++k) {
         const int j = w + k * kConnWaves;
-        if constexpr (LAG) acc[k].l0 = acc[k].l1 = acc[k].l2 = acc[k].l3 = 0.0;
-        else acc[k].re = acc[k].im = 0.0;
+        P::zero(acc[k]);
         if (j < np && live) {
             const int64_t o = tile.out[j];
             NW_DCHECK(o >= 0 && o < npairs && o * fn + ft < npairs * fn);
-            if constexpr (LAG) {
-                NW_DCHECK(NV * (o * fn + ft) + 1 < NV * npairs * fn);
-                const double2 u = cross[NV * (o * fn + ft)], v = cross[NV * (o * fn + ft) + 1];
-                acc[k].l0 = u.x, acc[k].l1 = u.y, acc[k].l2 = v.x, acc[k].l3 = v.y;
-            } else {
-                const double2 v = cross[o * fn + ft];
-                acc[k].re = v.x, acc[k].im = v.y;
-            }
+            NW_DCHECK(NV * (o * fn + ft) + NV - 1 < NV * npairs * fn);
+            P::load(acc[k], cross + NV * (o * fn + ft));
         }
     }
 
@@ -114,15 +91,7 @@ __global__ __launch_bounds__(kConnThreads) void nw_conn_accumulate_kernel(
 #pragma unroll
         for (int q = 0; q < kConnStage; ++q) {
             const int s = w + q * kConnWaves;
-            if (s < nch) {
-                double re = (double)in[q].re, im = (double)in[q].im;
-                if constexpr (PLV) {
-                    const double m = hypot(re, im);
-                    re /= m, im /= m;
-                }
-                stage[buf][s][0][lane] = re;
-                stage[buf][s][1][lane] = im;
-            }
+            if (s < nch) P::stage(in[q], stage[buf][s], lane);
         }
     };
 
@@ -141,18 +110,7 @@ __global__ __launch_bounds__(kConnThreads) void nw_conn_accumulate_kernel(
             if (j < np) {
                 const int a = tile.sa[j], b = tile.sb[j];
                 NW_DCHECK(a >= 0 && a < nch && b >= 0 && b < nch);
-                const double ar = stage[cur][a][0][lane], ai = stage[cur][a][1][lane];
-                const double br = stage[cur][b][0][lane], bi = stage[cur][b][1][lane];
-                if constexpr (LAG) {
-                    const double m = add_nc(mul_nc(ai, br), -mul_nc(ar, bi));
-                    acc[k].l0 = add_nc(acc[k].l0, m);
-                    acc[k].l1 = add_nc(acc[k].l1, fabs(m));
-                    acc[k].l2 = add_nc(acc[k].l2, mul_nc(m, m));
-                    acc[k].l3 = add_nc(acc[k].l3, lag_sgn(m));
-                } else {
-                    acc[k].re += add_nc(mul_nc(ar, br), mul_nc(ai, bi));
-                    acc[k].im += add_nc(mul_nc(ai, br), -mul_nc(ar, bi));
-                }
+                P::term(acc[k], stage[cur][a], stage[cur][b], lane);
             }
         }
         // the other buffer was last read before the previous barrier
@@ -166,13 +124,8 @@ __global__ __launch_bounds__(kConnThreads) void nw_conn_accumulate_kernel(
         if (j < np && live) {
             const int64_t o = tile.out[j];
             NW_DCHECK(o >= 0 && o < npairs && o * fn + ft < npairs * fn);
-            if constexpr (LAG) {
-                NW_DCHECK(NV * (o * fn + ft) + 1 < NV * npairs * fn);
-                cross[NV * (o * fn + ft)] = double2{acc[k].l0, acc[k].l1};
-                cross[NV * (o * fn + ft) + 1] = double2{acc[k].l2, acc[k].l3};
-            } else {
-                cross[o * fn + ft] = double2{acc[k].re, acc[k].im};
-            }
+            NW_DCHECK(NV * (o * fn + ft) + NV - 1 < NV * npairs * fn);
+            P::store(acc[k], cross + NV * (o * fn + ft));
         }
     }
 }
@@ -190,7 +143,7 @@ __global__ __launch_bounds__(256) void nw_conn_power_kernel(const cplx<T>* __res
             NW_DCHECK(e * count + i < ec * count);
             const cplx<T> v = src[e * count + i];
             const double re = (double)v.re, im = (double)v.im;
-            p += add_nc(mul_nc(re, re), mul_nc(im, im));
+            p += power_term(re, im);
         }
         power[i] = p;
     }

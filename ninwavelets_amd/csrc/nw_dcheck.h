@@ -14,6 +14,7 @@ namespace nw {
 using DcheckTake = hipError_t (*)(unsigned* fails, unsigned* site, const char** file);
 int dcheck_register(DcheckTake fn);   // nw_api.cpp; called at static initialisation
 constexpr unsigned kDcheckHeaderSite = 100000;   // sites in nw_fft_dev.h: line + this
+constexpr unsigned kDcheckReduceSite = 200000;   // sites in nw_reduce_dev.h: line + this
 }  // namespace nw
 
 #ifdef NW_DEBUG_BOUNDS
@@ -47,11 +48,18 @@ const int g_nw_dcheck_registered = nw::dcheck_register(&nw_dcheck_take);
     do {                                                                                \
         if (!(__VA_ARGS__)) nw_dcheck_fail(nw::kDcheckHeaderSite + (unsigned)__LINE__);  \
     } while (0)
+#define NW_DCHECK_R(...)                                                                \
+    do {                                                                                \
+        if (!(__VA_ARGS__)) nw_dcheck_fail(nw::kDcheckReduceSite + (unsigned)__LINE__);  \
+    } while (0)
 #else
 #define NW_DCHECK(...) \
     do {               \
     } while (0)
 #define NW_DCHECK_H(...) \
+    do {                 \
+    } while (0)
+#define NW_DCHECK_R(...) \
     do {                 \
     } while (0)
 #endif

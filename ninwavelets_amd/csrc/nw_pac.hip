@@ -25,28 +25,10 @@
 // (e, pair, i, k) belongs to exactly one block of one launch: no memset, no read-modify-write.
 #include <algorithm>
 
-#include "nw_dcheck.h"
-#include "nw_internal.h"
+#include "nw_reduce_dev.h"
 
 namespace nw {
 namespace {
-
-// a rounded fp64 product that the compiler may not fuse into a following add (as nw_conn_time.hip)
-__device__ __forceinline__ double mul_nc(double a, double b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ double add_nc(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-
-// the fold of the 64 lane values: every lane ends with the same sum, in the contract's order
-__device__ __forceinline__ double fold64(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = add_nc(v, __shfl_xor(v, d, 64));
-    return v;
-}
 
 constexpr int kPacThreads = kPacWaves * 64;
 
@@ -100,7 +82,7 @@ __global__ __launch_bounds__(kPacThreads) void nw_pac_kernel(
         }
     }
 
-    // (arrays of structs, as nw_conn_time.hip: plain double arrays end in scratch)
+    // (arrays of structs, as nw_reduce_dev.h's: plain double arrays end in scratch)
     PacAcc acc[kPacAmWave][kPacPh];
 #pragma unroll
     for (int k = 0; k < kPacAmWave; ++k)
@@ -205,42 +187,37 @@ __global__ __launch_bounds__(kPacThreads) void nw_pac_kernel(
 
 // amp[((e * C + c) * nam + k)] = {sum_j A, sum_j |y|^2} of row fam[k], phase[(e * C + c) * nph + i] =
 // sum_j u of row fph[i]: one wave per (epoch, channel, listed scale), the order of the contract; the
-// second amplitude sum is formed as nw_conn_time_power_kernel forms its power
+// second amplitude sum is formed as nw_conn_time_power_kernel forms its power (row_time_sums, nw_reduce_dev.h)
 template <typename T>
 __global__ __launch_bounds__(kPacThreads) void nw_pac_rows_kernel(
     const cplx<T>* __restrict__ src, double2* __restrict__ amp, double2* __restrict__ phase,
     const int32_t* __restrict__ fph, const int32_t* __restrict__ fam, int64_t nsig, int nfreq, int64_t n_out, int nph,
     int nam, int64_t t0, int64_t count, int64_t step) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * kPacWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t namp = amp ? nsig * nam : 0, nphs = phase ? nsig * nph : 0;
-    if (row >= namp + nphs) return;   // the whole wave
-    const bool is_amp = row < namp;
-    const int64_t r = is_amp ? row : row - namp;
-    const int nl = is_amp ? nam : nph;
-    const int64_t sig = r / nl;
-    const int f = (is_amp ? fam : fph)[r % nl];
-    NW_DCHECK(sig >= 0 && sig < nsig && f >= 0 && f < nfreq);
-    const int64_t off = (sig * nfreq + f) * n_out;
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll 4
-    for (int64_t j = lane; j < count; j += kConnTileN) {
-        const int64_t t = t0 + j * step;
-        NW_DCHECK(conn_time_lane(j) == lane && t >= 0 && t < n_out && off + t < nsig * nfreq * n_out);
-        const cplx<T> v = src[off + t];
-        const double re = (double)v.re, im = (double)v.im;
-        const double h = hypot(re, im);
-        if (is_amp) {
-            s0 = add_nc(s0, h);
-            s1 = add_nc(s1, add_nc(mul_nc(re, re), mul_nc(im, im)));
-        } else {
-            s0 = add_nc(s0, re / h);
-            s1 = add_nc(s1, im / h);
-        }
-    }
-    s0 = fold64(s0);
-    s1 = fold64(s1);
-    if (lane == 0) (is_amp ? amp : phase)[r] = double2{s0, s1};
+    row_time_sums<kPacWaves>(
+        src, namp + nphs, nsig * nfreq * n_out, n_out, t0, count, step,
+        [&](int64_t row) {
+            const bool is_amp = row < namp;
+            const int64_t r = is_amp ? row : row - namp;
+            const int nl = is_amp ? nam : nph;
+            const int64_t sig = r / nl;
+            const int f = (is_amp ? fam : fph)[r % nl];
+            NW_DCHECK(sig >= 0 && sig < nsig && f >= 0 && f < nfreq);
+            return (sig * nfreq + f) * n_out;
+        },
+        [&](int64_t row, double& s0, double& s1, double re, double im) {
+            const double h = hypot(re, im);
+            if (row < namp) {
+                s0 = add_nc(s0, h);
+                s1 = add_nc(s1, power_term(re, im));
+            } else {
+                s0 = add_nc(s0, re / h);
+                s1 = add_nc(s1, im / h);
+            }
+        },
+        [&](int64_t row, double s0, double s1) {
+            *(row < namp ? amp + row : phase + (row - namp)) = double2{s0, s1};
+        });
 }
 
 }  // namespace

@@ -571,6 +571,40 @@ def local_rank_count(env=None) -> int:
 HOST_POOL = HostPool(int(os.environ.get('NINWAVE_HOST_POOL_BYTES') or default_pool_cap()))
 
 
+def _ptr(a):
+    """The address of a device tensor or a numpy array as a ctypes argument (None: a null pointer)."""
+    if a is None:
+        return None
+    return ctypes.c_void_p(a.data_ptr()) if _is_device_tensor(a) else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _epochs(x):
+    """(E, C) of an (epochs, channels, n) input."""
+    if getattr(x, 'ndim', 0) != 3:
+        raise ValueError(f'x must be (epochs, channels, n), got shape {tuple(getattr(x, "shape", ()))}')
+    return int(x.shape[0]), int(x.shape[1])
+
+
+def _conn_kind(out_kind):
+    """(kind, lag, single) of a connectivity out_kind; single: one output and no power sums."""
+    if out_kind not in CONN_KINDS and out_kind not in LAG_KINDS:
+        raise ValueError(f"out_kind must be one of {', '.join({**CONN_KINDS, **LAG_KINDS})}; got {out_kind!r}")
+    return {**CONN_KINDS, **LAG_KINDS}[out_kind], out_kind == 'lag_sum', out_kind in ('plv_sum', 'lag_sum')
+
+
+def _unpack(out, n, what):
+    """``out`` as a list of n buffers (None: none given); ValueError(what) for anything else."""
+    if out is None:
+        return [None] * n
+    try:
+        outs = list(out)
+        if len(outs) != n:
+            raise TypeError
+    except TypeError:
+        raise ValueError(what) from None
+    return outs
+
+
 def _is_device_tensor(a) -> bool:
     return hasattr(a, 'data_ptr') and getattr(a, 'is_cuda', False)
 
@@ -745,58 +779,19 @@ class Plan:
         plv_sum.  ``lag_sum`` -> float64 (P, nfreq, n_out, 4), the phase-lag sums of every pair (see
         finalize_lag), one array or tensor as plv_sum.  The plan needs max_batch >= C (a chunk holds
         max_batch // C epochs)."""
-        if out_kind not in CONN_KINDS and out_kind not in LAG_KINDS:
-            raise ValueError(f"out_kind must be one of {', '.join({**CONN_KINDS, **LAG_KINDS})}; got {out_kind!r}")
-        kind = {**CONN_KINDS, **LAG_KINDS}[out_kind]
-        lag = out_kind == 'lag_sum'
-        plv = out_kind == 'plv_sum' or lag          # one output, no power sums
-        if getattr(x, 'ndim', 0) != 3:
-            raise ValueError(f'x must be (epochs, channels, n), got shape {tuple(getattr(x, "shape", ()))}')
-        nep, nchan = int(x.shape[0]), int(x.shape[1])
+        kind, lag, single = _conn_kind(out_kind)
+        nep, nchan = _epochs(x)
         ia, ib = check_indices(indices, nchan)
         npairs = int(ia.size)
-        fn = self.nfreq * self.n_out
-        P = ctypes.c_void_p
-        ip = (ia.ctypes.data_as(P), ib.ctypes.data_as(P))
-        if _is_device_tensor(x):
-            import torch
-            if out is None:
-                raise ValueError('device execute needs output tensors')
-            if self._check_device_input(x) != nep * nchan:
-                raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
-            cross, power = (out, None) if plv else out
-            for t, dt, count, name in ((cross, torch.float64 if lag else torch.complex128,
-                                        npairs * fn * (4 if lag else 1), 'cross'),
-                                       (power, torch.float64, nchan * fn, 'power')):
-                if t is None and name == 'power':
-                    continue
-                if not _is_device_tensor(t) or t.dtype != dt:
-                    raise ValueError(f'device output {name} must be a {dt} tensor on device {self.device}')
-                if not t.is_contiguous() or t.numel() != count:
-                    raise ValueError(f'device output {name} must be contiguous and hold {count} values')
-                if t.device.index != self.device:
-                    raise ValueError(f'device buffers must live on device {self.device}')
-            with self._ordered_with_torch(x.device):
-                L.check(L.lib().nw_execute_conn(self._h, P(x.data_ptr()), nep, nchan, *ip, npairs, P(cross.data_ptr()),
-                                                P(power.data_ptr()) if power is not None else None, kind,
-                                                L.NW_MEM_DEVICE))
-            return out
-        x = np.ascontiguousarray(x, dtype=self.dtype)
-        if x.shape[-1] != self.n:
-            raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
-        cross, power = (out, None) if plv or out is None else out
-        shapes = (((npairs, self.nfreq, self.n_out, 4), np.float64) if lag else
-                  ((npairs, self.nfreq, self.n_out), np.complex128), ((nchan, self.nfreq, self.n_out), np.float64))
-        if cross is None:
-            cross = np.empty(*shapes[0])
-        if power is None and not plv:
-            power = np.empty(*shapes[1])
-        for a, (shape, dt) in zip((cross, power), shapes):
-            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or a.size != int(np.prod(shape))):
-                raise ValueError('out must be C-contiguous arrays of the right dtype and size')
-        L.check(L.lib().nw_execute_conn(self._h, x.ctypes.data_as(P), nep, nchan, *ip, npairs, cross.ctypes.data_as(P),
-                                        None if plv else power.ctypes.data_as(P), kind, L.NW_MEM_HOST))
-        return cross if plv else (cross, power)
+        x = self._epoch_input(x, nep * nchan, out)
+        specs = [('cross', (npairs, self.nfreq, self.n_out) + ((4,) if lag else ()),
+                  np.float64 if lag else np.complex128, False),
+                 ('power', (nchan, self.nfreq, self.n_out), np.float64, True)][:1 if single else 2]
+        cross, power = (out, None) if single or out is None else out
+        # (this call alone never asked that host outputs be ndarrays)
+        outs = self._outputs(x, [cross, power], specs, ndarray_only=False)
+        self._epoch_execute(L.lib().nw_execute_conn, x, (nep, nchan, _ptr(ia), _ptr(ib), npairs), outs, (kind,))
+        return out if _is_device_tensor(x) else outs[0] if single else (outs[0], outs[1])
 
     def execute_conn_time(self, x, indices=None, window=None, step: int = 1, out=None, out_kind: str = 'cross_sum'):
         """Over-time connectivity sums (nw_execute_conn_time): x (E, C, n) as in execute_conn, every
@@ -807,71 +802,20 @@ class Plan:
         (E, P, nfreq, 4); see finalize_conn_time.  numpy arrays: synchronous, ``out`` optional.  Device
         tensors: asynchronous on the plan stream, ``out`` required ((sums, power) for cross_sum, power
         may be None: not formed).  The plan needs max_batch >= C."""
-        import operator
-        if out_kind not in CONN_KINDS and out_kind not in LAG_KINDS:
-            raise ValueError(f"out_kind must be one of {', '.join({**CONN_KINDS, **LAG_KINDS})}; got {out_kind!r}")
-        kind = {**CONN_KINDS, **LAG_KINDS}[out_kind]
-        lag = out_kind == 'lag_sum'
-        plv = out_kind == 'plv_sum' or lag          # one output, no power sums
-        if getattr(x, 'ndim', 0) != 3:
-            raise ValueError(f'x must be (epochs, channels, n), got shape {tuple(getattr(x, "shape", ()))}')
-        nep, nchan = int(x.shape[0]), int(x.shape[1])
+        kind, lag, single = _conn_kind(out_kind)
+        nep, nchan = _epochs(x)
         ia, ib = check_indices(indices, nchan)
         npairs = int(ia.size)
-        try:
-            t0, t1 = (0, self.n_out) if window is None else window
-            t0, t1, step = operator.index(t0), operator.index(t1), operator.index(step)
-        except (TypeError, ValueError):
-            raise ValueError(f'window must be a pair (t0, t1) of integers and step an integer, got {window!r} and '
-                             f'{step!r}') from None
-        if step < 1:
-            raise ValueError(f'step must be >= 1, got {step}')
-        if not 0 <= t0 <= t1 <= self.n_out:
-            raise ValueError(f'window must satisfy 0 <= t0 <= t1 <= n_out = {self.n_out}, got ({t0}, {t1})')
-        P = ctypes.c_void_p
-        ip = (ia.ctypes.data_as(P), ib.ctypes.data_as(P))
-        if _is_device_tensor(x):
-            import torch
-            if out is None:
-                raise ValueError('device execute needs output tensors')
-            if self._check_device_input(x) != nep * nchan:
-                raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
-            sums, power = (out, None) if plv else out
-            for t, dt, count, name in ((sums, torch.float64 if lag else torch.complex128,
-                                        nep * npairs * self.nfreq * (4 if lag else 1), 'sums'),
-                                       (power, torch.float64, nep * nchan * self.nfreq, 'power')):
-                if t is None and name == 'power':
-                    continue
-                if not _is_device_tensor(t) or t.dtype != dt:
-                    raise ValueError(f'device output {name} must be a {dt} tensor on device {self.device}')
-                if not t.is_contiguous() or t.numel() != count:
-                    raise ValueError(f'device output {name} must be contiguous and hold {count} values')
-                if t.device.index != self.device:
-                    raise ValueError(f'device buffers must live on device {self.device}')
-            with self._ordered_with_torch(x.device):
-                L.check(L.lib().nw_execute_conn_time(self._h, P(x.data_ptr()), nep, nchan, *ip, npairs, t0, t1, step,
-                                                     P(sums.data_ptr()),
-                                                     P(power.data_ptr()) if power is not None else None, kind,
-                                                     L.NW_MEM_DEVICE))
-            return out
-        x = np.ascontiguousarray(x, dtype=self.dtype)
-        if x.shape[-1] != self.n:
-            raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
-        sums, power = (out, None) if plv or out is None else out
-        shapes = (((nep, npairs, self.nfreq, 4), np.float64) if lag else
-                  ((nep, npairs, self.nfreq), np.complex128), ((nep, nchan, self.nfreq), np.float64))
-        if sums is None:
-            sums = np.empty(*shapes[0])
-        if power is None and not plv:
-            power = np.empty(*shapes[1])
-        for a, (shape, dt) in zip((sums, power), shapes):
-            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous
-                                  or a.size != int(np.prod(shape))):
-                raise ValueError('out must be C-contiguous arrays of the right dtype and size')
-        L.check(L.lib().nw_execute_conn_time(self._h, x.ctypes.data_as(P), nep, nchan, *ip, npairs, t0, t1, step,
-                                             sums.ctypes.data_as(P), None if plv else power.ctypes.data_as(P), kind,
-                                             L.NW_MEM_HOST))
-        return sums if plv else (sums, power)
+        t0, t1, step = self._window(window, step)
+        x = self._epoch_input(x, nep * nchan, out)
+        specs = [('sums', (nep, npairs, self.nfreq) + ((4,) if lag else ()),
+                  np.float64 if lag else np.complex128, False),
+                 ('power', (nep, nchan, self.nfreq), np.float64, True)][:1 if single else 2]
+        sums, power = (out, None) if single or out is None else out
+        outs = self._outputs(x, [sums, power], specs)
+        self._epoch_execute(L.lib().nw_execute_conn_time, x, (nep, nchan, _ptr(ia), _ptr(ib), npairs, t0, t1, step),
+                            outs, (kind,))
+        return out if _is_device_tensor(x) else outs[0] if single else (outs[0], outs[1])
 
     def execute_env_time(self, x, indices=None, window=None, step: int = 1, out=None, out_kind: str = 'env_orth_sum'):
         """Envelope-correlation sums (nw_execute_env_time): x (E, C, n), ``indices``, ``window`` (the
@@ -882,71 +826,22 @@ class Plan:
         finalize_env.  numpy arrays: synchronous, ``out`` optional.  Device tensors: asynchronous on the
         plan stream, ``out`` = (pair, chan) required (chan may be None: not formed).  The plan needs
         max_batch >= C."""
-        import operator
         if out_kind not in ENV_KINDS:
             raise ValueError(f"out_kind must be one of {', '.join(ENV_KINDS)}; got {out_kind!r}")
         kind = ENV_KINDS[out_kind]
-        if getattr(x, 'ndim', 0) != 3:
-            raise ValueError(f'x must be (epochs, channels, n), got shape {tuple(getattr(x, "shape", ()))}')
-        nep, nchan = int(x.shape[0]), int(x.shape[1])
+        nep, nchan = _epochs(x)
         ia, ib = check_indices(indices, nchan)
         npairs = int(ia.size)
-        try:
-            t0, t1 = (0, self.n_out) if window is None else window
-            t0, t1, step = operator.index(t0), operator.index(t1), operator.index(step)
-        except (TypeError, ValueError):
-            raise ValueError(f'window must be a pair (t0, t1) of integers and step an integer, got {window!r} and '
-                             f'{step!r}') from None
-        if step < 1:
-            raise ValueError(f'step must be >= 1, got {step}')
-        if not 0 <= t0 <= t1 <= self.n_out:
-            raise ValueError(f'window must satisfy 0 <= t0 <= t1 <= n_out = {self.n_out}, got ({t0}, {t1})')
-        P = ctypes.c_void_p
-        ip = (ia.ctypes.data_as(P), ib.ctypes.data_as(P))
-        shapes = ((nep, npairs, self.nfreq) + ((6,) if kind == L.NW_ENV_ORTH else ()), (nep, nchan, self.nfreq, 2))
-        if _is_device_tensor(x):
-            import torch
-            if out is None:
-                raise ValueError('device execute needs output tensors')
-            if self._check_device_input(x) != nep * nchan:
-                raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
-            try:
-                pair, chan = out
-            except (TypeError, ValueError):
-                raise ValueError('device output must be (pair, chan) tensors (chan may be None)') from None
-            for t, shape, name in zip((pair, chan), shapes, ('pair', 'chan')):
-                if t is None and name == 'chan':
-                    continue
-                if not _is_device_tensor(t) or t.dtype != torch.float64:
-                    raise ValueError(f'device output {name} must be a {torch.float64} tensor on device {self.device}')
-                if not t.is_contiguous() or t.numel() != int(np.prod(shape)):
-                    raise ValueError(f'device output {name} must be contiguous and hold {int(np.prod(shape))} values')
-                if t.device.index != self.device:
-                    raise ValueError(f'device buffers must live on device {self.device}')
-            with self._ordered_with_torch(x.device):
-                L.check(L.lib().nw_execute_env_time(self._h, P(x.data_ptr()), nep, nchan, *ip, npairs, t0, t1, step,
-                                                    P(pair.data_ptr()),
-                                                    P(chan.data_ptr()) if chan is not None else None, kind,
-                                                    L.NW_MEM_DEVICE))
-            return out
-        x = np.ascontiguousarray(x, dtype=self.dtype)
-        if x.shape[-1] != self.n:
-            raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
-        try:
-            pair, chan = (None, None) if out is None else out
-        except (TypeError, ValueError):
-            raise ValueError('out must be (pair, chan) arrays') from None
-        if pair is None:
-            pair = np.empty(shapes[0], dtype=np.float64)
-        if chan is None:
-            chan = np.empty(shapes[1], dtype=np.float64)
-        for a, shape in zip((pair, chan), shapes):
-            if (not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.c_contiguous
-                    or a.size != int(np.prod(shape))):
-                raise ValueError('out must be C-contiguous arrays of the right dtype and size')
-        L.check(L.lib().nw_execute_env_time(self._h, x.ctypes.data_as(P), nep, nchan, *ip, npairs, t0, t1, step,
-                                            pair.ctypes.data_as(P), chan.ctypes.data_as(P), kind, L.NW_MEM_HOST))
-        return pair, chan
+        t0, t1, step = self._window(window, step)
+        x = self._epoch_input(x, nep * nchan, out)
+        dev = _is_device_tensor(x)
+        outs = _unpack(out, 2, 'device output must be (pair, chan) tensors (chan may be None)' if dev else
+                       'out must be (pair, chan) arrays')
+        outs = self._outputs(x, outs, [('pair', (nep, npairs, self.nfreq) + ((6,) if kind == L.NW_ENV_ORTH else ()),
+                                        np.float64, False), ('chan', (nep, nchan, self.nfreq, 2), np.float64, True)])
+        self._epoch_execute(L.lib().nw_execute_env_time, x, (nep, nchan, _ptr(ia), _ptr(ib), npairs, t0, t1, step),
+                            outs, (kind,))
+        return out if dev else tuple(outs)
 
     def execute_pac(self, x, indices=None, phase=None, amp=None, window=None, step: int = 1, out=None):
         """Phase-amplitude coupling sums (nw_execute_pac): x (E, C, n) as in execute_conn_time, every
@@ -958,14 +853,26 @@ class Plan:
         complex128 (E, C, Fp) = sum u); see finalize_pac.  numpy arrays: synchronous, ``out`` optional.
         Device tensors: asynchronous on the plan stream, ``out`` = (M, amp, phase) required (amp and
         phase may be None: not formed).  The plan needs max_batch >= C."""
-        import operator
-        if getattr(x, 'ndim', 0) != 3:
-            raise ValueError(f'x must be (epochs, channels, n), got shape {tuple(getattr(x, "shape", ()))}')
-        nep, nchan = int(x.shape[0]), int(x.shape[1])
+        nep, nchan = _epochs(x)
         ip, ia = check_pac_indices(indices, nchan)
         npairs = int(ip.size)
         fph, fam = check_scales('phase', phase, self.nfreq), check_scales('amp', amp, self.nfreq)
         nph, nam = int(fph.size), int(fam.size)
+        t0, t1, step = self._window(window, step)
+        x = self._epoch_input(x, nep * nchan, out)
+        dev = _is_device_tensor(x)
+        outs = _unpack(out, 3, 'device output must be (M, amp, phase) tensors (amp and phase may be None)' if dev else
+                       'out must be (M, amp, phase) arrays')
+        outs = self._outputs(x, outs, [('M', (nep, npairs, nph, nam), np.complex128, False),
+                                       ('amp', (nep, nchan, nam, 2), np.float64, True),
+                                       ('phase', (nep, nchan, nph), np.complex128, True)])
+        self._epoch_execute(L.lib().nw_execute_pac, x,
+                            (nep, nchan, _ptr(ip), _ptr(ia), npairs, _ptr(fph), nph, _ptr(fam), nam, t0, t1, step), outs)
+        return out if dev else tuple(outs)
+
+    def _window(self, window, step):
+        """(t0, t1, step) of an over-time call, checked: ``window`` in the plan's output samples."""
+        import operator
         try:
             t0, t1 = (0, self.n_out) if window is None else window
             t0, t1, step = operator.index(t0), operator.index(t1), operator.index(step)
@@ -976,56 +883,52 @@ class Plan:
             raise ValueError(f'step must be >= 1, got {step}')
         if not 0 <= t0 <= t1 <= self.n_out:
             raise ValueError(f'window must satisfy 0 <= t0 <= t1 <= n_out = {self.n_out}, got ({t0}, {t1})')
-        P = ctypes.c_void_p
-        lists = (ip.ctypes.data_as(P), ia.ctypes.data_as(P), npairs, fph.ctypes.data_as(P), nph, fam.ctypes.data_as(P),
-                 nam, t0, t1, step)
-        shapes = (((nep, npairs, nph, nam), np.complex128), ((nep, nchan, nam, 2), np.float64),
-                  ((nep, nchan, nph), np.complex128))
+        return t0, t1, step
+
+    def _epoch_input(self, x, nsig, out):
+        """The (E, C, n) input of an epoch-chunk call, checked: a device tensor (``out`` is then
+        required), or a host array made contiguous in the plan's dtype."""
         if _is_device_tensor(x):
-            import torch
             if out is None:
                 raise ValueError('device execute needs output tensors')
-            if self._check_device_input(x) != nep * nchan:
+            if self._check_device_input(x) != nsig:
                 raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
-            try:
-                tm, ta, tp = out
-            except (TypeError, ValueError):
-                raise ValueError('device output must be (M, amp, phase) tensors (amp and phase may be None)') from None
-            for t, (shape, dt), name in zip((tm, ta, tp), shapes, ('M', 'amp', 'phase')):
-                if t is None and name != 'M':
-                    continue
-                dt = torch.complex128 if dt is np.complex128 else torch.float64
-                if not _is_device_tensor(t) or t.dtype != dt:
-                    raise ValueError(f'device output {name} must be a {dt} tensor on device {self.device}')
-                if not t.is_contiguous() or t.numel() != int(np.prod(shape)):
-                    raise ValueError(f'device output {name} must be contiguous and hold {int(np.prod(shape))} values')
-                if t.device.index != self.device:
-                    raise ValueError(f'device buffers must live on device {self.device}')
-            with self._ordered_with_torch(x.device):
-                L.check(L.lib().nw_execute_pac(self._h, P(x.data_ptr()), nep, nchan, *lists, P(tm.data_ptr()),
-                                               P(ta.data_ptr()) if ta is not None else None,
-                                               P(tp.data_ptr()) if tp is not None else None, L.NW_MEM_DEVICE))
-            return out
+            return x
         x = np.ascontiguousarray(x, dtype=self.dtype)
         if x.shape[-1] != self.n:
             raise ValueError(f'signal length {x.shape[-1]} != plan n {self.n}')
-        if out is None:
-            out = (None, None, None)
-        try:
-            outs = list(out)
-            if len(outs) != 3:
-                raise TypeError
-        except TypeError:
-            raise ValueError('out must be (M, amp, phase) arrays') from None
-        for k, (shape, dt) in enumerate(shapes):
-            if outs[k] is None:
-                outs[k] = np.empty(shape, dtype=dt)
-            a = outs[k]
-            if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or a.size != int(np.prod(shape)):
-                raise ValueError('out must be C-contiguous arrays of the right dtype and size')
-        L.check(L.lib().nw_execute_pac(self._h, x.ctypes.data_as(P), nep, nchan, *lists,
-                                       *(a.ctypes.data_as(P) for a in outs), L.NW_MEM_HOST))
-        return tuple(outs)
+        return x
+
+    def _outputs(self, x, outs, specs, ndarray_only=True):
+        """The output buffers of an epoch-chunk call on x's side: those of ``specs`` (name, shape, numpy
+        dtype, optional), then None for the rest of ``outs`` (outputs this call does not form).  Device:
+        every tensor validated; an optional one may be None (not formed).  Host: a missing array is
+        allocated, a given one validated."""
+        outs = list(outs)
+        for k, (name, shape, dt, optional) in enumerate(specs):
+            t, count = outs[k], int(np.prod(shape))
+            if not _is_device_tensor(x):
+                if t is None:
+                    t = outs[k] = np.empty(shape, dtype=dt)
+                if ((ndarray_only and not isinstance(t, np.ndarray)) or t.dtype != dt or not t.flags.c_contiguous
+                        or t.size != count):
+                    raise ValueError('out must be C-contiguous arrays of the right dtype and size')
+            elif t is not None or not optional:
+                import torch
+                tdt = torch.complex128 if dt is np.complex128 else torch.float64
+                if not _is_device_tensor(t) or t.dtype != tdt:
+                    raise ValueError(f'device output {name} must be a {tdt} tensor on device {self.device}')
+                if not t.is_contiguous() or t.numel() != count:
+                    raise ValueError(f'device output {name} must be contiguous and hold {count} values')
+                if t.device.index != self.device:
+                    raise ValueError(f'device buffers must live on device {self.device}')
+        return outs
+
+    def _epoch_execute(self, fn, x, head, outs, tail=()):
+        """fn(plan, x, *head, *outs, *tail, mem) on x's side; device tensors in order with torch's stream."""
+        dev = _is_device_tensor(x)
+        with self._ordered_with_torch(x.device) if dev else contextlib.nullcontext():
+            L.check(fn(self._h, _ptr(x), *head, *map(_ptr, outs), *tail, L.NW_MEM_DEVICE if dev else L.NW_MEM_HOST))
 
     def stream_ptr(self) -> int:
         """The hipStream_t the plan launches on."""

@@ -21,6 +21,8 @@ SWITCHES = {
     'nw_large.hip': ['NW_ABL_ROWS_NOW', 'NW_B_PLAIN', 'NW_ABL_COLS_NOFFT', 'NW_ABL_COLS_NOSTORE',
                      'NW_ABL_COLS_NOTW', 'NW_ABL_COLS_STREAM', 'NW_ABL_ROWS_STREAM', 'NW_ABL_NOSTORE', 'NW_ABL_NOTWIDDLE', 'NW_ABL_NOEXCH',
                      'NW_ROWS_NO_REC', 'NW_TAIL_EXACT', 'NW_COLS64_E16', 'NW_COLS32_SINGLE'],
+    # (the switches of nw_reduce_dev.h's skeleton and envelope policies, built through the kernels that use them)
+    'nw_env.hip': ['NW_ABL_ENV_NOLOAD', 'NW_ABL_ENV_NODIV'],
 }
 
 
