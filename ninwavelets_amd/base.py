@@ -466,29 +466,55 @@ class WaveletBase:
           plv        |plv_sum| / E  (float64; NaN where some |y| = 0, as itc)
         (engine.finalize_pair).  Results are float64 / complex128 whatever the compute dtype.
         One device is used: the first of the wavelet's.  ``decim`` as in cwt."""
+        return self._pair_sums(waves_a, waves_b, freqs, reuse, out, decim, PAIR_OUTS, finalize_pair, 0)
+
+    def _pair_sums(self, waves_a, waves_b, freqs, reuse, out, decim, names, finalize, min_pairs):
+        """The measures of the signal pairs of two (..., N) arrays: the argument checks (``out`` one of
+        ``names``, equal shapes, at least ``min_pairs`` pairs), sums = plan.execute_pair over the pairs
+        (_sums_on_plan; the plan holds max_batch >= 2, one pair) and finalize(out, sums, npairs)."""
         decim = check_decim(decim)
-        if out not in PAIR_OUTS:
-            raise ValueError(f"out must be one of {', '.join(PAIR_OUTS)}; got {out!r}")
+        if out not in names:
+            raise ValueError(f"out must be one of {', '.join(names)}; got {out!r}")
         waves_a, waves_b = np.asarray(waves_a), np.asarray(waves_b)
         if waves_a.ndim < 1 or waves_a.shape != waves_b.shape:
             raise ValueError(f'waves_a and waves_b must have the same (..., N) shape; got {waves_a.shape} '
                              f'and {waves_b.shape}')
-        if (not reuse) or self._cache is None:
-            self._build_cache(freqs, waves_a.shape[-1] / self.sfreq)
         n = waves_a.shape[-1]
         npairs = int(np.prod(waves_a.shape[:-1])) if waves_a.ndim > 1 else 1
+        if npairs < min_pairs:
+            raise ValueError(f'{out} needs at least {min_pairs} epochs, got {npairs}')
+        sums = self._sums_on_plan(freqs, reuse, n, 2 * npairs, decim, 2, 1, lambda plan: plan.execute_pair(
+            waves_a.reshape(npairs, n), waves_b.reshape(npairs, n), out_kind=names[out]))
+        return finalize(out, sums, npairs)
+
+    def _conn_sums(self, waves, freqs, reuse, out, indices, decim, names, finalize, min_epochs):
+        """_pair_sums for the channel pairs ``indices`` of (E, C, N) epochs: sums = plan.execute_conn (the
+        plan holds max_batch >= C, one epoch) and finalize(sums, ia, ib, E)."""
+        decim = check_decim(decim)
+        if out not in names:
+            raise ValueError(f"out must be one of {', '.join(names)}; got {out!r}")
+        waves, nep, nchan, n = _epochs(waves)
+        pairs = check_indices(indices, nchan)
+        if nep < min_epochs:
+            raise ValueError(f'{out} needs at least {min_epochs} epochs, got {nep}')
+        sums = self._sums_on_plan(freqs, reuse, n, nep * nchan, decim, nchan, 2,
+                                  lambda plan: plan.execute_conn(waves, pairs, out_kind=names[out]))
+        return finalize(sums, *pairs, nep)
+
+    def _sums_on_plan(self, freqs, reuse, n, nsig, decim, min_batch, axis, execute):
+        """The epoch sums execute(plan) (one array or a tuple of them, samples on ``axis``) at every
+        ``decim``-th sample: the cache, then the plan of _on_plan, which decimates where the device can;
+        elsewhere the full-rate sums are sliced."""
+        if (not reuse) or self._cache is None:
+            self._build_cache(freqs, n / self.sfreq)
         on_device = self._device_decim(n, decim)
-        self._used = 1
-        try:
-            plan = self._plan(n, 2 * npairs, (self.devices or [self.device])[0],
-                              decim=decim if on_device else 1, min_batch=2)
-            sums = plan.execute_pair(waves_a.reshape(npairs, n), waves_b.reshape(npairs, n), out_kind=PAIR_OUTS[out])
-        finally:
-            if len(self._plans) > 1:
-                self._evict_plans(keep=1)
-        if decim > 1 and not on_device:
-            sums = np.ascontiguousarray(sums[:, ::decim])
-        return finalize_pair(out, sums, npairs)
+        sums = self._on_plan(n, nsig, decim if on_device else 1, min_batch, execute)
+        if decim == 1 or on_device:
+            return sums
+        every = (slice(None),) * axis + (slice(None, None, decim),)
+        if isinstance(sums, tuple):
+            return tuple(np.ascontiguousarray(s[every]) for s in sums)
+        return np.ascontiguousarray(sums[every])
 
     def connectivity_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, out: str = 'coherence',
                            indices=None, decim: int = 1):
@@ -502,21 +528,9 @@ class WaveletBase:
         returns (S complex128 (P, F, N'), P_cc float64 (C, F, N')).  No reference counterpart
         (mne-connectivity's spectral_connectivity_epochs(..., indices=...) in its cwt_morlet mode
         returns the same maps); cache semantics, device choice and ``decim`` as in cross_batch."""
-        decim = check_decim(decim)
-        if out not in CONN_OUTS:
-            raise ValueError(f"out must be one of {', '.join(CONN_OUTS)}; got {out!r}")
-        waves, nep, nchan, n = _epochs(waves)
-        ia, ib = check_indices(indices, nchan)
-        if (not reuse) or self._cache is None:
-            self._build_cache(freqs, n / self.sfreq)
-        on_device = self._device_decim(n, decim)
-        sums = self._on_plan(n, nep * nchan, decim if on_device else 1, nchan,
-                             lambda plan: plan.execute_conn(waves, (ia, ib), out_kind=CONN_OUTS[out]))
-        cross, power = sums if CONN_OUTS[out] == 'cross_sum' else (sums, None)
-        if decim > 1 and not on_device:
-            cross = np.ascontiguousarray(cross[..., ::decim])
-            power = None if power is None else np.ascontiguousarray(power[..., ::decim])
-        return finalize_conn(out, cross, power, ia, ib, nep)
+        def finalize(sums, *a):
+            return finalize_conn(out, *(sums if CONN_OUTS[out] == 'cross_sum' else (sums, None)), *a)
+        return self._conn_sums(waves, freqs, reuse, out, indices, decim, CONN_OUTS, finalize, 0)
 
     def lag_batch(self, waves_a: np.ndarray, waves_b: np.ndarray, freqs=None, reuse: bool = True,
                   out: str = 'wpli', decim: int = 1) -> np.ndarray:
@@ -531,31 +545,8 @@ class WaveletBase:
           ciplv, ppc      from cross_batch's plv_sum
         (engine.finalize_lag; float64).  Argument checks, cache semantics, device choice and
         ``decim`` as in cross_batch."""
-        decim = check_decim(decim)
-        if out not in LAG_OUTS:
-            raise ValueError(f"out must be one of {', '.join(LAG_OUTS)}; got {out!r}")
-        waves_a, waves_b = np.asarray(waves_a), np.asarray(waves_b)
-        if waves_a.ndim < 1 or waves_a.shape != waves_b.shape:
-            raise ValueError(f'waves_a and waves_b must have the same (..., N) shape; got {waves_a.shape} '
-                             f'and {waves_b.shape}')
-        n = waves_a.shape[-1]
-        npairs = int(np.prod(waves_a.shape[:-1])) if waves_a.ndim > 1 else 1
-        if out in ('pli2_unbiased', 'ppc') and npairs < 2:
-            raise ValueError(f'{out} needs at least 2 epochs, got {npairs}')
-        if (not reuse) or self._cache is None:
-            self._build_cache(freqs, n / self.sfreq)
-        on_device = self._device_decim(n, decim)
-        self._used = 1
-        try:
-            plan = self._plan(n, 2 * npairs, (self.devices or [self.device])[0],
-                              decim=decim if on_device else 1, min_batch=2)
-            sums = plan.execute_pair(waves_a.reshape(npairs, n), waves_b.reshape(npairs, n), out_kind=LAG_OUTS[out])
-        finally:
-            if len(self._plans) > 1:
-                self._evict_plans(keep=1)
-        if decim > 1 and not on_device:
-            sums = np.ascontiguousarray(sums[:, ::decim])
-        return finalize_lag(out, sums, npairs)
+        return self._pair_sums(waves_a, waves_b, freqs, reuse, out, decim, LAG_OUTS, finalize_lag,
+                               2 if out in ('pli2_unbiased', 'ppc') else 0)
 
     def lag_connectivity_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, out: str = 'wpli',
                                indices=None, decim: int = 1) -> np.ndarray:
@@ -563,21 +554,9 @@ class WaveletBase:
         transform per epoch and channel, (P, F, N') float64 (``lag_sum``: (P, F, N', 4)), as
         connectivity_batch does for the cross sums: its argument checks, pair lists, cache
         semantics, device choice and ``decim``."""
-        decim = check_decim(decim)
-        if out not in LAG_OUTS:
-            raise ValueError(f"out must be one of {', '.join(LAG_OUTS)}; got {out!r}")
-        waves, nep, nchan, n = _epochs(waves)
-        pairs = check_indices(indices, nchan)
-        if out in ('pli2_unbiased', 'ppc') and nep < 2:
-            raise ValueError(f'{out} needs at least 2 epochs, got {nep}')
-        if (not reuse) or self._cache is None:
-            self._build_cache(freqs, n / self.sfreq)
-        on_device = self._device_decim(n, decim)
-        sums = self._on_plan(n, nep * nchan, decim if on_device else 1, nchan,
-                             lambda plan: plan.execute_conn(waves, pairs, out_kind=LAG_OUTS[out]))
-        if decim > 1 and not on_device:
-            sums = np.ascontiguousarray(sums[:, :, ::decim])
-        return finalize_lag(out, sums, nep)
+        return self._conn_sums(waves, freqs, reuse, out, indices, decim, LAG_OUTS,
+                               lambda sums, ia, ib, nep: finalize_lag(out, sums, nep),
+                               2 if out in ('pli2_unbiased', 'ppc') else 0)
 
     def connectivity_time_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, out: str = 'coherence',
                                 indices=None, window=None, decim: int = 1, average: bool = False):

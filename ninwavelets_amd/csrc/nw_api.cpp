@@ -796,6 +796,39 @@ int run_chunk(nw_plan* p, const nw::WDesc& d, const void* xs_dev, int64_t c, voi
 
 bool is_reduction(int out_kind) { return out_kind >= NW_OUT_POWER_MEAN && out_kind <= NW_OUT_PHASE_SUM; }
 bool is_phase(int out_kind) { return out_kind == NW_OUT_ITC || out_kind == NW_OUT_PHASE_SUM; }
+// the out_kinds of nw_execute and the nw_execute_multi* calls
+bool is_execute_kind(int out_kind) { return out_kind >= NW_OUT_CWT && out_kind <= NW_OUT_PHASE_SUM; }
+
+// Host buffers: the chunk's `bytes` of input at xs staged into d_x, one copy stage
+int stage_chunk(nw_plan* p, const void* xs, size_t bytes) {
+    return staged(p, ST_COPY, [&] {
+        NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, bytes, hipMemcpyHostToDevice, p->stream));
+        return NW_OK;
+    });
+}
+
+// The scratch a reduction's chunks leave their rows in: the rocFFT engine's run_chunk leaves y in d_Y;
+// the other forms write d_out, grown to the caller's `bytes`
+int reduce_scratch(nw_plan* p, size_t bytes, void** scratch) {
+    if (p->form == FORM_ROCFFT) {
+        NW_TRY(need_Y(p, p->nfreq));
+        *scratch = p->d_Y.ptr;
+    } else {
+        NW_TRY(p->d_out.ensure(bytes));
+        *scratch = p->d_out.ptr;
+    }
+    return NW_OK;
+}
+
+// The end of a reduction call: counted; with host buffers the result has landed and the stages are timed
+int end_reduce(nw_plan* p, bool host) {
+    p->stats.executes++;
+    if (host) {
+        NW_HIP(hipStreamSynchronize(p->stream));
+        NW_TRY(resolve_timing(p));
+    }
+    return NW_OK;
+}
 
 // Epoch reductions (mneutils.py:42-71): every chunk's per-signal results (|y|^2 from
 // the fused kernel, or y from the rocFFT engine's Y / the fused CWT for phases) are
@@ -835,16 +868,10 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
     // partials: plain fp64 sums (phase partials as 2 fn reals)
     const int src_kind = psum ? nw::ACC_POWER_REAL
                               : phase ? nw::ACC_PHASE_Y : (fused ? nw::ACC_POWER_REAL : nw::ACC_POWER_Y);
-    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
-    if (!fused) {
-        NW_TRY(need_Y(p, p->nfreq));
-        scratch = p->d_Y.ptr;
-    } else {
-        size_t sb = (size_t)p->max_batch * fn * (phase ? 2 : 1) * p->esz;
-        if (psum) sb = std::max(sb, (size_t)nw::fused_psum_groups(p->max_batch) * fn * (phase ? 2 : 1) * sizeof(double));
-        NW_TRY(p->d_out.ensure(sb));
-        scratch = p->d_out.ptr;
-    }
+    size_t sb = (size_t)p->max_batch * fn * (phase ? 2 : 1) * p->esz;
+    if (psum) sb = std::max(sb, (size_t)nw::fused_psum_groups(p->max_batch) * fn * (phase ? 2 : 1) * sizeof(double));
+    void* scratch = nullptr;
+    NW_TRY(reduce_scratch(p, sb, &scratch));
     // The chirp-z partial rows are those of the call's signal groups 0-7, 8-15, ... whatever
     // max_batch (chirp_psum_chunk), so the sums do not depend on it: a chunk shorter than a group
     // carries the group's row on, and the row is added once the group is complete.
@@ -852,10 +879,7 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
         c = chirp_psum ? nw::chirp_psum_chunk(s0, nsig, p->max_batch) : std::min<int64_t>(p->max_batch, nsig - s0);
         const void* xs = (const char*)x + (size_t)s0 * p->n * p->esz;
         if (host) {
-            NW_TRY(staged(p, ST_COPY, [&] {
-                NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, (size_t)c * p->n * p->esz, hipMemcpyHostToDevice, p->stream));
-                return NW_OK;
-            }));
+            NW_TRY(stage_chunk(p, xs, (size_t)c * p->n * p->esz));
             xs = p->d_x.ptr;
         }
         p->chirp_carry = chirp_psum && s0 % nw::kPsumGroup != 0;
@@ -879,12 +903,7 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
         NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, false, nw::launch_finalize(p->dtype, phase, acc, dst, fn, nsig, p->stream)));
         if (host) NW_HIP(hipMemcpyAsync(out, dst, (size_t)fn * p->esz, hipMemcpyDeviceToHost, p->stream));
     }
-    p->stats.executes++;
-    if (host) {
-        NW_HIP(hipStreamSynchronize(p->stream));
-        NW_TRY(resolve_timing(p));
-    }
-    return NW_OK;
+    return end_reduce(p, host);
 }
 
 // Cross-channel pair reductions (nw_execute_pair): per chunk of max_batch / 2 pairs the two
@@ -915,15 +934,9 @@ int execute_pair(nw_plan* p, const nw::WDesc& d, const void* xa, const void* xb,
             psum ? "fp64 block partial sums inside the transform kernel"
                  : "per-signal rows per chunk, added in pair order in fp64");
     p->stats.reduce_path = psum ? NW_REDUCE_PARTIALS : NW_REDUCE_ROWS;
-    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
-    if (p->form == FORM_ROCFFT) {
-        NW_TRY(need_Y(p, p->nfreq));
-        scratch = p->d_Y.ptr;
-    } else {
-        NW_TRY(p->d_out.ensure(psum ? (size_t)nw::fused_psum_groups(p->max_batch) * fn * comps * sizeof(double)
-                                    : (size_t)p->max_batch * fn * 2 * p->esz));
-        scratch = p->d_out.ptr;
-    }
+    void* scratch = nullptr;
+    NW_TRY(reduce_scratch(p, psum ? (size_t)nw::fused_psum_groups(p->max_batch) * fn * comps * sizeof(double)
+                                  : (size_t)p->max_batch * fn * 2 * p->esz, &scratch));
     const int64_t per = p->max_batch / 2;
     const size_t row = (size_t)p->n * p->esz;
     const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -949,12 +962,7 @@ int execute_pair(nw_plan* p, const nw::WDesc& d, const void* xa, const void* xb,
         p->stats.chunks++;
     }
     NW_HIP(hipMemcpyAsync(out, acc, acc_bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, p->stream));
-    p->stats.executes++;
-    if (host) {
-        NW_HIP(hipStreamSynchronize(p->stream));
-        NW_TRY(resolve_timing(p));
-    }
-    return NW_OK;
+    return end_reduce(p, host);
 }
 
 // The epoch-chunk reductions (nw_execute_conn, _conn_time, _env_time, _pac) share one layout of d_acc
@@ -1002,24 +1010,15 @@ bool xcd_order() { return !std::getenv("NW_CONN_PLAIN_ORDER"); }
 template <typename F>
 int run_epoch_chunks(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const SumRegion* r,
                      int nr, bool host, F&& launch) {
-    void* scratch = nullptr;            // rocFFT engine: run_chunk leaves y in d_Y
-    if (p->form == FORM_ROCFFT) {
-        NW_TRY(need_Y(p, p->nfreq));
-        scratch = p->d_Y.ptr;
-    } else {
-        NW_TRY(p->d_out.ensure((size_t)p->max_batch * p->nfreq * p->n_out() * 2 * p->esz));
-        scratch = p->d_out.ptr;
-    }
+    void* scratch = nullptr;
+    NW_TRY(reduce_scratch(p, (size_t)p->max_batch * p->nfreq * p->n_out() * 2 * p->esz, &scratch));
     const int64_t per = p->max_batch / nchan;
     const size_t epoch_bytes = (size_t)nchan * p->n * p->esz;
     for (int64_t e0 = 0; e0 < nepochs; e0 += per) {
         const int64_t ec = std::min<int64_t>(per, nepochs - e0);
         const void* xs = (const char*)x + (size_t)e0 * epoch_bytes;
         if (host) {
-            NW_TRY(staged(p, ST_COPY, [&] {
-                NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, (size_t)ec * epoch_bytes, hipMemcpyHostToDevice, p->stream));
-                return NW_OK;
-            }));
+            NW_TRY(stage_chunk(p, xs, (size_t)ec * epoch_bytes));
             xs = p->d_x.ptr;
         }
         NW_TRY(run_chunk(p, d, xs, ec * nchan, scratch, NW_OUT_CWT, false));
@@ -1029,12 +1028,7 @@ int run_epoch_chunks(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepo
     const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     for (int i = 0; i < nr; ++i)
         if (r[i].bytes) NW_HIP(hipMemcpyAsync(r[i].out, r[i].dev, r[i].bytes, back, p->stream));
-    p->stats.executes++;
-    if (host) {
-        NW_HIP(hipStreamSynchronize(p->stream));
-        NW_TRY(resolve_timing(p));
-    }
-    return NW_OK;
+    return end_reduce(p, host);
 }
 
 // Multi-channel connectivity (nw_execute_conn): per chunk nw_conn_accumulate_kernel adds every pair's
@@ -1230,7 +1224,8 @@ int check_window(const char* who, int64_t n_out, int64_t t0, int64_t t1, int64_t
     return NW_OK;
 }
 
-// the out_kind of nw_execute_conn and nw_execute_conn_time: null, or what is wrong with it
+// the out_kind of nw_execute_pair (no out_power), nw_execute_conn and nw_execute_conn_time: null, or
+// what is wrong with it
 const char* conn_kind_error(int out_kind, const void* out_power) {
     if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM && out_kind != NW_OUT_LAG_SUM)
         return "out_kind must be NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM or NW_OUT_LAG_SUM";
@@ -1625,16 +1620,14 @@ int nw_plan_row_support(nw_plan* p, int method, int32_t* kmax_out) {
 int nw_execute(nw_plan* p, const void* x, int64_t nsig, void* out, int out_kind, int mem) {
     if (!p || (!x && nsig > 0) || (!out && nsig > 0)) return fail(NW_E_INVALID, "nw_execute: null argument");
     if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute: nw_plan_set_wavelet first");
-    if (out_kind < NW_OUT_CWT || out_kind > NW_OUT_PHASE_SUM) return fail(NW_E_INVALID, "nw_execute: bad out_kind");
+    if (!is_execute_kind(out_kind)) return fail(NW_E_INVALID, "nw_execute: bad out_kind");
     if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute: bad mem");
     if (nsig < 0) return fail(NW_E_INVALID, "nw_execute: nsig < 0");
     if (is_reduction(out_kind) && !out) return fail(NW_E_INVALID, "nw_execute: null out");
     if (nsig == 0 && !is_reduction(out_kind)) return NW_OK;
     DeviceGuard guard(p->device);
-    p->executed = true;
-    const nw::WDesc d = exec_rows(p);
-    // settle the form of a tentative length before any buffer choice
-    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
+    nw::WDesc d;
+    NW_TRY(begin_execute(p, &d));
 
     nw_logf(1, "plan %p: execute %s, %lld signals, %s buffers", (void*)p, out_name(out_kind), (long long)nsig,
             mem == NW_MEM_HOST ? "host" : "device");
@@ -1666,10 +1659,7 @@ int nw_execute(nw_plan* p, const void* x, int64_t nsig, void* out, int out_kind,
         const char* xs = (const char*)x + (size_t)s0 * p->n * p->esz;
         char* os = (char*)out + (size_t)s0 * row_out;
         if (host) {
-            NW_TRY(staged(p, ST_COPY, [&] {
-                NW_HIP(hipMemcpyAsync(p->d_x.ptr, xs, (size_t)c * p->n * p->esz, hipMemcpyHostToDevice, p->stream));
-                return NW_OK;
-            }));
+            NW_TRY(stage_chunk(p, xs, (size_t)c * p->n * p->esz));
             NW_TRY(run_chunk(p, d, p->d_x.ptr, c, staging, out_kind, true));
             NW_TRY(staged(p, ST_COPY, [&] {
                 if (direct) {
@@ -1696,18 +1686,14 @@ int nw_pair_partials_supported(int64_t n, int dtype, int kind, int out_kind) {
 int nw_execute_pair(nw_plan* p, const void* xa, const void* xb, int64_t npairs, void* out, int out_kind, int mem) {
     if (!p || !out || ((!xa || !xb) && npairs > 0)) return fail(NW_E_INVALID, "nw_execute_pair: null argument");
     if (!p->has_wavelet) return fail(NW_E_STATE, "nw_execute_pair: nw_plan_set_wavelet first");
-    if (out_kind != NW_OUT_CROSS_SUM && out_kind != NW_OUT_PLV_SUM && out_kind != NW_OUT_LAG_SUM)
-        return fail(NW_E_INVALID,
-                    "nw_execute_pair: out_kind must be NW_OUT_CROSS_SUM, NW_OUT_PLV_SUM or NW_OUT_LAG_SUM");
+    if (const char* e = conn_kind_error(out_kind, nullptr)) return fail(NW_E_INVALID, std::string("nw_execute_pair: ") + e);
     if (mem != NW_MEM_HOST && mem != NW_MEM_DEVICE) return fail(NW_E_INVALID, "nw_execute_pair: bad mem");
     if (npairs < 0) return fail(NW_E_INVALID, "nw_execute_pair: npairs < 0");
     if (p->max_batch < 2)
         return fail(NW_E_INVALID, "nw_execute_pair: the plan's max_batch must be >= 2 (a chunk holds max_batch / 2 pairs)");
     DeviceGuard guard(p->device);
-    p->executed = true;
-    const nw::WDesc d = exec_rows(p);
-    // settle the form of a tentative length before any buffer choice
-    if (p->form == FORM_CHIRP && p->chirp_tentative) NW_TRY(chirp_table(p, d));
+    nw::WDesc d;
+    NW_TRY(begin_execute(p, &d));
     nw_logf(1, "plan %p: execute %s, %lld pairs, %s buffers", (void*)p, out_name(out_kind), (long long)npairs,
             mem == NW_MEM_HOST ? "host" : "device");
     NW_TRY(execute_pair(p, d, xa, xb, npairs, out, out_kind, mem == NW_MEM_HOST));
@@ -1906,10 +1892,15 @@ int reduce_partials(nw_plan* const* plans, int nplans, int out_kind, int64_t tot
     return NW_OK;
 }
 
-int check_same_config(nw_plan* const* plans, int nplans, const char* who) {
+// scale_slices: the plans of nw_execute_multi_scales hold slices of one scale list, so their nfreq is
+// free, and they mask the same half of the spectrum
+int check_same_config(nw_plan* const* plans, int nplans, const char* who, bool scale_slices = false) {
     for (int i = 1; i < nplans; ++i)
-        if (plans[i]->n != plans[0]->n || plans[i]->nfreq != plans[0]->nfreq || plans[i]->dtype != plans[0]->dtype)
-            return fail(NW_E_INVALID, std::string(who) + ": plans must share n, nfreq and dtype");
+        if (plans[i]->n != plans[0]->n || plans[i]->dtype != plans[0]->dtype ||
+            (scale_slices ? (plans[i]->flags & NW_INTERPOLATE) != (plans[0]->flags & NW_INTERPOLATE)
+                          : plans[i]->nfreq != plans[0]->nfreq))
+            return fail(NW_E_INVALID, std::string(who) + (scale_slices ? ": plans must share n, dtype and interpolate"
+                                                                       : ": plans must share n, nfreq and dtype"));
     for (int i = 1; i < nplans; ++i)
         if (plans[i]->decim != plans[0]->decim)
             return fail(NW_E_INVALID, std::string(who) + ": plans must share decim");
@@ -1925,7 +1916,7 @@ int nw_execute_multi(nw_plan* const* plans, int nplans, const void* x, int64_t n
     NW_TRY(check_distinct(plans, nplans, "nw_execute_multi"));
     NW_TRY(check_same_config(plans, nplans, "nw_execute_multi"));
     const nw_plan* p0 = plans[0];
-    if (out_kind < NW_OUT_CWT || out_kind > NW_OUT_PHASE_SUM) return fail(NW_E_INVALID, "nw_execute_multi: bad out_kind");
+    if (!is_execute_kind(out_kind)) return fail(NW_E_INVALID, "nw_execute_multi: bad out_kind");
     if (nsig < 0) return fail(NW_E_INVALID, "nw_execute_multi: nsig < 0");
     if (is_reduction(out_kind)) return execute_multi_reduce(plans, nplans, x, nsig, out, out_kind);
     const size_t x_row = (size_t)p0->n * p0->esz;
@@ -1947,8 +1938,7 @@ int nw_execute_multi_device(nw_plan* const* plans, int nplans, const void* const
     if (!plans || nplans < 1 || !x || !nsig || !out) return fail(NW_E_INVALID, "nw_execute_multi_device: null argument");
     NW_TRY(check_distinct(plans, nplans, "nw_execute_multi_device"));
     NW_TRY(check_same_config(plans, nplans, "nw_execute_multi_device"));
-    if (out_kind < NW_OUT_CWT || out_kind > NW_OUT_PHASE_SUM)
-        return fail(NW_E_INVALID, "nw_execute_multi_device: bad out_kind");
+    if (!is_execute_kind(out_kind)) return fail(NW_E_INVALID, "nw_execute_multi_device: bad out_kind");
     int64_t total = 0;
     for (int i = 0; i < nplans; ++i) {
         if (nsig[i] < 0) return fail(NW_E_INVALID, "nw_execute_multi_device: nsig < 0");
@@ -1981,15 +1971,9 @@ int nw_execute_multi_scales(nw_plan* const* plans, int nplans, const void* x, in
                             int out_kind) {
     if (!plans || nplans < 1 || !plans[0]) return fail(NW_E_INVALID, "nw_execute_multi_scales: no plans");
     NW_TRY(check_distinct(plans, nplans, "nw_execute_multi_scales"));
+    NW_TRY(check_same_config(plans, nplans, "nw_execute_multi_scales", true));
     const nw_plan* p0 = plans[0];
-    for (int i = 1; i < nplans; ++i)
-        if (!plans[i] || plans[i]->n != p0->n || plans[i]->dtype != p0->dtype ||
-            (plans[i]->flags & NW_INTERPOLATE) != (p0->flags & NW_INTERPOLATE))
-            return fail(NW_E_INVALID, "nw_execute_multi_scales: plans must share n, dtype and interpolate");
-    for (int i = 1; i < nplans; ++i)
-        if (plans[i]->decim != p0->decim) return fail(NW_E_INVALID, "nw_execute_multi_scales: plans must share decim");
-    if (out_kind < NW_OUT_CWT || out_kind > NW_OUT_PHASE_SUM)
-        return fail(NW_E_INVALID, "nw_execute_multi_scales: bad out_kind");
+    if (!is_execute_kind(out_kind)) return fail(NW_E_INVALID, "nw_execute_multi_scales: bad out_kind");
     if (nsig < 0) return fail(NW_E_INVALID, "nw_execute_multi_scales: nsig < 0");
     if (nsig > 0 && (!x || !out)) return fail(NW_E_INVALID, "nw_execute_multi_scales: null argument");
     int64_t F = 0;

@@ -29,9 +29,7 @@ PAIR_OUTS = {'cross_sum': 'cross_sum', 'plv_sum': 'plv_sum', 'csd': 'cross_sum',
 # multi-channel connectivity (Plan.execute_conn): the same two sums for every channel pair of a list,
 # cross_sum -> complex128 (P, F, n) + float64 (C, F, n), plv_sum -> complex128 (P, F, n); and what
 # finalize_conn forms from them
-CONN_KINDS = {'cross_sum': L.NW_OUT_CROSS_SUM, 'plv_sum': L.NW_OUT_PLV_SUM}
-CONN_OUTS = {'cross_sum': 'cross_sum', 'plv_sum': 'plv_sum', 'csd': 'cross_sum', 'coherency': 'cross_sum',
-             'coherence': 'cross_sum', 'imcoh': 'cross_sum', 'plv': 'plv_sum'}
+CONN_KINDS, CONN_OUTS = PAIR_KINDS, PAIR_OUTS
 # phase-lag connectivity (Plan.execute_pair / execute_conn with out_kind='lag_sum'): float64
 # (..., 4) = {L0, L1, L2, L3}, the epoch sums of m, |m|, m^2, sgn m with m = Im y_a conj(y_b); and
 # what finalize_lag forms, name -> the sums it needs (ciplv and ppc come from the unit-phasor sums)
@@ -198,14 +196,27 @@ def finalize_conn(kind: str, cross: np.ndarray, power, ia, ib, nepochs: int):
         return cross, power
     if kind == 'plv_sum':
         return cross
-    cross = np.asarray(cross, dtype=np.complex128)
-    out = np.empty(cross.shape, dtype=np.complex128 if kind in ('csd', 'coherency') else np.float64)
-    for p in range(cross.shape[0]):
-        if kind == 'plv':
-            out[p] = finalize_pair('plv', cross[p], nepochs)
+    return _finalize_pairs(kind, cross, power, ia, ib, nepochs, 0)
+
+
+def _finalize_pairs(kind: str, sums, power, ia, ib, count: int, axis: int):
+    """The per-pair loop of finalize_conn (pairs and channels on axis 0) and finalize_conn_time (on
+    ``axis`` 1): pair p's slice of ``sums`` through finalize_lag, or finalize_pair on it (plv) or on
+    stack(Re S, Im S, P of ia[p], P of ib[p]), into pair p's slice of a result of sums' layout."""
+    lag = kind in LAG_OUTS
+    sums = np.asarray(sums) if lag else np.asarray(sums, dtype=np.complex128)
+    out = np.empty(sums.shape[:-1] if LAG_OUTS.get(kind) == 'lag_sum' else sums.shape,
+                   dtype=np.complex128 if kind in ('csd', 'coherency') else np.float64)
+    rows, res = np.moveaxis(sums, axis, 0), np.moveaxis(out, axis, 0)          # views, pair axis first
+    chan = None if lag or kind == 'plv' else np.moveaxis(power, axis, 0)
+    for p in range(rows.shape[0]):
+        if lag:
+            res[p] = finalize_lag(kind, rows[p], count)
+        elif kind == 'plv':
+            res[p] = finalize_pair('plv', rows[p], count)
         else:
-            sums = np.stack([cross[p].real, cross[p].imag, power[ia[p]], power[ib[p]]], axis=-1)
-            out[p] = finalize_pair(kind, sums, nepochs)
+            four = np.stack([rows[p].real, rows[p].imag, chan[ia[p]], chan[ib[p]]], axis=-1)
+            res[p] = finalize_pair(kind, four, count)
     return out
 
 
@@ -226,24 +237,9 @@ def finalize_conn_time(kind: str, sums, power, ia, ib, nsamples: int):
     if kind in ('plv_sum', 'lag_sum'):
         return sums
     T = int(nsamples)
-    if kind in LAG_OUTS:
-        if kind in ('pli2_unbiased', 'ppc') and T < 2:
-            raise ValueError(f'{kind} needs at least 2 samples in the window, got {T}')
-        sums = np.asarray(sums)
-        shape = sums.shape[:-1] if LAG_OUTS[kind] == 'lag_sum' else sums.shape
-        out = np.empty(shape, dtype=np.float64)
-        for p in range(shape[1]):
-            out[:, p] = finalize_lag(kind, sums[:, p], T)
-        return out
-    sums = np.asarray(sums, dtype=np.complex128)
-    out = np.empty(sums.shape, dtype=np.complex128 if kind in ('csd', 'coherency') else np.float64)
-    for p in range(sums.shape[1]):
-        if kind == 'plv':
-            out[:, p] = finalize_pair('plv', sums[:, p], T)
-        else:
-            four = np.stack([sums[:, p].real, sums[:, p].imag, power[:, ia[p]], power[:, ib[p]]], axis=-1)
-            out[:, p] = finalize_pair(kind, four, T)
-    return out
+    if kind in ('pli2_unbiased', 'ppc') and T < 2:
+        raise ValueError(f'{kind} needs at least 2 samples in the window, got {T}')
+    return _finalize_pairs(kind, sums, power, ia, ib, T, 1)
 
 
 def check_pac_indices(indices, nchan: int):
@@ -727,46 +723,27 @@ class Plan:
         (nfreq, n_out, 4) = {Re S_ab, Im S_ab, P_aa, P_bb}; ``plv_sum`` -> complex128
         (nfreq, n_out); see finalize_pair.  ``lag_sum`` -> float64 (nfreq, n_out, 4) = the
         phase-lag sums {L0, L1, L2, L3}; see finalize_lag.  The plan needs max_batch >= 2."""
-        if out_kind not in PAIR_KINDS and out_kind not in LAG_KINDS:
-            raise ValueError(f"out_kind must be one of {', '.join({**PAIR_KINDS, **LAG_KINDS})}; got {out_kind!r}")
-        kind = {**PAIR_KINDS, **LAG_KINDS}[out_kind]
-        plv = out_kind == 'plv_sum'
-        count = self.nfreq * self.n_out * (1 if plv else 4)
-        if _is_device_tensor(xa) or _is_device_tensor(xb):
-            import torch
+        kind = _conn_kind(out_kind)[0]
+        dev = _is_device_tensor(xa) or _is_device_tensor(xb)
+        if dev:
             if out is None:
                 raise ValueError('device execute needs an output tensor')
             npairs = self._check_device_input(xa)
             if self._check_device_input(xb) != npairs:
                 raise ValueError('the two inputs must hold the same number of signals')
-            if not _is_device_tensor(out) or out.dtype != (torch.complex128 if plv else torch.float64):
-                raise ValueError(f'device output must be a {"complex128" if plv else "float64"} tensor '
-                                 f'on device {self.device}')
-            if not out.is_contiguous() or out.numel() != count:
-                raise ValueError('device output must be contiguous, (nfreq, n_out, 4) for cross_sum and lag_sum / '
-                                 '(nfreq, n_out) for plv_sum')
-            if out.device.index != self.device:
-                raise ValueError(f'device buffers must live on device {self.device}')
-            with self._ordered_with_torch(xa.device):
-                L.check(L.lib().nw_execute_pair(self._h, ctypes.c_void_p(xa.data_ptr()), ctypes.c_void_p(xb.data_ptr()),
-                                                npairs, ctypes.c_void_p(out.data_ptr()), kind, L.NW_MEM_DEVICE))
-            return out
-        xa = np.ascontiguousarray(xa, dtype=self.dtype)
-        xb = np.ascontiguousarray(xb, dtype=self.dtype)
-        if xa.shape != xb.shape:
-            raise ValueError(f'the two inputs must have the same shape, got {xa.shape} and {xb.shape}')
-        if xa.ndim < 1 or xa.shape[-1] != self.n:
-            raise ValueError(f'signal length {xa.shape[-1] if xa.ndim else None} != plan n {self.n}')
-        npairs = int(np.prod(xa.shape[:-1])) if xa.ndim > 1 else 1
-        odt = np.dtype(np.complex128 if plv else np.float64)
-        shape = (self.nfreq, self.n_out) if plv else (self.nfreq, self.n_out, 4)
-        if out is None:
-            out = np.empty(shape, dtype=odt)
-        elif out.dtype != odt or not out.flags.c_contiguous or out.size != count:
-            raise ValueError('out must be a C-contiguous array of the right dtype and size')
-        L.check(L.lib().nw_execute_pair(self._h, xa.ctypes.data_as(ctypes.c_void_p), xb.ctypes.data_as(ctypes.c_void_p),
-                                        npairs, out.ctypes.data_as(ctypes.c_void_p), kind, L.NW_MEM_HOST))
-        return out
+        else:
+            xa = np.ascontiguousarray(xa, dtype=self.dtype)
+            xb = np.ascontiguousarray(xb, dtype=self.dtype)
+            if xa.shape != xb.shape:
+                raise ValueError(f'the two inputs must have the same shape, got {xa.shape} and {xb.shape}')
+            if xa.ndim < 1 or xa.shape[-1] != self.n:
+                raise ValueError(f'signal length {xa.shape[-1] if xa.ndim else None} != plan n {self.n}')
+            npairs = int(np.prod(xa.shape[:-1])) if xa.ndim > 1 else 1
+        plv = out_kind == 'plv_sum'
+        spec = ('sums', (self.nfreq, self.n_out) + (() if plv else (4,)), np.complex128 if plv else np.float64, False)
+        outs = self._outputs(xa, [out], [spec], ndarray_only=False)
+        self._epoch_execute(L.lib().nw_execute_pair, xa, (_ptr(xb), npairs), outs, (kind,))
+        return outs[0]
 
     def execute_conn(self, x, indices=None, out=None, out_kind: str = 'cross_sum'):
         """Multi-channel connectivity sums (nw_execute_conn): x (E, C, n), the E epochs of C
@@ -788,7 +765,7 @@ class Plan:
                   np.float64 if lag else np.complex128, False),
                  ('power', (nchan, self.nfreq, self.n_out), np.float64, True)][:1 if single else 2]
         cross, power = (out, None) if single or out is None else out
-        # (this call alone never asked that host outputs be ndarrays)
+        # (this call and execute_pair never asked that host outputs be ndarrays)
         outs = self._outputs(x, [cross, power], specs, ndarray_only=False)
         self._epoch_execute(L.lib().nw_execute_conn, x, (nep, nchan, _ptr(ia), _ptr(ib), npairs), outs, (kind,))
         return out if _is_device_tensor(x) else outs[0] if single else (outs[0], outs[1])

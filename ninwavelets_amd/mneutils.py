@@ -24,6 +24,21 @@ class EpochsWavelet:
         idx = self.epochs.ch_names.index(ch_name)
         return self.epochs.get_data()[:, idx, :]
 
+    def _pick(self, ch_names) -> np.ndarray:
+        """The (E, C, N) data of the channels ``ch_names``, in that order."""
+        idx = [self.epochs.ch_names.index(c) for c in list(ch_names)]
+        return self.epochs.get_data()[:, idx, :]
+
+    def _padded(self, n: int, padding: float):
+        """(k, n - k), k = round(padding * sfreq): the window of n-sample epochs that ``padding`` seconds
+        on each side leave; ValueError if it is empty."""
+        if not padding >= 0:
+            raise ValueError(f'padding must be >= 0 seconds, got {padding!r}')
+        k = int(round(padding * self.epochs.info['sfreq']))
+        if k >= n - k:
+            raise ValueError(f'padding of {padding} s ({k} samples on each side) leaves no sample of the {n}')
+        return k, n - k
+
     def cwt(self, ch_name: str, freqs, decim: int = 1) -> np.ndarray:
         """(epochs, F, N) complex (mneutils.py:26-40); ``decim`` (MNE's, as MorseMNE.cwt passes
         it, wavelets.py:170-191) keeps every decim-th sample of the last axis, here and below."""
@@ -93,9 +108,7 @@ class EpochsWavelet:
     def lag_connectivity(self, ch_names, freqs, method: str = 'wpli', indices=None, decim: int = 1):
         """``method`` (lag_batch's outs: pli, pli2_unbiased, dpli, wpli, wpli2_debiased, ciplv, ppc,
         lag_sum) for the channel pairs ``indices`` of ``ch_names``, (P, F, N), as connectivity."""
-        ch_names = list(ch_names)
-        idx = [self.epochs.ch_names.index(c) for c in ch_names]
-        waves = self.epochs.get_data()[:, idx, :]
+        waves = self._pick(ch_names)
         return self.wavelet.lag_connectivity_batch(waves, freqs, reuse=True, out=method, indices=indices, decim=decim)
 
     # -- over-time connectivity: one value per epoch, pair and scale, the sums taken over the samples
@@ -106,17 +119,10 @@ class EpochsWavelet:
         mne-connectivity's spectral_connectivity_time returns.  ``padding`` in seconds, as there: with
         k = round(padding * sfreq) the samples [k, N - k) of every epoch are summed (ValueError if
         that window is empty).  ``average=True``: the mean over the epochs, (P, F)."""
-        ch_names = list(ch_names)
-        idx = [self.epochs.ch_names.index(c) for c in ch_names]
-        waves = self.epochs.get_data()[:, idx, :]
-        n = waves.shape[-1]
-        if not padding >= 0:
-            raise ValueError(f'padding must be >= 0 seconds, got {padding!r}')
-        k = int(round(padding * self.epochs.info['sfreq']))
-        if k >= n - k:
-            raise ValueError(f'padding of {padding} s ({k} samples on each side) leaves no sample of the {n}')
+        waves = self._pick(ch_names)
+        window = self._padded(waves.shape[-1], padding)
         return self.wavelet.connectivity_time_batch(waves, freqs, reuse=True, out=method, indices=indices,
-                                                    window=(k, n - k), decim=decim, average=average)
+                                                    window=window, decim=decim, average=average)
 
     # -- envelope correlation: the amplitude-coupling counterpart, per epoch, pair and scale
     #    (WaveletBase.envelope_correlation_batch) ------------------------------------------------
@@ -127,17 +133,10 @@ class EpochsWavelet:
         returns per pair, with the wavelet rows as the analytic signals.  ``indices`` = (ia, ib),
         positions in ``ch_names`` (default: every pair a < b); ``padding`` as in connectivity_time;
         ``average=True``: the mean over the epochs, (P, F)."""
-        ch_names = list(ch_names)
-        idx = [self.epochs.ch_names.index(c) for c in ch_names]
-        waves = self.epochs.get_data()[:, idx, :]
-        n = waves.shape[-1]
-        if not padding >= 0:
-            raise ValueError(f'padding must be >= 0 seconds, got {padding!r}')
-        k = int(round(padding * self.epochs.info['sfreq']))
-        if k >= n - k:
-            raise ValueError(f'padding of {padding} s ({k} samples on each side) leaves no sample of the {n}')
+        waves = self._pick(ch_names)
+        window = self._padded(waves.shape[-1], padding)
         return self.wavelet.envelope_correlation_batch(waves, freqs, reuse=True, out=method, indices=indices,
-                                                       window=(k, n - k), decim=decim, average=average)
+                                                       window=window, decim=decim, average=average)
 
     # -- phase-amplitude coupling: one comodulogram per epoch and pair (WaveletBase.pac_batch) ------
     def pac(self, ch_names, phase_freqs, amp_freqs, method: str = 'direct_pac', indices=None, padding: float = 0.,
@@ -147,19 +146,12 @@ class EpochsWavelet:
         frequency list is transformed once.  ``indices`` = (phase channels, amplitude channels),
         positions in ``ch_names`` (default: every channel with itself); ``padding`` as in
         connectivity_time; ``average=True``: the mean over the epochs, (P, Fp, Fa)."""
-        ch_names = list(ch_names)
-        idx = [self.epochs.ch_names.index(c) for c in ch_names]
-        waves = self.epochs.get_data()[:, idx, :]
-        n = waves.shape[-1]
-        if not padding >= 0:
-            raise ValueError(f'padding must be >= 0 seconds, got {padding!r}')
-        k = int(round(padding * self.epochs.info['sfreq']))
-        if k >= n - k:
-            raise ValueError(f'padding of {padding} s ({k} samples on each side) leaves no sample of the {n}')
+        waves = self._pick(ch_names)
+        window = self._padded(waves.shape[-1], padding)
         pf, af = list(phase_freqs), list(amp_freqs)
         return self.wavelet.pac_batch(waves, pf + af, reuse=False, phase=np.arange(len(pf)),
                                       amp=np.arange(len(pf), len(pf) + len(af)), out=method, indices=indices,
-                                      window=(k, n - k), decim=decim, average=average)
+                                      window=window, decim=decim, average=average)
 
     # -- connectivity between many channels: one transform per epoch and channel, every pair's
     #    sums from it (WaveletBase.connectivity_batch; no reference counterpart) ---------------
@@ -168,7 +160,5 @@ class EpochsWavelet:
         channel pairs ``indices`` = (ia, ib), positions in ``ch_names`` (default: every pair
         a < b), (P, F, N): what mne-connectivity's spectral_connectivity_epochs(..., indices=...)
         returns per pair in its cwt_morlet mode."""
-        ch_names = list(ch_names)
-        idx = [self.epochs.ch_names.index(c) for c in ch_names]
-        waves = self.epochs.get_data()[:, idx, :]
+        waves = self._pick(ch_names)
         return self.wavelet.connectivity_batch(waves, freqs, reuse=True, out=method, indices=indices, decim=decim)
