@@ -421,7 +421,7 @@ static void print_ladder() {
 }
 
 // every rule of the table, one line each, for tests/test_host_asan.py to compare with the
-// tests' Python restatement (tests/fused_variants.py, tests/test_decim_cpu.py)
+// tests' Python restatement (tests/fused_variants.py)
 static void print_shapes() {
     using namespace nw;
     for (int dtype : {NW_F32, NW_F64})

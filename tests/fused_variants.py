@@ -2,7 +2,8 @@
 restated from ninwavelets_amd/csrc/nw_shape.h for the tests that steer rows into every
 instantiated variant (tests/test_gpu_dft_forms.py: analytic rows, tests/test_gpu_table_rows.py:
 table rows).  tests/test_host_asan.py compares this restatement, line by line, with what the
-header itself gives for every row of the size table (tests/asan/host_asan.cpp, mode `shapes`).
+header itself gives for every row of the size table (tests/asan/host_asan.cpp, mode `shapes`), and
+decim_rule with the header's decim_supported.
 
 A row's support ends at its last bin above kTailRel x the row's max |W| (nw_internal.h);
 wsupport_kernel rounds the pass-0 elements reaching it to wnz, pass0_variant picks the smallest
@@ -50,3 +51,10 @@ def row_wnz(row, n, dtype):
 
 def variant_of(wnz, variants):
     return min(v for v in variants if v >= max(wnz, 4))
+
+
+def decim_rule(n, decim):
+    """Where the decimated kernel runs (decim_supported, nw_shape.h): power-of-two 2048 <= n <= 16384, power-of-two
+    decim >= 2, n / decim >= 1024."""
+    pow2 = lambda v: v > 0 and v & (v - 1) == 0  # noqa: E731
+    return pow2(n) and 2048 <= n <= 16384 and pow2(decim) and decim >= 2 and n // decim >= 1024

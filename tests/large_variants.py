@@ -5,7 +5,14 @@ for the tests that steer rows into every variant (tests/test_gpu_large_variants.
 n = N1 * N2 (split_of); a row pass workgroup owns rows k1 of one scale, thread t of its
 T = N2 / E threads the bins k = k1 + N1 * (t + r T), r < E (rows_kernel).  With km the scale's
 last bin above the tail threshold (Plan.row_support()), elements r >= need(km, k1) are zero for
-every thread, and the row runs the smallest instantiated NZ >= need (nzv_of)."""
+every thread, and the row runs the smallest instantiated NZ >= need (nzv_of).
+
+tol_f32 is the two-pass form's fp32 tolerance against the fp64 oracle (test_gpu_large.py, where it is derived)."""
+
+
+def tol_f32(n):
+    """max |out - ref| <= tol_f32(n) max |ref|: 1e-5 up to n = 2^16, 3e-5 above."""
+    return 1e-5 if n <= (1 << 16) else 3e-5
 
 
 def split(n):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from epoch_cases import FakeEpochs
 
 import ninwavelets_amd as nw
 from ninwavelets_amd import _lib as L
@@ -167,14 +168,6 @@ def test_check_indices():
     for bad in (([0, 1], [1]), ([0], [4]), ([-1], [0]), ([0.5], [1.]), ([[0]], [[1]]), 3, ([0],)):
         with pytest.raises(ValueError, match='indices'):
             check_indices(bad, 4)
-
-
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
 
 
 def test_bad_arguments_are_value_errors_before_any_device_work():

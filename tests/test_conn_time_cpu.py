@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from epoch_cases import FakeEpochs
 
 import ninwavelets_amd as nw
 from ninwavelets_amd import _lib as L
@@ -136,14 +137,6 @@ def test_window_arithmetic(decim):
     for bad in ((-1, 5), (6, 5), (0, n + 1), (0.5, 3), (1,), 3, 'ab', (1, 2, 3)):
         with pytest.raises(ValueError, match='window'):
             time_window(n, decim, bad, False)
-
-
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
 
 
 def test_bad_arguments_are_value_errors_before_any_device_work():

@@ -9,16 +9,11 @@ reaches."""
 import numpy as np
 import pytest
 
+from fused_variants import decim_rule as rule
 from oracle import nw_oracle as O
 
 import ninwavelets_amd as nw
 from ninwavelets_amd import _lib as L
-
-
-def rule(n, decim):
-    """The issue's rule: power-of-two 2048 <= n <= 16384, power-of-two decim >= 2, n / decim >= 1024."""
-    pow2 = lambda v: v > 0 and v & (v - 1) == 0  # noqa: E731
-    return pow2(n) and 2048 <= n <= 16384 and pow2(decim) and decim >= 2 and n // decim >= 1024
 
 
 def test_decim_supported_table():

@@ -5,24 +5,16 @@ the one real exchange, the all_reduce of fp64 epoch-reduction partial sums
 (ninwavelets_amd/dist.py).  The per-rank partial sums here come from the CPU
 oracle (the checker), standing in for each rank's device result."""
 import os
-import socket
 
 import numpy as np
 import pytest
 
+from dist_cases import free_port
 from oracle import nw_oracle as O
 
 from ninwavelets_amd import dist as D
 
 FREQS = [2., 5., 11., 23., 47.]
-
-
-def free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 def epochs(E=7, n=512, seed=3):

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from dist_cases import free_port
 from oracle import nw_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +39,6 @@ def _worker(rank, world, port, out_dir):
 
 def test_two_rank_epochs_reduce_on_device(tmp_path):
     import torch.multiprocessing as mp
-    from test_dist_cpu import free_port
     mp.spawn(_worker, args=(2, free_port(), str(tmp_path)), nprocs=2, join=True)
     c = O.epochs_cwt('morse', data(), FREQS)
     ref_p = np.mean(np.abs(c) ** 2, axis=0)

@@ -10,11 +10,12 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from epoch_cases import FREQS, FakeEpochs
+from epoch_cases import lagged_rows as oracle_rows
 
 import ninwavelets_amd as nw
 from ninwavelets_amd import _lib as L
 from ninwavelets_amd.engine import ENV_KINDS, ENV_OUTS, all_pairs, finalize_env
-from test_gpu_conn_time import FREQS, oracle_rows
 
 MEASURES = ('aec', 'aec_directed', 'aec_orth', 'aec_orth_signed')
 
@@ -169,14 +170,6 @@ def test_diagnostic_switches_compile(tmp_path):
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert os.path.getsize(out) > 0
-
-
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
 
 
 def test_bad_arguments_are_value_errors_before_any_device_work():

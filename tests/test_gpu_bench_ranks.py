@@ -12,6 +12,7 @@ import sys
 import pytest
 
 from conftest import ROOT
+from dist_cases import free_port
 
 pytestmark = pytest.mark.gpu
 
@@ -143,7 +144,6 @@ def test_rccl_single_rank_bench_path():
     """The driver's N-GPU launch (torchrun, one rank per GPU, backend nccl = RCCL) at N = 1 on
     the lease: process group over RCCL, barriers, the device all_reduce(MAX) of the elapsed
     time, real kernels (the sharded loop is mneutils.py:39's per-epoch batching)."""
-    from test_dist_cpu import free_port
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
                         '--master-addr', '127.0.0.1', '--master-port', str(free_port()),
@@ -185,7 +185,6 @@ def test_rccl_device_collectives_of_dist(tmp_path):
     import numpy as np
     import torch.multiprocessing as mp
     from oracle import nw_oracle as O
-    from test_dist_cpu import free_port
     mp.spawn(_nccl_worker, args=(1, free_port(), str(tmp_path)), nprocs=1, join=True)
     got = np.load(tmp_path / 'nccl.npz')
     c = O.epochs_cwt('morse', got['x'], [3., 9., 27., 81.])

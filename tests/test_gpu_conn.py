@@ -6,9 +6,9 @@ For epochs e, channels c with rows y_e,c (F, n_out) and pairs p = (a, b):
     S_p = sum_e y_a conj(y_b),  P_cc = sum_e |y_c|^2,  Phi_p = sum_e (y_a/|y_a|) conj(y_b/|y_b|)
 every sum in fp64 in epoch order.  References are formed here from oracle.nw_oracle in complex128.
 
-Inputs: rng = default_rng(2300 + n), common = rng.standard_normal((E, 1, n)),
+Inputs: the plain recipe of epoch_cases.py: rng = default_rng(2300 + n), common = rng.standard_normal((E, 1, n)),
 x = 0.6 common + 0.8 rng.standard_normal((E, C, n)); Morse(1000) with its default b, r and the nine
-scales of test_gpu_pair.py (three for the C = 17 tile case and the 2^15 case).
+scales FREQS (three, FREQS3, for the C = 17 tile case and the 2^15 case).
 
 Bounds (those of test_gpu_pair.py).  A_e,c: that signal's max|y| over (F, N); tol: 1e-12 fp64,
 1e-5 fp32, 2e-5 fp32 on chirp-z lengths.
@@ -22,15 +22,12 @@ The transform rows of the fp32 one-pass kernel at n <= 4096 carry two signals pe
 signal's fp32 rows depend (in rounding) on its neighbour in the chunk: the exact comparisons between
 differently chunked calls are made in fp64, where a row depends on its signal alone."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from oracle import nw_oracle as O
+from epoch_cases import (EPOCH_AXIS, FREQS, SHAPES, FakeEpochs, forms, morse_plan, run_under_bounds_checks, tol_of)
+from epoch_cases import plain_rows as oracle_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -38,37 +35,9 @@ import ninwavelets_amd as nw  # noqa: E402
 from ninwavelets_amd import _lib as L  # noqa: E402
 from ninwavelets_amd.engine import PAIR_OUTS, all_pairs, finalize_conn, finalize_pair  # noqa: E402
 
-FREQS = [4., 7., 12., 20., 40., 70., 120., 200., 300.]
-FREQS3 = [3., 30., 200.]
 V = 0.01
-CHIRP = (1201,)
 DTYPES = ['float32', 'float64']
 OUTS = ['cross_sum', 'plv_sum', 'csd', 'coherency', 'coherence', 'imcoh', 'plv']
-
-
-def tol_of(n, dtype):
-    if dtype == 'float64':
-        return 1e-12
-    return 2e-5 if n in CHIRP else 1e-5
-
-
-_ROWS = {}
-
-
-def oracle_rows(n, E, C, dtype, freqs):
-    """(x, y): the inputs (E, C, n) in the compute dtype and their complex128 CWT rows
-    (E, C, F, n), computed once per case and shared (read-only)."""
-    key = (n, E, C, dtype, tuple(freqs))
-    if key not in _ROWS:
-        rng = np.random.default_rng(2300 + n)
-        common = rng.standard_normal((E, 1, n))
-        x = (0.6 * common + 0.8 * rng.standard_normal((E, C, n))).astype(dtype)
-        rows = O.fft_wavelets('morse', freqs, 1000., n / 1000., False)
-        y = np.stack([np.stack([O.cwt_from_rows(s.astype(np.float64), rows, False) for s in ep]) for ep in x])
-        x.setflags(write=False)
-        y.setflags(write=False)
-        _ROWS[key] = (x, y)
-    return _ROWS[key]
 
 
 def sums_of(y, ia, ib):
@@ -85,12 +54,6 @@ def sums_of(y, ia, ib):
     return s, power, phi
 
 
-def morse_plan(n, dtype, freqs, max_batch, **kw):
-    p = nw.Plan(n, len(freqs), dtype, max_batch=max_batch, **kw)
-    p.set_wavelet('morse', [17.5, 3.], np.asarray(freqs), L.trans_grid(n / 1000., 1000., False))
-    return p
-
-
 def run_conn(n, dtype, freqs, max_batch, x, indices=None, **kw):
     """(cross, power, phi, stats after cross_sum, stats after plv_sum) of one plan."""
     p = morse_plan(n, dtype, freqs, max_batch, **kw)
@@ -104,17 +67,11 @@ def run_conn(n, dtype, freqs, max_batch, x, indices=None, **kw):
     return cross, power, phi, st_c, st_p
 
 
-# (id, n, dtype, E, C, freqs, plan keywords, decim, kernel of the form)
-CASES = [('1024-f32', 1024, 'float32', 5, 5, FREQS, {}, 1, 'nw_fused_pair_kernel'),
-         ('1024-f64', 1024, 'float64', 5, 5, FREQS, {}, 1, 'nw_fused_kernel'),
-         ('chirp-1201-f32', 1201, 'float32', 5, 5, FREQS, {}, 1, 'nw_chirp_kernel'),      # tail tile: 49 samples
-         ('chirp-1201-f64', 1201, 'float64', 5, 5, FREQS, {}, 1, 'nw_chirp_kernel'),
-         ('decim-4096', 4096, 'float32', 5, 5, FREQS, {}, 4, 'nw_fused_decim_kernel'),
-         ('e32-8192', 8192, 'float32', 5, 5, FREQS, {}, 1, 'nw_fused_kernel'),
-         ('rocfft-1000', 1000, 'float32', 5, 5, FREQS, {'engine': 'rocfft'}, 1, 'k1_multiply'),
-         ('twopass-32768', 32768, 'float32', 2, 3, FREQS3, {}, 1, 'cols_kernel'),
-         # more than 16 channels: several pair tiles, some of them partial
-         ('tiles-17ch-f64', 1024, 'float64', 3, 17, FREQS3, {}, 1, 'nw_fused_kernel')]
+# (id, n, dtype, E, C, freqs, plan keywords, decim, kernel of the form): five epochs but for the rows of SHAPES
+CASES = []
+for name, n, dtype, kw, decim, _, kernel in forms(*EPOCH_AXIS):
+    E, C, freqs = SHAPES.get(name, (5, 5, FREQS))
+    CASES.append((name, n, dtype, E, C, freqs, kw, decim, kernel))
 
 
 @pytest.mark.parametrize('case', CASES, ids=[c[0] for c in CASES])
@@ -273,14 +230,6 @@ def test_chunking_changes_nothing(n):
         assert np.array_equal(got, want)
 
 
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
-
-
 def test_class_layer():
     """connectivity_batch against cross_batch pair by pair (T2's bounds on the sums; every finalised
     output is finalize_pair of the call's own sums, exactly), decim, EpochsWavelet.connectivity."""
@@ -421,12 +370,7 @@ def test_edge_cases_and_errors(dtype):
 def test_conn_under_bounds_checks():
     """The debug library (kernel bounds checks, nw_dcheck.h) on several pair tiles with partial
     ones (C = 17) and on a tail tile (n = 1201): no check fails."""
-    code = ('import sys; sys.path.insert(0, %r)\n'
-            'import numpy as np\n'
-            'import ninwavelets_amd as nw\n'
-            'from ninwavelets_amd import _lib as L\n'
-            'print("debug", L.lib().nw_debug_bounds())\n'
-            'rng = np.random.default_rng(1)\n'
+    body = ('rng = np.random.default_rng(1)\n'
             'for n, E, C, dt in ((1024, 3, 17, "float64"), (1201, 3, 5, "float32")):\n'
             '    x = rng.standard_normal((E, C, n)).astype(dt)\n'
             '    p = nw.Plan(n, 3, dt, max_batch=2 * C + 3)\n'
@@ -434,9 +378,6 @@ def test_conn_under_bounds_checks():
             '    c, pw = p.execute_conn(x)\n'
             '    phi = p.execute_conn(x, ([C - 1, 0, 2], [0, 0, 2]), out_kind="plv_sum")\n'
             '    print("ok", n, bool(np.all(np.isfinite(c)) and np.all(pw > 0) and np.all(np.isfinite(phi))))\n'
-            '    p.close()\n') % ROOT
-    env = dict(os.environ, NINWAVE_LIB=os.path.join(ROOT, 'ninwavelets_amd', 'libninwave_debug.so'))
-    r = subprocess.run([sys.executable, '-u', '-c', code], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = r.stdout.splitlines()
-    assert 'debug 1' in lines and 'ok 1024 True' in lines and 'ok 1201 True' in lines, r.stdout
+            '    p.close()\n')
+    lines = run_under_bounds_checks(body)
+    assert 'ok 1024 True' in lines and 'ok 1201 True' in lines, lines

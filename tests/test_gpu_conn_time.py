@@ -8,7 +8,7 @@ and m_j = Im y_a conj(y_b) at s_j:
     L0 .. L3 = sum_j of m_j, |m_j|, m_j^2, sgn m_j
 one value per (e, pair, f).  References are formed here from oracle.nw_oracle in complex128.
 
-Inputs: the lagged recipe of test_gpu_lag.py: rng = default_rng(2300 + n), x[:, c] = 0.6 roll(common, 3 c) +
+Inputs: the lagged recipe of epoch_cases.py: rng = default_rng(2300 + n), x[:, c] = 0.6 roll(common, 3 c) +
 0.8 noise[:, c]; Morse(1000) with its default b, r and the nine scales FREQS (three, FREQS3, where stated).
 E = 3 epochs and C = 5 channels unless stated; max_batch = 2 C + 3: chunks of 2 and 1 epochs.
 Windows (in the plan's output samples): full, (0, 1), (37, 1001) and an empty one; the full-rate n = 1000 plan
@@ -31,15 +31,12 @@ max |y| over (F, N) of the undecimated rows.
       2 tol) where that bound is <= 0.05: at least 0.7 (wpli) / 0.85 (coherence) of every pair's (e, f), asserted
       on the reference alone; pli and dpli from the L3 bound.
   T5  the layers; T6 the debug library."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from oracle import nw_oracle as O
+from epoch_cases import (FREQS, FREQS3, OVER_TIME, SHAPES, FakeEpochs, forms, lane_sum, morse_plan,
+                         run_under_bounds_checks, tol_of, vis_of, windows_of)
+from epoch_cases import lagged_rows as oracle_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -48,48 +45,8 @@ from ninwavelets_amd import _lib as L  # noqa: E402
 from ninwavelets_amd.engine import (CONN_OUTS, LAG_OUTS, all_pairs, finalize_conn_time, finalize_lag,  # noqa: E402
                                     finalize_pair, time_window)
 
-FREQS = [4., 7., 12., 20., 40., 70., 120., 200., 300.]
-FREQS3 = [3., 30., 200.]
-CHIRP = (1201,)
 KINDS = ('cross_sum', 'plv_sum', 'lag_sum')
 MEASURES = [k for k in list(CONN_OUTS) + list(LAG_OUTS) if not k.endswith('_sum')]
-
-
-def tol_of(n, dtype):
-    if dtype == 'float64':
-        return 1e-12
-    return 2e-5 if n in CHIRP else 1e-5
-
-
-def vis_of(dtype):
-    return 1e-9 if dtype == 'float64' else 1e-4
-
-
-_ROWS = {}
-
-
-def oracle_rows(n, E, C, dtype, freqs):
-    """(x, y): the inputs (E, C, n) in the compute dtype and their complex128 CWT rows
-    (E, C, F, n), computed once per case and shared (read-only)."""
-    key = (n, E, C, dtype, tuple(freqs))
-    if key not in _ROWS:
-        rng = np.random.default_rng(2300 + n)
-        common = rng.standard_normal((E, 1, n))
-        noise = rng.standard_normal((E, C, n))
-        x = np.stack([0.6 * np.roll(common[:, 0], 3 * c, axis=-1) + 0.8 * noise[:, c] for c in range(C)],
-                     axis=1).astype(dtype)
-        rows = O.fft_wavelets('morse', freqs, 1000., n / 1000., False)
-        y = np.stack([np.stack([O.cwt_from_rows(s.astype(np.float64), rows, False) for s in ep]) for ep in x])
-        x.setflags(write=False)
-        y.setflags(write=False)
-        _ROWS[key] = (x, y)
-    return _ROWS[key]
-
-
-def morse_plan(n, dtype, freqs, max_batch, **kw):
-    p = nw.Plan(n, len(freqs), dtype, max_batch=max_batch, **kw)
-    p.set_wavelet('morse', [17.5, 3.], np.asarray(freqs), L.trans_grid(n / 1000., 1000., False))
-    return p
 
 
 def run_all(p, x, indices, win, step):
@@ -98,19 +55,6 @@ def run_all(p, x, indices, win, step):
     phi = p.execute_conn_time(x, indices, win, step, out_kind='plv_sum')
     lag = p.execute_conn_time(x, indices, win, step, out_kind='lag_sum')
     return S, P, phi, lag
-
-
-def windows_of(n, n_out, host_decim):
-    """(name, (t0, t1), step) in the plan's output samples."""
-    if host_decim > 1:                       # a full-rate plan summing every host_decim-th sample
-        out = []
-        for name, w in (('full', None), ('one', (0, 1)), ('inner', (37, min(1001, n))), ('empty', (500, 500))):
-            t0, t1, step, _ = time_window(n, host_decim, w, False)
-            out.append((name, (t0, t1), step))
-        return out
-    # (stride: not one of the listed windows; the step > 1 addressing on every form, bit for bit in T2)
-    return [('full', (0, n_out), 1), ('one', (0, 1), 1), ('inner', (37, 1001), 1), ('empty', (500, 500), 1),
-            ('stride', (5, n_out - 3), 4)]
 
 
 def ref_sums(y, ia, ib, idx):
@@ -163,25 +107,6 @@ def check_t1(name, got, y, A, ia, ib, idx, tol, dtype, listed=True):
     return rS, rP, rphi, rlag, K
 
 
-def lane_sum(terms):
-    """The contract's sum of ``terms`` (..., T) along the last axis: 64 lane sums, lane l adding j = l,
-    l + 64, ... in order from +0.0, then v = v[:h] + v[h:] for h = 32 .. 1.  (A lane or tail sample
-    without a j < T adds nothing: padding with +0.0 is the same, an accumulator never being -0.0.)"""
-    T = terms.shape[-1]
-    ntl = -(-T // 64)
-    pad = np.zeros(terms.shape[:-1] + (ntl * 64,))
-    pad[..., :T] = terms
-    pad = pad.reshape(terms.shape[:-1] + (ntl, 64))
-    v = np.zeros(terms.shape[:-1] + (64,))
-    for it in range(ntl):
-        v = v + pad[..., it, :]
-    h = 32
-    while h >= 1:
-        v = v[..., :h] + v[..., h:]
-        h //= 2
-    return v[..., 0]
-
-
 def own_sums(rows, ia, ib, idx):
     """(S, P, Phi, lag) of the plan's own complex128 rows (E, C, F, n_out) in the contract's order."""
     yw = rows[..., idx]
@@ -203,16 +128,12 @@ def own_sums(rows, ia, ib, idx):
     return S, P, phi, lag
 
 
-# (id, n, dtype, E, C, freqs, plan keywords, device decim, host decim, kernel of the form)
-CASES = [('1024-f32', 1024, 'float32', 3, 5, FREQS, {}, 1, 1, 'nw_fused_pair_kernel'),
-         ('1024-f64', 1024, 'float64', 3, 5, FREQS, {}, 1, 1, 'nw_fused_kernel'),
-         ('chirp-1201-f32', 1201, 'float32', 3, 5, FREQS, {}, 1, 1, 'nw_chirp_kernel'),     # tail tile: 49 samples
-         ('chirp-1201-f64', 1201, 'float64', 3, 5, FREQS, {}, 1, 1, 'nw_chirp_kernel'),
-         ('decim-4096', 4096, 'float32', 3, 5, FREQS, {}, 4, 1, 'nw_fused_decim_kernel'),
-         ('rocfft-1000-step4', 1000, 'float32', 3, 5, FREQS, {'engine': 'rocfft'}, 1, 4, 'k1_multiply'),
-         ('twopass-32768', 32768, 'float32', 2, 3, FREQS3, {}, 1, 1, 'cols_kernel'),         # 512 sample tiles
-         # more than 16 channels: three pair tiles, some of them partial
-         ('tiles-17ch-f64', 1024, 'float64', 3, 17, FREQS3, {}, 1, 1, 'nw_fused_kernel')]
+# (id, n, dtype, E, C, freqs, plan keywords, device decim, host decim, kernel of the form): three epochs but for the
+# rows of SHAPES
+CASES = []
+for name, n, dtype, kw, decim, host_decim, kernel in forms(*OVER_TIME):
+    E, C, freqs = SHAPES.get(name, (3, 5, FREQS))
+    CASES.append((name, n, dtype, E, C, freqs, kw, decim, host_decim, kernel))
 
 
 @pytest.mark.parametrize('case', CASES, ids=[c[0] for c in CASES])
@@ -458,14 +379,6 @@ def test_measures(case):
     assert np.all(dpli <= 2 * K / T + 1e-15) and np.all(ddpli <= K / T + 1e-15)
 
 
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
-
-
 def test_class_layer():
     """T5: connectivity_time_batch is finalize_conn_time of Plan.execute_conn_time, with device decim and with
     host decim; average; EpochsWavelet's padding."""
@@ -548,12 +461,7 @@ def test_class_layer():
 def test_conn_time_under_bounds_checks():
     """T6: the debug library (kernel bounds checks, nw_dcheck.h) on n = 1024, on a tail tile (n = 1201) and on
     several pair tiles with partial ones (C = 17), every kind, three windows and a short list: no check fails."""
-    code = ('import sys; sys.path.insert(0, %r)\n'
-            'import numpy as np\n'
-            'import ninwavelets_amd as nw\n'
-            'from ninwavelets_amd import _lib as L\n'
-            'print("debug", L.lib().nw_debug_bounds())\n'
-            'rng = np.random.default_rng(1)\n'
+    body = ('rng = np.random.default_rng(1)\n'
             'for tag, n, E, C, dt in (("a", 1024, 3, 5, "float32"), ("b", 1201, 3, 5, "float64"), ("c", 1024, 3, 17, "float64")):\n'
             '    x = rng.standard_normal((E, C, n)).astype(dt)\n'
             '    p = nw.Plan(n, 3, dt, max_batch=2 * C + 3)\n'
@@ -566,9 +474,6 @@ def test_conn_time_under_bounds_checks():
             '            for a in (full if kind == "cross_sum" else (full,)) + (short if kind == "cross_sum" else (short,)):\n'
             '                ok = ok and bool(np.all(np.isfinite(a))) and a.shape[0] == E\n'
             '    print("ok", tag, ok)\n'
-            '    p.close()\n') % ROOT
-    env = dict(os.environ, NINWAVE_LIB=os.path.join(ROOT, 'ninwavelets_amd', 'libninwave_debug.so'))
-    r = subprocess.run([sys.executable, '-u', '-c', code], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = r.stdout.splitlines()
-    assert 'debug 1' in lines and 'ok a True' in lines and 'ok b True' in lines and 'ok c True' in lines, r.stdout
+            '    p.close()\n')
+    lines = run_under_bounds_checks(body)
+    assert 'ok a True' in lines and 'ok b True' in lines and 'ok c True' in lines, lines

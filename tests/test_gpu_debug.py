@@ -12,10 +12,9 @@ import sys
 import pytest
 
 from conftest import ROOT
+from epoch_cases import DEBUG_LIB, run_under_bounds_checks
 
 pytestmark = pytest.mark.gpu
-
-DEBUG_LIB = os.path.join(ROOT, 'ninwavelets_amd', 'libninwave_debug.so')
 
 
 def child(args, timeout=600):
@@ -26,16 +25,11 @@ def child(args, timeout=600):
 def test_debug_checks_fire():
     """A kernel whose checks fail on purpose (lanes >= 32 of one 64-lane block): the status is
     NW_E_BOUNDS with the count and the site; the next call starts clean."""
-    code = ('import sys; sys.path.insert(0, %r)\n'
-            'from ninwavelets_amd import _lib as L\n'
-            'lib = L.lib()\n'
-            'print("debug", lib.nw_debug_bounds())\n'
+    body = ('lib = L.lib()\n'
             'print("rc", lib.nw_debug_selftest(0))\n'
             'print("msg", lib.nw_last_error().decode())\n'
-            'print("rc2", lib.nw_debug_selftest(0))\n') % ROOT
-    r = child(['-c', code], timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = dict(ln.split(' ', 1) for ln in r.stdout.splitlines() if ' ' in ln)
+            'print("rc2", lib.nw_debug_selftest(0))\n')
+    out = dict(ln.split(' ', 1) for ln in run_under_bounds_checks(body) if ' ' in ln)
     assert out['debug'] == '1'
     assert int(out['rc']) == -7 and int(out['rc2']) == -7          # NW_E_BOUNDS, each time
     assert '32 failing check(s), first at nw_kernels.hip:' in out['msg'], out['msg']

@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from epoch_cases import FakeEpochs
 from oracle import nw_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -252,14 +253,6 @@ def test_decim_class_api(dtype):
             assert np.max(np.abs(got - want)) <= 3 * itc_tol, o
         else:
             assert np.max(np.abs(got - want)) <= 4 * TOL[dtype] * np.max(np.abs(want)), o
-
-
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
 
 
 def test_decim_epochs_wavelet():

@@ -7,9 +7,9 @@ per sample, A_c = |y_c|, the unit phasors w_c = y_c / |y_c|, s = |Im w_a conj(w_
     env_sum       sum_j A_a A_b                                                   (E, P, F)
     env_orth_sum  sum_j of u, u^2, u A_b, v, v^2, v A_a                            (E, P, F, 6)
     chan          sum_j of A_c, re^2 + im^2                                        (E, C, F, 2)
-References are formed here from oracle.nw_oracle in complex128.  Inputs, cases, windows, max_batch = 2 C + 3
-and tol (1e-12 fp64, 1e-5 fp32, 2e-5 on chirp lengths) are those of test_gpu_conn_time.py, whose cached
-oracle rows are shared; Amax_c is the signal's max |y| over (F, N) of the undecimated rows.
+References are formed here from oracle.nw_oracle in complex128.  Inputs (the lagged recipe of epoch_cases.py), cases,
+windows, max_batch = 2 C + 3 and tol (1e-12 fp64, 1e-5 fp32, 2e-5 on chirp lengths) are those of
+test_gpu_conn_time.py, and the cached oracle rows are shared with it; Amax_c is the signal's max |y| over (F, N) of the undecimated rows.
 
   T1  against the oracle, first-order bounds.  Per sample, with eta_c = 2 tol Amax_c, theta_c = eta_c / |y_c|,
       sigma = min(1, theta_a + theta_b + theta_a theta_b), du = eta_a s + |y_a| sigma + eta_a sigma (dv likewise):
@@ -28,22 +28,18 @@ oracle rows are shared; Amax_c is the signal's max |y| over (F, N) of the undeci
       the reference alone); fp64 every finalised kind within its propagated bound + 1e-9 (T 2^-53 = 1.1e-13 of
       summation rounding, times sum x^2 / var <= 830, times four sums).
   T5  the layers; T6 the debug library."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from epoch_cases import (FREQS, FREQS3, OVER_TIME, SHAPES, FakeEpochs, forms, lane_sum, morse_plan,
+                         run_under_bounds_checks, tol_of, windows_of)
+from epoch_cases import lagged_rows as oracle_rows
 
 pytestmark = pytest.mark.gpu
 
 import ninwavelets_amd as nw  # noqa: E402
 from ninwavelets_amd import _lib as L  # noqa: E402
 from ninwavelets_amd.engine import ENV_OUTS, all_pairs, finalize_env, time_window  # noqa: E402
-from test_gpu_conn_time import (CASES, FREQS, FREQS3, FakeEpochs, lane_sum, morse_plan, oracle_rows,  # noqa: E402
-                                tol_of, windows_of)
 
 KINDS = ('env_sum', 'env_orth_sum')
 MEASURES = ('aec', 'aec_directed', 'aec_orth', 'aec_orth_signed')
@@ -119,6 +115,13 @@ def own_env(rows, ia, ib, idx):
     p1, p2 = re * re, im * im
     chan = np.stack([lane_sum(h), lane_sum(p1 + p2)], axis=-1)
     return lane_sum(Aa * Ab), orth, chan, h.max(axis=-1)
+
+
+# (id, n, dtype, E, C, freqs, plan keywords, device decim, host decim, kernel of the form): test_gpu_conn_time.py's
+CASES = []
+for name, n, dtype, kw, decim, host_decim, kernel in forms(*OVER_TIME):
+    E, C, freqs = SHAPES.get(name, (3, 5, FREQS))
+    CASES.append((name, n, dtype, E, C, freqs, kw, decim, host_decim, kernel))
 
 
 @pytest.mark.parametrize('case', CASES, ids=[c[0] for c in CASES])
@@ -464,12 +467,7 @@ def test_class_layer():
 def test_env_time_under_bounds_checks():
     """T6: the debug library (kernel bounds checks, nw_dcheck.h) on n = 1024, on a tail tile (n = 1201) and on
     several pair tiles with partial ones (C = 17), both modes, five windows and a short list: no check fails."""
-    code = ('import sys; sys.path.insert(0, %r)\n'
-            'import numpy as np\n'
-            'import ninwavelets_amd as nw\n'
-            'from ninwavelets_amd import _lib as L\n'
-            'print("debug", L.lib().nw_debug_bounds())\n'
-            'rng = np.random.default_rng(1)\n'
+    body = ('rng = np.random.default_rng(1)\n'
             'for tag, n, E, C, dt in (("a", 1024, 3, 5, "float32"), ("b", 1201, 3, 5, "float64"), ("c", 1024, 3, 17, "float64")):\n'
             '    x = rng.standard_normal((E, C, n)).astype(dt)\n'
             '    p = nw.Plan(n, 3, dt, max_batch=2 * C + 3)\n'
@@ -482,9 +480,6 @@ def test_env_time_under_bounds_checks():
             '            for a in full + short:\n'
             '                ok = ok and bool(np.all(np.isfinite(a))) and a.shape[0] == E\n'
             '    print("ok", tag, ok)\n'
-            '    p.close()\n') % ROOT
-    env = dict(os.environ, NINWAVE_LIB=os.path.join(ROOT, 'ninwavelets_amd', 'libninwave_debug.so'))
-    r = subprocess.run([sys.executable, '-u', '-c', code], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = r.stdout.splitlines()
-    assert 'debug 1' in lines and 'ok a True' in lines and 'ok b True' in lines and 'ok c True' in lines, r.stdout
+            '    p.close()\n')
+    lines = run_under_bounds_checks(body)
+    assert 'ok a True' in lines and 'ok b True' in lines and 'ok c True' in lines, lines

@@ -6,10 +6,10 @@ For epochs e, channels c with rows y_e,c (F, n_out), a pair (a, b) and m_e = Im 
     L0 = sum_e m_e,  L1 = sum_e |m_e|,  L2 = sum_e m_e^2,  L3 = sum_e sgn m_e
 every sum in fp64 in epoch order.  References are formed here from oracle.nw_oracle in complex128.
 
-Inputs: the recipe of test_gpu_conn.py with a lag, so that the sign sums are not centred on 0:
-rng = default_rng(2300 + n), common = rng.standard_normal((E, 1, n)), noise = rng.standard_normal((E, C, n)),
+Inputs: the lagged recipe of epoch_cases.py, test_gpu_conn.py's with a lag, so that the sign sums are not centred
+on 0: rng = default_rng(2300 + n), common = rng.standard_normal((E, 1, n)), noise = rng.standard_normal((E, C, n)),
 x[:, c] = 0.6 roll(common[:, 0], 3 c) + 0.8 noise[:, c]; Morse(1000) with its default b, r and the nine
-scales of test_gpu_pair.py (three where stated).
+scales FREQS (three, FREQS3, where stated).
 
 Bounds.  A_e,c: that signal's max|y| over (F, N) of the undecimated rows; S = sum_e A_e,a A_e,b;
 tol: 1e-12 fp64, 1e-5 fp32, 2e-5 fp32 on chirp-z lengths (the per-signal contract).
@@ -28,15 +28,13 @@ tol: 1e-12 fp64, 1e-5 fp32, 2e-5 fp32 on chirp-z lengths (the per-signal contrac
 The exact comparisons between differently chunked calls are made in fp64, where a row depends on its
 signal alone (test_gpu_conn.py)."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from oracle import nw_oracle as O
+from epoch_cases import (EPOCH_AXIS, FREQS, SHAPES, FakeEpochs, forms, morse_plan, run_under_bounds_checks, tol_of,
+                         vis_of)
+from epoch_cases import lagged_rows as oracle_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -44,43 +42,9 @@ import ninwavelets_amd as nw  # noqa: E402
 from ninwavelets_amd import _lib as L  # noqa: E402
 from ninwavelets_amd.engine import LAG_OUTS, all_pairs, finalize_lag  # noqa: E402
 
-FREQS = [4., 7., 12., 20., 40., 70., 120., 200., 300.]
-FREQS3 = [3., 30., 200.]
 W = 0.003
-CHIRP = (1201,)
 DTYPES = ['float32', 'float64']
 LAG_NAMES = ['pli', 'pli2_unbiased', 'dpli', 'wpli', 'wpli2_debiased']
-
-
-def tol_of(n, dtype):
-    if dtype == 'float64':
-        return 1e-12
-    return 2e-5 if n in CHIRP else 1e-5
-
-
-def vis_of(dtype):
-    return 1e-9 if dtype == 'float64' else 1e-4
-
-
-_ROWS = {}
-
-
-def oracle_rows(n, E, C, dtype, freqs):
-    """(x, y): the inputs (E, C, n) in the compute dtype and their complex128 CWT rows
-    (E, C, F, n), computed once per case and shared (read-only)."""
-    key = (n, E, C, dtype, tuple(freqs))
-    if key not in _ROWS:
-        rng = np.random.default_rng(2300 + n)
-        common = rng.standard_normal((E, 1, n))
-        noise = rng.standard_normal((E, C, n))
-        x = np.stack([0.6 * np.roll(common[:, 0], 3 * c, axis=-1) + 0.8 * noise[:, c] for c in range(C)],
-                     axis=1).astype(dtype)
-        rows = O.fft_wavelets('morse', freqs, 1000., n / 1000., False)
-        y = np.stack([np.stack([O.cwt_from_rows(s.astype(np.float64), rows, False) for s in ep]) for ep in x])
-        x.setflags(write=False)
-        y.setflags(write=False)
-        _ROWS[key] = (x, y)
-    return _ROWS[key]
 
 
 def lag_of(y, ia, ib, floor, scale=None):
@@ -97,12 +61,6 @@ def lag_of(y, ia, ib, floor, scale=None):
         sums[..., 3] += np.sign(m)
         seen &= np.abs(m) >= floor * (np.abs(a) * np.abs(b) if scale is None else scale[e][:, None, None])
     return sums, seen
-
-
-def morse_plan(n, dtype, freqs, max_batch, **kw):
-    p = nw.Plan(n, len(freqs), dtype, max_batch=max_batch, **kw)
-    p.set_wavelet('morse', [17.5, 3.], np.asarray(freqs), L.trans_grid(n / 1000., 1000., False))
-    return p
 
 
 def run_lag(n, dtype, freqs, max_batch, x, indices=None, **kw):
@@ -134,17 +92,12 @@ def check_t1(name, got, y, A, ia, ib, tol, dtype, share=0.8):
     return want, seen
 
 
-# (id, n, dtype, E, C, freqs, plan keywords, decim, kernel of the form, visible share)
-CASES = [('1024-f32', 1024, 'float32', 5, 5, FREQS, {}, 1, 'nw_fused_pair_kernel', 0.8),
-         ('1024-f64', 1024, 'float64', 5, 5, FREQS, {}, 1, 'nw_fused_kernel', 0.8),
-         ('chirp-1201-f32', 1201, 'float32', 5, 5, FREQS, {}, 1, 'nw_chirp_kernel', 0.8),      # tail tile: 49 samples
-         ('chirp-1201-f64', 1201, 'float64', 5, 5, FREQS, {}, 1, 'nw_chirp_kernel', 0.8),
-         ('decim-4096', 4096, 'float32', 5, 5, FREQS, {}, 4, 'nw_fused_decim_kernel', 0.8),
-         ('e32-8192', 8192, 'float32', 5, 5, FREQS, {}, 1, 'nw_fused_kernel', 0.8),
-         ('rocfft-1000', 1000, 'float32', 5, 5, FREQS, {'engine': 'rocfft'}, 1, 'k1_multiply', 0.8),
-         ('twopass-32768', 32768, 'float32', 2, 3, FREQS3, {}, 1, 'cols_kernel', 0.8),
-         # more than 16 channels: three pair tiles, some of them partial
-         ('tiles-17ch-f64', 1024, 'float64', 3, 17, FREQS3, {}, 1, 'nw_fused_kernel', 0.6)]
+# (id, n, dtype, E, C, freqs, plan keywords, decim, kernel of the form, visible share): five epochs but for the rows
+# of SHAPES
+CASES = []
+for name, n, dtype, kw, decim, _, kernel in forms(*EPOCH_AXIS):
+    E, C, freqs = SHAPES.get(name, (5, 5, FREQS))
+    CASES.append((name, n, dtype, E, C, freqs, kw, decim, kernel, 0.6 if name == 'tiles-17ch-f64' else 0.8))
 
 
 @pytest.mark.parametrize('case', CASES, ids=[c[0] for c in CASES])
@@ -356,14 +309,6 @@ def test_edge_cases_and_errors(dtype):
         p.close()
 
 
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
-
-
 def test_class_layer():
     """Every finalised output is finalize_lag of the same call's own sums, exactly; one plan; decim;
     EpochsWavelet."""
@@ -438,12 +383,7 @@ def test_lag_under_bounds_checks():
     """The debug library (kernel bounds checks, nw_dcheck.h) on several pair tiles with partial
     ones (C = 17) and on a tail tile (n = 1201), with a short index list and through the pair path:
     no check fails."""
-    code = ('import sys; sys.path.insert(0, %r)\n'
-            'import numpy as np\n'
-            'import ninwavelets_amd as nw\n'
-            'from ninwavelets_amd import _lib as L\n'
-            'print("debug", L.lib().nw_debug_bounds())\n'
-            'rng = np.random.default_rng(1)\n'
+    body = ('rng = np.random.default_rng(1)\n'
             'for n, E, C, dt in ((1024, 3, 17, "float64"), (1201, 3, 5, "float32")):\n'
             '    x = rng.standard_normal((E, C, n)).astype(dt)\n'
             '    p = nw.Plan(n, 3, dt, max_batch=2 * C + 3)\n'
@@ -453,9 +393,6 @@ def test_lag_under_bounds_checks():
             '    pair = p.execute_pair(x[:, 0], x[:, C - 1], out_kind="lag_sum")\n'
             '    ok = all(bool(np.all(np.isfinite(a))) for a in (full, short, pair))\n'
             '    print("ok", n, ok and full.shape == (C * (C - 1) // 2, 3, n, 4) and short.shape == (3, 3, n, 4))\n'
-            '    p.close()\n') % ROOT
-    env = dict(os.environ, NINWAVE_LIB=os.path.join(ROOT, 'ninwavelets_amd', 'libninwave_debug.so'))
-    r = subprocess.run([sys.executable, '-u', '-c', code], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = r.stdout.splitlines()
-    assert 'debug 1' in lines and 'ok 1024 True' in lines and 'ok 1201 True' in lines, r.stdout
+            '    p.close()\n')
+    lines = run_under_bounds_checks(body)
+    assert 'ok 1024 True' in lines and 'ok 1201 True' in lines, lines

@@ -9,6 +9,7 @@ fp64 parity test), |.|^2 2e-12.
 import numpy as np
 import pytest
 
+from large_variants import tol_f32 as tol
 from oracle import nw_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -20,10 +21,6 @@ CLASSES = {'morse': nw.Morse, 'morlet': nw.Morlet, 'shannon': nw.Shannon, 'mexic
 
 def rel_err(got, ref):
     return np.max(np.abs(got - ref)) / max(np.max(np.abs(ref)), 1e-300)
-
-
-def tol(n):
-    return 1e-5 if n <= (1 << 16) else 3e-5
 
 
 def synth(S, n, seed, sfreq=1000.):

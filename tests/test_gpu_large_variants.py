@@ -11,7 +11,7 @@ the kernel cols_kernel and row_support(scan=True) == row_support().
 Signals are white noise drawn as float32 and handed to both dtypes.  References in complex128:
 oracle.nw_oracle.cwt for the stock kinds, cwt_from_rows on the exact rows handed to the plan for
 tables; |.| and |.|^2 are taken from them.  Tolerance, per (signal, row): max|got_row - ref_row|
-<= tol x max|ref_row| with tol = test_gpu_large.tol(n) for fp32 (1e-5 to 2^16, 3e-5 above) and
+<= tol x max|ref_row| with tol = large_variants.tol_f32(n) for fp32 (1e-5 to 2^16, 3e-5 above) and
 1e-12 for fp64, doubled for power.
 
 The row pass gives a workgroup kRowGroup = 4 rows when a launch holds >= 8 scales, else one:
@@ -23,7 +23,6 @@ import pytest
 
 import large_variants as V
 from oracle import nw_oracle as O
-from test_gpu_large import tol as tol_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +36,7 @@ MAXIMA = {}                                           # (dtype, out) -> largest 
 
 
 def tol(dtype, n, out='cwt'):
-    return (tol_f32(n) if dtype == 'float32' else 1e-12) * (2 if out == 'power' else 1)
+    return (V.tol_f32(n) if dtype == 'float32' else 1e-12) * (2 if out == 'power' else 1)
 
 
 def noise(S, n, seed):

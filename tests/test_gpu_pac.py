@@ -7,8 +7,8 @@ u = y_p[fp, s_j] / |y_p[fp, s_j]|:
     M = sum_j A u (E, P, Fp, Fa),  amp = {sum_j A, sum_j A^2} (E, C, Fa, 2),  phase = sum_j u (E, C, Fp).
 References are formed here from oracle.nw_oracle in complex128.
 
-Inputs: rng = default_rng(2600 + n); x[:, c] = 0.6 roll(common, 3 c) + 0.8 noise[:, c] (the lag tests' recipe);
-every even channel also gets 2 cos(phi) + 1.5 (1 + 0.9 cos(phi)) cos(2 pi 70 t + 1), phi = 2 pi 7 t + a uniform
+Inputs: the coupled recipe of epoch_cases.py: rng = default_rng(2600 + n); x[:, c] = 0.6 roll(common, 3 c) +
+0.8 noise[:, c] (the lagged recipe on another seed); every even channel also gets 2 cos(phi) + 1.5 (1 + 0.9 cos(phi)) cos(2 pi 70 t + 1), phi = 2 pi 7 t + a uniform
 random phase per epoch: a 70 Hz amplitude that follows the 7 Hz phase.  sfreq 1000, Morse(1000) with its default
 b, r, FREQS (nine scales), phase = [0, 1, 2, 3], amp = [4 .. 8], E = 3, C = 5, max_batch = 2 C + 3 (chunks of 2 and
 1 epochs) unless stated.  PAIRS: every channel with itself and three cross-channel pairs.
@@ -29,15 +29,12 @@ rows; u_j = min(2, 2 tol A_p / |y_p|) (a unit phasor moves by at most 2 |dy| / |
   T4  measures: fp64 every kind within 1e-7 of the formula on the oracle's sums; fp32 |d direct_pac| <=
       (bM + 2 tol T A_a) / (sqrt(T sum A^2) - 2 tol T A_a) on every cell, bM the T1 bound.
   T5  the layers; T6 the debug library."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from oracle import nw_oracle as O
+from epoch_cases import (FREQS, OVER_TIME, FakeEpochs, forms, lane_sum, morse_plan, run_under_bounds_checks, tol_of,
+                         windows_of)
+from epoch_cases import coupled_rows as oracle_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -45,11 +42,9 @@ import ninwavelets_amd as nw  # noqa: E402
 from ninwavelets_amd import _lib as L  # noqa: E402
 from ninwavelets_amd.engine import finalize_pac, time_window  # noqa: E402
 
-FREQS = [4., 7., 12., 20., 40., 70., 120., 200., 300.]
 PHASE, AMP = [0, 1, 2, 3], [4, 5, 6, 7, 8]
-FREQS3 = [7., 70., 200.]
+FREQS3 = [7., 70., 200.]             # this file's three: the coupled pair of scales is among them
 FREQS26 = [float(f) for f in np.round(np.geomspace(4., 300., 26), 2)]
-CHIRP = (1201,)
 KINDS = ('mvl', 'mvl_norm', 'direct_pac', 'debiased_pac')
 # (phase channel, amplitude channel): every channel with itself, then three cross-channel pairs
 PAIRS = (np.array([0, 1, 2, 3, 4, 0, 1, 2]), np.array([0, 1, 2, 3, 4, 2, 0, 3]))
@@ -60,58 +55,10 @@ PAIRS = (np.array([0, 1, 2, 3, 4, 0, 1, 2]), np.array([0, 1, 2, 3, 4, 2, 0, 3]))
 UNCOUPLED = 3
 
 
-def tol_of(n, dtype):
-    if dtype == 'float64':
-        return 1e-12
-    return 2e-5 if n in CHIRP else 1e-5
-
-
-_ROWS = {}
-
-
-def oracle_rows(n, E, C, dtype, freqs):
-    """(x, y): the inputs (E, C, n) in the compute dtype and their complex128 CWT rows (E, C, F, n), computed
-    once per case and shared (read-only)."""
-    key = (n, E, C, dtype, tuple(freqs))
-    if key not in _ROWS:
-        rng = np.random.default_rng(2600 + n)
-        common = rng.standard_normal((E, 1, n))
-        noise = rng.standard_normal((E, C, n))
-        x = np.stack([0.6 * np.roll(common[:, 0], 3 * c, axis=-1) + 0.8 * noise[:, c] for c in range(C)], axis=1)
-        t = np.arange(n) / 1000.
-        phi = 2 * np.pi * 7 * t + rng.uniform(0., 2 * np.pi, E)[:, None]                  # (E, n)
-        x[:, 0::2] += (2 * np.cos(phi) + 1.5 * (1 + 0.9 * np.cos(phi)) * np.cos(2 * np.pi * 70 * t + 1))[:, None]
-        x = x.astype(dtype)
-        rows = O.fft_wavelets('morse', freqs, 1000., n / 1000., False)
-        y = np.stack([np.stack([O.cwt_from_rows(s.astype(np.float64), rows, False) for s in ep]) for ep in x])
-        x.setflags(write=False)
-        y.setflags(write=False)
-        _ROWS[key] = (x, y)
-    return _ROWS[key]
-
-
-def morse_plan(n, dtype, freqs, max_batch, **kw):
-    p = nw.Plan(n, len(freqs), dtype, max_batch=max_batch, **kw)
-    p.set_wavelet('morse', [17.5, 3.], np.asarray(freqs), L.trans_grid(n / 1000., 1000., False))
-    return p
-
-
 def pairs_of(C):
     ip, ia = PAIRS
     keep = (ip < C) & (ia < C)
     return ip[keep], ia[keep]
-
-
-def windows_of(n, n_out, host_decim):
-    """(name, (t0, t1), step) in the plan's output samples."""
-    if host_decim > 1:                       # a full-rate plan summing every host_decim-th sample
-        out = []
-        for name, w in (('full', None), ('one', (0, 1)), ('inner', (37, min(1001, n))), ('empty', (500, 500))):
-            t0, t1, step, _ = time_window(n, host_decim, w, False)
-            out.append((name, (t0, t1), step))
-        return out
-    return [('full', (0, n_out), 1), ('one', (0, 1), 1), ('inner', (37, 1001), 1), ('empty', (500, 500), 1),
-            ('stride', (5, n_out - 3), 4)]
 
 
 def ref_sums(y, ip, ia, fph, fam, idx):
@@ -176,25 +123,6 @@ def check_t1(name, got, y, Ac, ip, ia, fph, fam, idx, tol):
     return rM, ramp, rphase, bM
 
 
-def lane_sum(terms):
-    """The contract's sum of ``terms`` (..., T) along the last axis: 64 lane sums, lane l adding j = l,
-    l + 64, ... in order from +0.0, then v = v[:h] + v[h:] for h = 32 .. 1.  (A lane or tail sample
-    without a j < T adds nothing: padding with +0.0 is the same, an accumulator never being -0.0.)"""
-    T = terms.shape[-1]
-    ntl = -(-T // 64)
-    pad = np.zeros(terms.shape[:-1] + (ntl * 64,))
-    pad[..., :T] = terms
-    pad = pad.reshape(terms.shape[:-1] + (ntl, 64))
-    v = np.zeros(terms.shape[:-1] + (64,))
-    for it in range(ntl):
-        v = v + pad[..., it, :]
-    h = 32
-    while h >= 1:
-        v = v[..., :h] + v[..., h:]
-        h //= 2
-    return v[..., 0]
-
-
 def own_sums(rows, ip, ia, fph, fam, idx):
     """(M, amp, phase) of the plan's own complex128 rows (E, C, F, n_out) in the contract's order."""
     yw = rows[..., idx]
@@ -211,17 +139,15 @@ def own_sums(rows, ip, ia, fph, fam, idx):
     return M, amp, phase
 
 
-# (id, n, dtype, E, C, freqs, phase, amp, plan keywords, device decim, host decim, kernel of the form)
-CASES = [('1024-f32', 1024, 'float32', 3, 5, FREQS, PHASE, AMP, {}, 1, 1, 'nw_fused_pair_kernel'),
-         ('1024-f64', 1024, 'float64', 3, 5, FREQS, PHASE, AMP, {}, 1, 1, 'nw_fused_kernel'),
-         ('chirp-1201-f32', 1201, 'float32', 3, 5, FREQS, PHASE, AMP, {}, 1, 1, 'nw_chirp_kernel'),   # tail tile: 49
-         ('chirp-1201-f64', 1201, 'float64', 3, 5, FREQS, PHASE, AMP, {}, 1, 1, 'nw_chirp_kernel'),
-         ('decim-4096', 4096, 'float32', 3, 5, FREQS, PHASE, AMP, {}, 4, 1, 'nw_fused_decim_kernel'),
-         ('rocfft-1000-step4', 1000, 'float32', 3, 5, FREQS, PHASE, AMP, {'engine': 'rocfft'}, 1, 4, 'k1_multiply'),
-         ('twopass-32768', 32768, 'float32', 2, 3, FREQS3, [0], [1, 2], {}, 1, 1, 'cols_kernel'),
-         # 9 phase x 17 amplitude scales: two phase tiles and two amplitude tiles, one of each partial
-         ('tiles-9x17-f64', 1024, 'float64', 2, 2, FREQS26, list(range(9)), list(range(9, 26)), {}, 1, 1,
-          'nw_fused_kernel')]
+# (id, n, dtype, E, C, freqs, phase, amp, plan keywords, device decim, host decim, kernel of the form): three epochs
+# of five channels, PHASE and AMP of the nine scales, but for the two-pass row; the tile row is this file's own
+CASES = []
+for name, n, dtype, kw, decim, host_decim, kernel in forms(*OVER_TIME[:-1]):
+    E, C, freqs, fph, fam = (2, 3, FREQS3, [0], [1, 2]) if name == 'twopass-32768' else (3, 5, FREQS, PHASE, AMP)
+    CASES.append((name, n, dtype, E, C, freqs, fph, fam, kw, decim, host_decim, kernel))
+# 9 phase x 17 amplitude scales: two phase tiles and two amplitude tiles, one of each partial
+CASES.append(('tiles-9x17-f64', 1024, 'float64', 2, 2, FREQS26, list(range(9)), list(range(9, 26)), {}, 1, 1,
+              'nw_fused_kernel'))
 
 
 @pytest.mark.parametrize('case', CASES, ids=[c[0] for c in CASES])
@@ -457,14 +383,6 @@ def test_measures(case):
     assert np.all(d <= bound), np.max(d / bound)
 
 
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
-
-
 def test_class_layer():
     """T5: pac_batch is finalize_pac of Plan.execute_pac, with device decim and with host decim; average;
     cross-channel indices; EpochsWavelet.pac's concatenated scale list and padding."""
@@ -533,12 +451,7 @@ def test_class_layer():
 def test_pac_under_bounds_checks():
     """T6: the debug library (kernel bounds checks, nw_dcheck.h) on n = 1024, on a tail tile (n = 1201) and on
     partial scale tiles (9 x 17 scales), five windows, own and cross-channel pairs: no check fails."""
-    code = ('import sys; sys.path.insert(0, %r)\n'
-            'import numpy as np\n'
-            'import ninwavelets_amd as nw\n'
-            'from ninwavelets_amd import _lib as L\n'
-            'print("debug", L.lib().nw_debug_bounds())\n'
-            'rng = np.random.default_rng(1)\n'
+    body = ('rng = np.random.default_rng(1)\n'
             'for tag, n, E, C, dt, F, ph, am in (("a", 1024, 3, 5, "float32", 9, [0, 1, 2, 3], [4, 5, 6, 7, 8]),\n'
             '                                    ("b", 1201, 3, 5, "float64", 3, [0], [1, 2]),\n'
             '                                    ("c", 1024, 2, 2, "float64", 26, list(range(9)), list(range(9, 26)))):\n'
@@ -552,9 +465,6 @@ def test_pac_under_bounds_checks():
             '        for a in own + short:\n'
             '            ok = ok and bool(np.all(np.isfinite(a))) and a.shape[0] == E\n'
             '    print("ok", tag, ok)\n'
-            '    p.close()\n') % ROOT
-    env = dict(os.environ, NINWAVE_LIB=os.path.join(ROOT, 'ninwavelets_amd', 'libninwave_debug.so'))
-    r = subprocess.run([sys.executable, '-u', '-c', code], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = r.stdout.splitlines()
-    assert 'debug 1' in lines and 'ok a True' in lines and 'ok b True' in lines and 'ok c True' in lines, r.stdout
+            '    p.close()\n')
+    lines = run_under_bounds_checks(body)
+    assert 'ok a True' in lines and 'ok b True' in lines and 'ok c True' in lines, lines

@@ -7,7 +7,7 @@ For epochs e, channel rows y_a,e and y_b,e (F, n_out):
     S_ab = sum_e y_a conj(y_b),  P_aa = sum_e |y_a|^2,  Phi_ab = sum_e (y_a/|y_a|) conj(y_b/|y_b|)
 every sum in fp64 in epoch order.  References are formed here from oracle.nw_oracle in complex128.
 
-Inputs: rng = default_rng(2100 + n), a = rng.standard_normal((E, n)), b = 0.6 a + 0.8 rng.standard_normal((E, n)),
+Inputs: pair_rows of epoch_cases.py: rng = default_rng(2100 + n), a = rng.standard_normal((E, n)), b = 0.6 a + 0.8 rng.standard_normal((E, n)),
 Morse(1000) with its default b, r, nine scales (one more than a tile), E = 6 epochs (12 signals: two
 blocks of 8, the second holding 2 pairs).
 
@@ -23,7 +23,8 @@ Measured maxima (MI355X), as fractions of the bounds: see DESIGN.md section 5.""
 import numpy as np
 import pytest
 
-from oracle import nw_oracle as O
+from epoch_cases import FREQS, FREQS3, FakeEpochs, forms, morse_plan, tol_of
+from epoch_cases import pair_rows as oracle_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -31,46 +32,10 @@ import ninwavelets_amd as nw  # noqa: E402
 from ninwavelets_amd import _lib as L  # noqa: E402
 from ninwavelets_amd.engine import finalize_pair  # noqa: E402
 
-FREQS = [4., 7., 12., 20., 40., 70., 120., 200., 300.]
-FREQS3 = [3., 30., 200.]
 E6 = 6
 V = 0.01
-CHIRP = (1201,)                     # lengths the tests run on the chirp-z form
 DTYPES = ['float32', 'float64']
 OUTS = ['cross_sum', 'plv_sum', 'csd', 'coherency', 'coherence', 'imcoh', 'plv']
-
-
-def tol_of(n, dtype):
-    if dtype == 'float64':
-        return 1e-12
-    return 2e-5 if n in CHIRP else 1e-5
-
-
-def signals(n, E, dtype):
-    rng = np.random.default_rng(2100 + n)
-    a = rng.standard_normal((E, n))
-    b = 0.6 * a + 0.8 * rng.standard_normal((E, n))
-    return a.astype(dtype), b.astype(dtype)
-
-
-_ROWS = {}
-
-
-def oracle_rows(n, E, dtype, freqs, zero_b=None):
-    """(a, b, ya, yb): the inputs in the compute dtype and their complex128 CWT rows (E, F, n),
-    computed once per case and shared (read-only)."""
-    key = (n, E, dtype, tuple(freqs), zero_b)
-    if key not in _ROWS:
-        a, b = signals(n, E, dtype)
-        if zero_b is not None:
-            b[zero_b] = 0
-        rows = O.fft_wavelets('morse', freqs, 1000., n / 1000., False)
-        ya = np.stack([O.cwt_from_rows(x.astype(np.float64), rows, False) for x in a])
-        yb = np.stack([O.cwt_from_rows(x.astype(np.float64), rows, False) for x in b])
-        for arr in (a, b, ya, yb):
-            arr.setflags(write=False)
-        _ROWS[key] = (a, b, ya, yb)
-    return _ROWS[key]
 
 
 def sums_of(ya, yb):
@@ -88,21 +53,14 @@ def sums_of(ya, yb):
     return np.stack([s.real, s.imag, paa, pbb], axis=-1), phi
 
 
-def morse_plan(n, dtype, freqs, max_batch, **kw):
-    p = nw.Plan(n, len(freqs), dtype, max_batch=max_batch, **kw)
-    p.set_wavelet('morse', [17.5, 3.], np.asarray(freqs), L.trans_grid(n / 1000., 1000., False))
-    return p
-
-
-# (id, n, dtype, E, freqs, plan keywords, decim, kernel of the form)
+# (id, n, dtype, E, freqs, plan keywords, decim, kernel of the form): every size the fused pair partials may cover,
+# in both dtypes, then the other forms; six epochs of the nine scales but for the two-pass row
 CASES = [(f'pair-{n}', n, 'float32', E6, FREQS, {}, 1, 'nw_fused_pair_kernel') for n in (1024, 2048, 4096)]
 CASES += [(f'f64-{n}', n, 'float64', E6, FREQS, {}, 1, 'nw_fused_kernel') for n in (1024, 2048, 4096)]
-CASES += [('e32-8192', 8192, 'float32', E6, FREQS, {}, 1, 'nw_fused_kernel'),
-          ('chirp-1201-f32', 1201, 'float32', E6, FREQS, {}, 1, 'nw_chirp_kernel'),
-          ('chirp-1201-f64', 1201, 'float64', E6, FREQS, {}, 1, 'nw_chirp_kernel'),
-          ('rocfft-1000', 1000, 'float32', E6, FREQS, {'engine': 'rocfft'}, 1, 'k1_multiply'),
-          ('twopass-32768', 32768, 'float32', 3, FREQS3, {}, 1, 'cols_kernel'),
-          ('decim-4096', 4096, 'float32', E6, FREQS, {}, 4, 'nw_fused_decim_kernel')]
+for name, n, dtype, kw, decim, _, kernel in forms('e32-8192', 'chirp-1201-f32', 'chirp-1201-f64', 'rocfft-1000',
+                                                  'twopass-32768', 'decim-4096'):
+    E, freqs = (3, FREQS3) if name == 'twopass-32768' else (E6, FREQS)
+    CASES.append((name, n, dtype, E, freqs, kw, decim, kernel))
 
 
 def cross_err(got, ya, yb):
@@ -282,14 +240,6 @@ def test_device_tensors_equal_the_host_call_bit_for_bit(dtype):
     finally:
         p.close()
     assert np.array_equal(dev[0], host[0]) and np.array_equal(dev[1], host[1])
-
-
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
 
 
 @pytest.mark.parametrize('dtype', DTYPES)

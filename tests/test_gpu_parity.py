@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_names, load_golden
+from epoch_cases import FakeEpochs
 from oracle import nw_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -98,14 +99,6 @@ def test_reuse_cache_is_unkeyed(engine):
     w = nw.Morse(1000, interpolate=True, engine=engine)
     assert rel_err(w.cwt(g['xa'], g['freqs']), g['oa']) <= 1e-12
     assert rel_err(w.cwt(g['xb'], [1., 2.]), g['ob']) <= 1e-12
-
-
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
 
 
 @pytest.mark.parametrize('dtype', ['float64', 'float32'])

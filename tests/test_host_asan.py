@@ -40,10 +40,9 @@ def test_host_logic_under_asan(host_asan):
 
 def test_python_restatement_matches_the_shape_header(host_asan):
     """tests/fused_variants.py (the rules the GPU tests use to steer rows into every pass-0
-    variant) and tests/test_decim_cpu.py's rule, line by line against what nw_shape.h -- the
+    variant, and decim_rule), line by line against what nw_shape.h -- the
     header the kernels and launchers compile -- gives for every row of the size table."""
     import fused_variants as V
-    from test_decim_cpu import rule
     r = subprocess.run([host_asan, 'shapes'], capture_output=True, text=True, env=ENV, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     got = r.stdout.splitlines()
@@ -69,7 +68,7 @@ def test_python_restatement_matches_the_shape_header(host_asan):
             want += [None, None]                              # the two partial-sum lines (no Python restatement)
     for dtype in ('float32', 'float64'):
         for n in sizes + [1000, 3000, 4097, 6144, 12288, 16383, 16385]:
-            want += [f'decim {dtype} {n} {d}' for d in range(-2, 33) if d > 0 and rule(n, d)]
+            want += [f'decim {dtype} {n} {d}' for d in range(-2, 33) if d > 0 and V.decim_rule(n, d)]
     assert len(got) == len(want), (len(got), len(want))
     for g, w in zip(got, want):
         if w is not None:

@@ -5,6 +5,8 @@ device work) and the host-only predicate nw_pair_partials_supported (0 for NW_OU
 import numpy as np
 import pytest
 
+from epoch_cases import FakeEpochs
+
 import ninwavelets_amd as nw
 from ninwavelets_amd import _lib as L
 from ninwavelets_amd.engine import LAG_KINDS, LAG_OUTS, finalize_lag
@@ -118,14 +120,6 @@ def test_finalize_lag_rejects_bad_arguments():
             finalize_lag(kind, sums, 5)
     with pytest.raises(ValueError, match=r'\(\.\.\., 4\)'):
         finalize_lag('wpli', np.zeros((3, 8, 2)), 5)
-
-
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
 
 
 def test_bad_arguments_are_value_errors_before_any_device_work():

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from epoch_cases import FakeEpochs
 
 import ninwavelets_amd as nw
 from ninwavelets_amd import _lib as L
@@ -114,14 +115,6 @@ def test_index_and_scale_checks():
     for bad in ([], None, [9], [-1, 2], [0.5], [[0, 1]], 3, 'ab'):
         with pytest.raises(ValueError, match='phase'):
             check_scales('phase', bad, 9)
-
-
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
 
 
 def test_bad_arguments_are_value_errors_before_any_device_work():

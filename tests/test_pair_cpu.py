@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from epoch_cases import FakeEpochs
 
 import ninwavelets_amd as nw
 from ninwavelets_amd import _lib as L
@@ -63,14 +64,6 @@ def test_coherence_of_a_channel_with_itself_is_one():
     assert np.array_equal(finalize_pair('coherence', cross, 6), np.ones_like(p))
     assert np.array_equal(finalize_pair('imcoh', cross, 6), np.zeros_like(p))
     assert np.array_equal(finalize_pair('csd', cross, 6), p / 6 + 0j)
-
-
-class FakeEpochs:
-    def __init__(self, data, sfreq, ch_names):
-        self._d, self.info, self.ch_names = data, {'sfreq': sfreq}, list(ch_names)
-
-    def get_data(self):
-        return self._d
 
 
 def test_bad_arguments_are_value_errors_before_any_device_work():
