@@ -164,6 +164,9 @@ typedef struct nw_stats {
                                   nw_pac_kernel                                                 */
 #define NW_REDUCE_ENV      6   /* nw_execute_env_time: per-signal rows per chunk, every (epoch,
                                   pair, scale) summed over the window by nw_env_time_kernel    */
+#define NW_REDUCE_PAC_BINS 7   /* nw_execute_pac_bins: per-signal rows per chunk, every (epoch, pair,
+                                  phase scale, amplitude scale, phase bin) summed over the window
+                                  by nw_pac_bins_kernel                                         */
 
 /* nw_stats.kernel: which kernel wrote the output rows (the dominant kernel of a step) */
 #define NW_K_NONE        0
@@ -365,6 +368,45 @@ int nw_execute_pac(nw_plan* plan, const void* x, int64_t nepochs, int32_t nchan,
                    const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam,
                    int64_t t0, int64_t t1, int64_t step,
                    void* out_m, void* out_amp, void* out_phase, int mem);
+
+/* Phase-binned phase-amplitude coupling: per epoch, channel pair and (phase scale, amplitude scale)
+ * the amplitude summed within each of nbins phase bins, reduced on the device along the samples of a
+ * window: what Tort's modulation index (Tort et al. 2010), the height ratio, the preferred phase and
+ * the phase-amplitude histogram are formed from.  x, ip / ia, fph / fam, nchan, chunking, mem, every
+ * engine form, decimated plans, the window (t0, t1, step), T, the empty cases and NW_E_NOMEM are
+ * nw_execute_pac's.  nbins must be even with 2 <= nbins <= NW_PAC_MAX_BINS (NW_E_INVALID otherwise).
+ * Outputs are epoch-major:
+ *   out_sum   float64 (nepochs, npairs, nph, nam, nbins) = sum_{j : bin_j = b} A_j
+ *   out_count float64 (nepochs, nchan, nph, nbins)       = #{j : bin_j = b}          (may be NULL)
+ * with A = hypot(re, im) of row fam[k] of channel ia[p] (nw_execute_pac's A) and bin_j the bin of row
+ * fph[i] of channel ip[p] (out_count: of channel c) at sample s_j.  The counts are exact integers and
+ * each row of them sums to T.
+ * THE BIN (part of the contract; no atan2).  With (re, im) the row value converted to double,
+ * h = nbins / 2 and (c_b, s_b) the table of nw_pac_bin_edges(nbins) -- the device reads these very
+ * doubles, uploaded, and evaluates no cos or sin of its own:
+ *   upper = im > 0 || (im == 0 && re > 0),  base = upper ? h : 0,
+ *   bin   = base + #{k = 1 .. h - 1 : c_{base+k} im - s_{base+k} re >= 0},
+ * each product rounded on its own and then subtracted (no fma), and bin = h where re == 0 && im == 0
+ * (stated on its own: the count alone would put that point in bin h - 1).  Bin b holds the phases
+ * [theta_b, theta_{b+1}), theta_b = -pi + 2 pi b / nbins, as floor((atan2(im, re) + pi) / (2 pi / nbins))
+ * does away from the edges.  So: re < 0, im = +-0 is bin 0; y = 0 is bin h, as atan2(0, 0) = 0; a NaN
+ * row value (both parts NaN, or im NaN) falls to bin 0, every comparison being false (re NaN with
+ * im > 0: bin h).
+ * Every sum runs in nw_execute_conn_time's SUMMATION ORDER per bin: lane l visits j = l, l + 64, ... in
+ * order and adds A_j to its partial sum of bin bin_j (64 x nbins partial sums, each starting at +0.0),
+ * and each bin's 64 lane values are folded with xor 32 .. 1.  A >= +0 and a partial sum is never -0.0,
+ * so this is the SUMMATION ORDER applied to the terms (bin_j == b ? A_j : 0.0).  A result depends only
+ * on its two rows, nbins and (t0, t1, step): not on the pair list, the scale lists, their tiling or the
+ * chunks.  nw_stats.reduce_path: NW_REDUCE_PAC_BINS. */
+#define NW_PAC_MAX_BINS 36
+/* host-only (no GPU): cs[nbins][2] = {cos theta_b, sin theta_b}, theta_b = -pi + 2 pi b / nbins; nbins
+ * as above (NW_E_INVALID otherwise, the message names the value) */
+int nw_pac_bin_edges(int32_t nbins, double* cs);
+int nw_execute_pac_bins(nw_plan* plan, const void* x, int64_t nepochs, int32_t nchan,
+                        const int32_t* ip, const int32_t* ia, int64_t npairs,
+                        const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam,
+                        int64_t t0, int64_t t1, int64_t step, int32_t nbins,
+                        void* out_sum, void* out_count, int mem);
 
 /* Envelope correlation (Hipp et al. 2012; mne-connectivity's envelope_correlation): per epoch, channel
  * pair and scale the sums from which the Pearson correlation over time of two amplitude envelopes is

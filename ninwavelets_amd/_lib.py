@@ -45,6 +45,8 @@ NW_REDUCE_CONN = 3                                              # ... of nw_exec
 NW_REDUCE_CONN_TIME = 4                                         # ... of nw_execute_conn_time
 NW_REDUCE_PAC = 5                                               # ... of nw_execute_pac
 NW_REDUCE_ENV = 6                                               # ... of nw_execute_env_time
+NW_REDUCE_PAC_BINS = 7                                          # ... of nw_execute_pac_bins
+NW_PAC_MAX_BINS = 36                                            # nw_execute_pac_bins: nbins even, 2 .. 36
 NW_ENV_PLAIN, NW_ENV_ORTH = 0, 1                                # nw_execute_env_time's env_kind
 NW_MEM_HOST, NW_MEM_DEVICE = 0, 1
 # nw_stats.kernel -> the kernel name rocprofv3 shows
@@ -107,6 +109,9 @@ SIGNATURES = [
                                            ctypes.c_int, ctypes.c_int]),
     ('nw_execute_pac', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _P, ctypes.c_int32, _P, ctypes.c_int32,
                                       _I64, _I64, _I64, _P, _P, _P, ctypes.c_int]),
+    ('nw_pac_bin_edges', ctypes.c_int, [ctypes.c_int32, _P]),
+    ('nw_execute_pac_bins', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _P, ctypes.c_int32, _P,
+                                           ctypes.c_int32, _I64, _I64, _I64, ctypes.c_int32, _P, _P, ctypes.c_int]),
     ('nw_execute_multi',ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _I64, _P, ctypes.c_int]),
     ('nw_execute_multi_scales', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _I64, _P, ctypes.c_int]),
     ('nw_execute_multi_device', ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(_P),
@@ -231,3 +236,29 @@ def conn_time_count(n_out: int, t0: int, t1: int, step: int = 1) -> int:
     count = ctypes.c_int64()
     check(lib().nw_conn_time_count(int(n_out), int(t0), int(t1), int(step), ctypes.byref(count)))
     return int(count.value)
+
+
+def check_nbins(nbins) -> int:
+    """``nbins`` of the phase-binned calls as an int: even, 2 <= nbins <= NW_PAC_MAX_BINS; ValueError for
+    anything else, before any device work."""
+    import operator
+    try:
+        if isinstance(nbins, bool):
+            raise TypeError
+        nb = operator.index(nbins)
+    except TypeError:
+        nb = None
+    if nb is None or nb < 2 or nb > NW_PAC_MAX_BINS or nb % 2:
+        raise ValueError(f'nbins must be an even integer with 2 <= nbins <= {NW_PAC_MAX_BINS}, got {nbins!r}')
+    return nb
+
+
+def pac_bin_edges(nbins: int):
+    """The edge table of nw_execute_pac_bins (nw_pac_bin_edges; host-only): float64 (nbins, 2) =
+    {cos theta_b, sin theta_b}, theta_b = -pi + 2 pi b / nbins: the doubles the device tests a sample against.
+    ValueError unless nbins is an even integer with 2 <= nbins <= NW_PAC_MAX_BINS (check_nbins)."""
+    import numpy as np
+    nb = check_nbins(nbins)
+    cs = np.empty((nb, 2), dtype=np.float64)
+    check(lib().nw_pac_bin_edges(nb, cs.ctypes.data_as(_P)))
+    return cs

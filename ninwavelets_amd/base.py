@@ -26,10 +26,10 @@ import numpy as np
 from scipy.fftpack import fft, ifft
 
 from . import _lib as L
-from .engine import (CONN_OUTS, ENV_OUTS, LAG_OUTS, PAC_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim, check_indices,
-                     check_pac_indices, check_scales, execute_multi, finalize_conn, finalize_conn_time, finalize_env,
-                     finalize_lag,
-                     finalize_pac, finalize_pair, np_dtype, time_window)
+from .engine import (CONN_OUTS, ENV_OUTS, LAG_OUTS, PAC_BIN_OUTS, PAC_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim,
+                     check_indices, check_nbins, check_pac_indices, check_scales, execute_multi, finalize_conn,
+                     finalize_conn_time, finalize_env, finalize_lag, finalize_pac, finalize_pac_bins, finalize_pair,
+                     np_dtype, time_window)
 from .engine import make_wavelets as _make_wavelets_dev
 
 # Device working-set budget per plan chunk (bytes); signals are streamed through it.
@@ -655,6 +655,27 @@ class WaveletBase:
                                window, decim, average, 0 if out == 'pac_sum' else 1,
                                lambda plan, *a: plan.execute_pac(*a),
                                lambda sums, *a: finalize_pac(out, *sums, *a), scales=(phase, amp))
+
+    def pac_bins_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, phase=None, amp=None, out: str = 'mi',
+                       nbins: int = 18, indices=None, window=None, decim: int = 1, average: bool = False):
+        """Phase-binned phase-amplitude coupling of ``waves`` (E, C, N): the amplitude of the scales ``amp``
+        averaged within ``nbins`` bins of the phase of the scales ``phase``, and what is formed from that
+        distribution (engine.finalize_pac_bins): ``mi`` (Tort's Kullback-Leibler modulation index, tensorpac's
+        idpac=(2, ...)), ``hr`` (the height ratio) and ``pref_phase`` (the centre of the bin with the largest
+        mean amplitude), each (E, P, Fp, Fa) float64, and ``bin_amp``, the phase-amplitude histogram
+        (E, P, Fp, Fa, nbins); ``bin_sum`` returns the sums (S (E, P, Fp, Fa, nbins), count (E, C, Fp, nbins)).
+        ``nbins`` even, 2 .. 36.  Every signal is transformed once and reduced on the device; the (E, C, F, N)
+        rows never leave it.  ``phase``, ``amp``, ``indices``, ``window``, ``decim`` and ``average`` (the mean over
+        the epochs; ValueError for ``bin_sum`` and for ``pref_phase``, an angle) as in pac_batch; an empty
+        window is a ValueError for the finalised kinds.  Cache semantics, device choice and plan eviction
+        as in connectivity_batch."""
+        nbins = check_nbins(nbins)
+        if average and out == 'pref_phase':
+            raise ValueError("average=True takes a measure that can be averaged over the epochs, not the angle 'pref_phase'")
+        return self._time_sums(waves, freqs, reuse, out, dict.fromkeys(sorted(PAC_BIN_OUTS)), check_pac_indices, indices,
+                               window, decim, average, 0 if out == 'bin_sum' else 1,
+                               lambda plan, *a: plan.execute_pac_bins(*a, nbins=nbins),
+                               lambda sums, ip, ia, count: finalize_pac_bins(out, *sums, ip), scales=(phase, amp))
 
     def plan_stats(self) -> list:
         """Per-plan device stage timings (nw_plan_stats)."""

@@ -1180,6 +1180,92 @@ int execute_pac(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, 
     });
 }
 
+// the table of nw_pac_bin_edges: cs[b] = {cos theta_b, sin theta_b}, theta_b = -pi + 2 pi b / nbins
+void pac_bin_edges(int nbins, double* cs) {
+    const double pi = 3.14159265358979323846;
+    for (int b = 0; b < nbins; ++b) {
+        const double theta = -pi + 2.0 * pi * b / nbins;
+        cs[2 * b] = std::cos(theta);
+        cs[2 * b + 1] = std::sin(theta);
+    }
+}
+
+// Phase-binned phase-amplitude coupling (nw_execute_pac_bins): as execute_pac with nw_pac_bins_kernel's
+// (E, P, nph, nam, nbins) sums and nw_pac_bins_rows_kernel's (E, C, nph, nbins) counts.  The blob is the
+// pair and scale lists, padded to 16 bytes, and then the edge table the kernels read.
+int execute_pac_bins(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ip,
+                     const int32_t* ia, int64_t npairs, const int32_t* fph, int nph, const int32_t* fam, int nam,
+                     int64_t t0, int64_t t1, int64_t step, int nbins, void* out_sum, void* out_count, bool host) {
+    const int64_t count = nw::conn_time_count(t0, t1, step);
+    const size_t sum_epoch = (size_t)npairs * nph * nam * nbins * sizeof(double);   // of one epoch
+    const size_t count_epoch = (size_t)nchan * nph * nbins * sizeof(double);
+    SumRegion r[2] = {{out_sum, (size_t)nepochs * sum_epoch, sum_epoch},
+                      {out_count, out_count ? (size_t)nepochs * count_epoch : 0, count_epoch}};
+    std::vector<int32_t>& lists = p->pac_lists;                   // ip, ia, fph, fam, padding, the edge table
+    lists.clear();
+    lists.insert(lists.end(), ip, ip + npairs);
+    lists.insert(lists.end(), ia, ia + npairs);
+    lists.insert(lists.end(), fph, fph + nph);
+    lists.insert(lists.end(), fam, fam + nam);
+    lists.resize((lists.size() + 3) / 4 * 4, 0);
+    const size_t edges_at = lists.size();
+    double cs[2 * NW_PAC_MAX_BINS];
+    pac_bin_edges(nbins, cs);
+    lists.resize(edges_at + (size_t)nbins * 4);
+    std::memcpy(lists.data() + edges_at, cs, (size_t)nbins * 2 * sizeof(double));
+    const char* d_lists = nullptr;
+    NW_TRY(place_sums(p, r, 2, lists.data(), lists.size() * sizeof(int32_t), &d_lists, false,
+                      "nw_execute_pac_bins: the fp64 sums of " + std::to_string(nepochs) + " epochs, " +
+                          std::to_string(npairs) + " pairs and " + std::to_string(nph) + " x " + std::to_string(nam) +
+                          " scales x " + std::to_string(nbins) + " bins"));
+    const int32_t* const d_ip = (const int32_t*)d_lists;
+    const int32_t* const d_ia = d_ip + npairs;
+    const int32_t* const d_fph = d_ia + npairs;
+    const int32_t* const d_fam = d_fph + nph;
+    const void* const d_edges = (const int32_t*)d_lists + edges_at;
+    const bool xcd = xcd_order();
+    nw_logf(1, "plan %p: pac bin sums, %lld epochs x %d channels, %lld pairs, %d phase x %d amplitude scales x %d bins "
+               "in %lld tiles of %d amplitude scales, %lld B of LDS per block (%lld epochs per chunk), window [%lld, "
+               "%lld) step %lld of %lld samples, %s buffers: per-signal rows per chunk, every (epoch, pair, phase "
+               "scale, amplitude scale, bin) summed over its samples of the window's %lld in fp64 in lane order",
+            (void*)p, (long long)nepochs, nchan, (long long)npairs, nph, nam, nbins,
+            (long long)nw::pac_bins_tiles(nph, nam, nbins), nw::pac_bins_am(nbins), (long long)nw::pac_bins_lds(nbins),
+            (long long)(p->max_batch / nchan), (long long)t0, (long long)t1, (long long)step, (long long)p->n_out(),
+            host ? "host" : "device", (long long)count);
+    p->stats.reduce_path = NW_REDUCE_PAC_BINS;
+    return run_epoch_chunks(p, d, x, nepochs, nchan, r, 2, host, [&](int64_t e0, int64_t ec, void* rows) -> int {
+        if (!(r[0].bytes + r[1].bytes)) return NW_OK;
+        return NW_KERNEL_STAGE(p, ST_EPI, true,
+                               nw::launch_pac_bins(p->dtype, rows, r[0].at(e0), r[1].at(e0), d_ip, d_ia, d_fph, d_fam,
+                                                   d_edges, ec, nchan, p->nfreq, p->n_out(), npairs, nph, nam, nbins, t0,
+                                                   count, step, xcd, p->stream));
+    });
+}
+
+// the scale lists of nw_execute_pac and nw_execute_pac_bins: positions inside the plan's scale list
+int check_scale_lists(const char* who, const nw_plan* p, const int32_t* fph, int32_t nph, const int32_t* fam,
+                      int32_t nam) {
+    const std::string w = std::string(who) + ": ";
+    if (nph < 0 || nam < 0) return fail(NW_E_INVALID, w + "nph < 0 or nam < 0");
+    if ((nph > 0 && !fph) || (nam > 0 && !fam)) return fail(NW_E_INVALID, w + "null scale list");
+    for (int which = 0; which < 2; ++which) {
+        const int32_t* const f = which ? fam : fph;
+        for (int32_t i = 0; i < (which ? nam : nph); ++i)
+            if (f[i] < 0 || f[i] >= p->nfreq)
+                return fail(NW_E_INVALID, w + (which ? "amplitude" : "phase") + " scale " + std::to_string(i) + " = " +
+                                              std::to_string(f[i]) + " is outside [0, " + std::to_string(p->nfreq) + ")");
+    }
+    return NW_OK;
+}
+
+// nbins of nw_pac_bin_edges and nw_execute_pac_bins
+int check_nbins(const char* who, int32_t nbins) {
+    if (!nw::pac_bins_valid(nbins))
+        return fail(NW_E_INVALID, std::string(who) + ": nbins (" + std::to_string(nbins) + ") must be even with 2 <= nbins <= " +
+                                      std::to_string(NW_PAC_MAX_BINS));
+    return NW_OK;
+}
+
 // the pair list of nw_conn_tiles / nw_execute_conn: indices inside [0, nchan)
 int check_pairs(const char* who, int32_t nchan, const int32_t* ia, const int32_t* ib, int64_t npairs) {
     if (nchan < 1) return fail(NW_E_INVALID, std::string(who) + ": nchan < 1");
@@ -1770,16 +1856,7 @@ int nw_execute_pac(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, co
     const char* const who = "nw_execute_pac";
     NW_TRY(check_epoch_call(who, p, !p || (!x && nepochs > 0) || (!out_m && npairs > 0 && nepochs > 0 && nph > 0 && nam > 0),
                             nullptr, mem, nepochs, nchan, ip, ia, npairs));
-    if (nph < 0 || nam < 0) return fail(NW_E_INVALID, "nw_execute_pac: nph < 0 or nam < 0");
-    if ((nph > 0 && !fph) || (nam > 0 && !fam)) return fail(NW_E_INVALID, "nw_execute_pac: null scale list");
-    for (int which = 0; which < 2; ++which) {
-        const int32_t* const f = which ? fam : fph;
-        for (int32_t i = 0; i < (which ? nam : nph); ++i)
-            if (f[i] < 0 || f[i] >= p->nfreq)
-                return fail(NW_E_INVALID, std::string("nw_execute_pac: ") + (which ? "amplitude" : "phase") +
-                                              " scale " + std::to_string(i) + " = " + std::to_string(f[i]) +
-                                              " is outside [0, " + std::to_string(p->nfreq) + ")");
-    }
+    NW_TRY(check_scale_lists(who, p, fph, nph, fam, nam));
     NW_TRY(check_chunk(who, p, nchan));
     NW_TRY(check_window(who, p->n_out(), t0, t1, step));
     // the grid of one chunk's launch (block indices are 32-bit)
@@ -1792,6 +1869,37 @@ int nw_execute_pac(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, co
     NW_TRY(begin_execute(p, &d));
     NW_TRY(execute_pac(p, d, x, nepochs, nchan, ip, ia, npairs, fph, nph, fam, nam, t0, t1, step, out_m, out_amp,
                        out_phase, mem == NW_MEM_HOST));
+    return dcheck_collect(p->stream);
+}
+
+int nw_pac_bin_edges(int32_t nbins, double* cs) {
+    NW_TRY(check_nbins("nw_pac_bin_edges", nbins));
+    if (!cs) return fail(NW_E_INVALID, "nw_pac_bin_edges: null argument");
+    pac_bin_edges(nbins, cs);
+    return NW_OK;
+}
+
+int nw_execute_pac_bins(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ip, const int32_t* ia,
+                        int64_t npairs, const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam, int64_t t0,
+                        int64_t t1, int64_t step, int32_t nbins, void* out_sum, void* out_count, int mem) {
+    const char* const who = "nw_execute_pac_bins";
+    NW_TRY(check_epoch_call(who, p, !p || (!x && nepochs > 0) || (!out_sum && npairs > 0 && nepochs > 0 && nph > 0 && nam > 0),
+                            nullptr, mem, nepochs, nchan, ip, ia, npairs));
+    NW_TRY(check_scale_lists(who, p, fph, nph, fam, nam));
+    NW_TRY(check_nbins(who, nbins));
+    NW_TRY(check_chunk(who, p, nchan));
+    NW_TRY(check_window(who, p->n_out(), t0, t1, step));
+    // the grid of one chunk's launch (block indices are 32-bit)
+    const int64_t blocks = nw::pac_blocks(std::max<int64_t>(p->max_batch / nchan, 1), npairs,
+                                          nw::pac_bins_tiles(nph, nam, nbins), true);
+    if (blocks < 0 || blocks > 0x7fffffff)
+        return fail(NW_E_INVALID, std::string(who) + ": " + std::to_string(npairs) + " pairs x " + std::to_string(nph) + " x " +
+                                      std::to_string(nam) + " scales per chunk need more than 2^31 - 1 blocks");
+    DeviceGuard guard(p->device);
+    nw::WDesc d;
+    NW_TRY(begin_execute(p, &d));
+    NW_TRY(execute_pac_bins(p, d, x, nepochs, nchan, ip, ia, npairs, fph, nph, fam, nam, t0, t1, step, nbins, out_sum,
+                            out_count, mem == NW_MEM_HOST));
     return dcheck_collect(p->stream);
 }
 

@@ -275,6 +275,15 @@ hipError_t launch_pac(int dtype, const void* src, void* m, void* amp, void* phas
                       const int32_t* fph, const int32_t* fam, int64_t ec, int nchan, int nfreq, int64_t n_out,
                       int64_t npairs, int nph, int nam, int64_t t0, int64_t count, int64_t step, bool xcd,
                       hipStream_t s);
+// phase-binned phase-amplitude coupling (nw_pac_bins.hip): src, the lists and the window as launch_pac;
+// sum (ec, npairs, nph, nam, nbins) fp64 = per phase bin of channel ip[p]'s row fph[i] the sum of A over
+// the window samples in that bin, in the order of conn_time_lane per bin; cnt (ec, nchan, nph, nbins) fp64 =
+// the samples per bin of every channel's listed phase rows (null: not formed).  edges: device array of
+// nbins {cos, sin} fp64 pairs, the table of nw_pac_bin_edges.  Every value is written, none is read.
+hipError_t launch_pac_bins(int dtype, const void* src, void* sum, void* cnt, const int32_t* ip, const int32_t* ia,
+                           const int32_t* fph, const int32_t* fam, const void* edges, int64_t ec, int nchan, int nfreq,
+                           int64_t n_out, int64_t npairs, int nph, int nam, int nbins, int64_t t0, int64_t count,
+                           int64_t step, bool xcd, hipStream_t s);
 hipError_t launch_finalize(int dtype, bool itc, const double* acc, void* out, int64_t fn, int64_t nsig,
                            hipStream_t s);
 hipError_t launch_add_f64(double* acc, const double* src, int64_t count, hipStream_t s);

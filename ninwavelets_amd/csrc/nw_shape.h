@@ -13,6 +13,8 @@
 //     map, block count, the sample count of a window and the lane of a sample (the order contract);
 //   - the phase-amplitude coupling kernel (nw_pac.hip): its scale tile, the tile counts and its
 //     block -> (epoch, pair, phase tile, amplitude tile) map;
+//   - the phase-binned coupling kernel (nw_pac_bins.hip): the geometry chosen from nbins, its LDS
+//     bytes and its tile counts;
 //   - the two-pass engine (nw_large.hip): the (N1, N2) split and its visitor, the row pass's
 //     elements per thread, rows per block, pass-0 ladder and LDS-DMA rule, the column pass's
 //     block shape, the scale chunk and the support buffer's layout (mode `large` prints them);
@@ -474,6 +476,46 @@ static_assert(pac_tiles_ph(8) == 1 && pac_tiles_ph(9) == 2 && pac_tiles_am(16) =
               "scale tile counts");
 static_assert(pac_blocks(2, 5, 4, false) == 40 && pac_blocks(2, 5, 4, true) == 64 && pac_blocks(0, 5, 4, true) == 0,
               "block count");
+
+// ---- phase-binned phase-amplitude coupling (nw_pac_bins.hip) -----------------------------------
+
+// nw_pac_bins_kernel: a block owns one epoch e of the chunk, one channel pair, ONE listed phase scale
+// and a tile of kPacBinsWaves * ka listed amplitude scales; wave w keeps the tile's amplitude scales
+// w * ka .. w * ka + ka - 1, lane = sample of a kConnTileN-sample tile, sums in conn_time_lane's order.
+// A lane's nbins * ka partial sums are addressed by a run-time bin, so they live in LDS and not in
+// registers: acc[w][bin * ka + k][lane] in fp64, a wave's accesses differing in the lane term only
+// (conflict-free), cap * ka * 512 B per wave with cap >= nbins the bins the build holds.  The geometry is
+// chosen from nbins so that two blocks fit a CU's 160 KiB: fewer bins, more amplitude scales per wave.
+constexpr int kPacBinsWaves = 4;
+constexpr int kPacBinsMax = NW_PAC_MAX_BINS;
+static_assert(kPacBinsMax == 36, "the geometry classes below");
+struct PacBinsGeom {
+    int cap, ka;   // bins the accumulators hold, amplitude scales per wave
+};
+constexpr PacBinsGeom pac_bins_geom(int nbins) {
+    return nbins <= 8 ? PacBinsGeom{8, 4} : nbins <= 18 ? PacBinsGeom{18, 2} : PacBinsGeom{kPacBinsMax, 1};
+}
+constexpr bool pac_bins_valid(int64_t nbins) { return nbins >= 2 && nbins <= kPacBinsMax && nbins % 2 == 0; }
+// the amplitude scales of a tile, and the static LDS of a block: the accumulators, the double-buffered
+// bin indices of kPacBinsWaves sample tiles and the edge table
+constexpr int pac_bins_am(int nbins) { return kPacBinsWaves * pac_bins_geom(nbins).ka; }
+constexpr int64_t pac_bins_lds(int nbins) {
+    return (int64_t)kPacBinsWaves * pac_bins_geom(nbins).cap * pac_bins_geom(nbins).ka * kConnTileN * 8 +
+           2 * kPacBinsWaves * kConnTileN * 4 + pac_bins_geom(nbins).cap * 16;
+}
+constexpr int64_t pac_bins_tiles_am(int64_t nam, int nbins) { return (nam + pac_bins_am(nbins) - 1) / pac_bins_am(nbins); }
+// The tiles of one (epoch, pair): listed phase scale x amplitude tile, amplitude tile fastest.  block ->
+// (epoch, pair, phase position, amplitude tile) is pac_slot(b, npairs, ntiles, nta, xcd) with tp the phase
+// position, and the grid is pac_blocks(ec, npairs, ntiles, xcd).
+constexpr int64_t pac_bins_tiles(int64_t nph, int64_t nam, int nbins) { return nph * pac_bins_tiles_am(nam, nbins); }
+static_assert(pac_bins_geom(2).ka == 4 && pac_bins_geom(8).ka == 4 && pac_bins_geom(10).ka == 2 &&
+                  pac_bins_geom(18).ka == 2 && pac_bins_geom(20).ka == 1 && pac_bins_geom(36).cap == 36,
+              "geometry classes");
+static_assert(2 * pac_bins_lds(2) <= 160 * 1024 && 2 * pac_bins_lds(18) <= 160 * 1024 && 2 * pac_bins_lds(36) <= 160 * 1024,
+              "two blocks per CU");
+static_assert(pac_bins_tiles(9, 17, 18) == 27 && pac_bins_tiles(9, 17, 36) == 45 && pac_bins_tiles(9, 17, 4) == 18 &&
+                  pac_bins_tiles(0, 5, 18) == 0,
+              "tile counts");
 
 // ---- the two-pass engine (nw_large.hip) -----------------------------------------------------
 

@@ -38,6 +38,8 @@ LAG_OUTS = {'lag_sum': 'lag_sum', 'pli': 'lag_sum', 'pli2_unbiased': 'lag_sum', 
             'wpli': 'lag_sum', 'wpli2_debiased': 'lag_sum', 'ciplv': 'plv_sum', 'ppc': 'plv_sum'}
 # phase-amplitude coupling (Plan.execute_pac): what finalize_pac forms from its sums (M, amp, phase)
 PAC_OUTS = {'pac_sum', 'mvl', 'mvl_norm', 'direct_pac', 'debiased_pac'}
+# phase-binned coupling (Plan.execute_pac_bins): what finalize_pac_bins forms from its sums (S, count)
+PAC_BIN_OUTS = {'bin_sum', 'bin_amp', 'mi', 'hr', 'pref_phase'}
 # envelope correlation (Plan.execute_env_time): the Pearson sums of two amplitude envelopes, plain
 # (float64 (E, P, F)) or pairwise orthogonalised (float64 (E, P, F, 6)), each with the per-channel sums
 # float64 (E, C, F, 2); and what finalize_env forms, name -> the sums it needs
@@ -299,6 +301,52 @@ def finalize_pac(kind: str, M, amp, phase, ip, ia, nsamples: int):
     den = np.broadcast_to(den, M.shape)
     zero = den == 0
     return np.where(zero, 0., np.abs(M) / np.where(zero, 1., den))
+
+
+check_nbins = L.check_nbins     # nbins of the phase-binned calls, checked before any device work
+
+
+def finalize_pac_bins(kind: str, S, count, ip):
+    """The phase-binned coupling measure ``kind`` per epoch, pair and (phase scale, amplitude scale) from
+    the sums of Plan.execute_pac_bins: ``S`` float64 (E, P, Fp, Fa, nbins), the amplitude of the pair's
+    amplitude channel summed within each phase bin of its phase channel ip[p], and ``count`` float64
+    (E, C, Fp, nbins), the samples N_b per bin.  With the mean amplitude A_b = S_b / N_b of a bin and the
+    distribution P_b = A_b / sum_b A_b:
+      bin_amp     A_b                                               (E, P, Fp, Fa, nbins): the histogram
+      mi          (log nbins + sum_b P_b log P_b) / log nbins       (Tort et al. 2010; a bin with P_b = 0 adds 0)
+      hr          (max P - min P) / max P                           the height ratio
+      pref_phase  theta_b + pi / nbins of the first bin with the largest A_b, theta_b = -pi + 2 pi b / nbins
+    mi, hr and pref_phase float64 (E, P, Fp, Fa).  A bin without a sample (N_b = 0) makes bin_amp NaN there
+    and mi, hr and pref_phase of the cell NaN; sum_b A_b = 0 with no empty bin gives mi = hr = 0 (the
+    zero-denominator convention of finalize_pac).  ``bin_sum`` returns (S, count) unchanged."""
+    if kind not in PAC_BIN_OUTS:
+        raise ValueError(f"out must be one of {', '.join(sorted(PAC_BIN_OUTS))}; got {kind!r}")
+    if kind == 'bin_sum':
+        return S, count
+    S, count = np.asarray(S, dtype=np.float64), np.asarray(count, dtype=np.float64)
+    if S.ndim != 5 or count.ndim != 4 or S.shape[-1] != count.shape[-1]:
+        raise ValueError(f'S must be (epochs, pairs, phase scales, amplitude scales, bins) and count (epochs, channels, '
+                         f'phase scales, bins), got shapes {S.shape} and {count.shape}')
+    nbins = S.shape[-1]
+    N = count[:, np.asarray(ip, dtype=np.intp)][:, :, :, None, :]                  # (E, P, Fp, 1, nbins)
+    empty = np.broadcast_to(N == 0, S.shape)
+    A = np.where(empty, np.nan, S / np.where(N == 0, 1., N))
+    if kind == 'bin_amp':
+        return A
+    bad = empty.any(axis=-1) | np.isnan(A).any(axis=-1)                            # an empty bin, a NaN sum
+    tot = np.where(bad, 1., A.sum(axis=-1))
+    if kind == 'pref_phase':
+        first = np.argmax(np.where(bad[..., None], 0., A), axis=-1)
+        return np.where(bad, np.nan, -np.pi + 2 * np.pi * first / nbins + np.pi / nbins)
+    zero = tot == 0
+    P = np.where(bad[..., None], 1., A) / np.where(zero, 1., tot)[..., None]
+    if kind == 'hr':
+        top = P.max(axis=-1)
+        res = np.where(top == 0, 0., (top - P.min(axis=-1)) / np.where(top == 0, 1., top))
+    else:
+        plogp = np.where(P > 0, P * np.log(np.where(P > 0, P, 1.)), 0.)
+        res = np.where(zero, 0., (np.log(nbins) + plogp.sum(axis=-1)) / np.log(nbins))
+    return np.where(bad, np.nan, res)
 
 
 def _pearson(sxy, sx, sy, sxx, syy, T: int):
@@ -845,6 +893,33 @@ class Plan:
                                        ('phase', (nep, nchan, nph), np.complex128, True)])
         self._epoch_execute(L.lib().nw_execute_pac, x,
                             (nep, nchan, _ptr(ip), _ptr(ia), npairs, _ptr(fph), nph, _ptr(fam), nam, t0, t1, step), outs)
+        return out if dev else tuple(outs)
+
+    def execute_pac_bins(self, x, indices=None, phase=None, amp=None, window=None, step: int = 1, nbins: int = 18,
+                         out=None):
+        """Phase-binned phase-amplitude coupling sums (nw_execute_pac_bins): x, ``indices``, ``phase``,
+        ``amp``, ``window`` and ``step`` as in execute_pac; ``nbins`` even, 2 .. 36.  Returns (S float64
+        (E, P, Fp, Fa, nbins) = the amplitude |y_a| summed within each phase bin of y_p, count float64
+        (E, C, Fp, nbins) = the samples per bin); bin b holds the phases [-pi + 2 pi b / nbins, -pi + 2 pi
+        (b + 1) / nbins), by the rule of ninwave.h on the table L.pac_bin_edges(nbins); see finalize_pac_bins.
+        numpy arrays: synchronous, ``out`` optional.  Device tensors: asynchronous on the plan stream,
+        ``out`` = (S, count) required (count may be None: not formed).  The plan needs max_batch >= C."""
+        nep, nchan = _epochs(x)
+        ip, ia = check_pac_indices(indices, nchan)
+        npairs = int(ip.size)
+        fph, fam = check_scales('phase', phase, self.nfreq), check_scales('amp', amp, self.nfreq)
+        nph, nam = int(fph.size), int(fam.size)
+        nbins = check_nbins(nbins)
+        t0, t1, step = self._window(window, step)
+        x = self._epoch_input(x, nep * nchan, out)
+        dev = _is_device_tensor(x)
+        outs = _unpack(out, 2, 'device output must be (S, count) tensors (count may be None)' if dev else
+                       'out must be (S, count) arrays')
+        outs = self._outputs(x, outs, [('S', (nep, npairs, nph, nam, nbins), np.float64, False),
+                                       ('count', (nep, nchan, nph, nbins), np.float64, True)])
+        self._epoch_execute(L.lib().nw_execute_pac_bins, x,
+                            (nep, nchan, _ptr(ip), _ptr(ia), npairs, _ptr(fph), nph, _ptr(fam), nam, t0, t1, step, nbins),
+                            outs)
         return out if dev else tuple(outs)
 
     def _window(self, window, step):

@@ -153,6 +153,19 @@ class EpochsWavelet:
                                       amp=np.arange(len(pf), len(pf) + len(af)), out=method, indices=indices,
                                       window=window, decim=decim, average=average)
 
+    def pac_bins(self, ch_names, phase_freqs, amp_freqs, method: str = 'mi', nbins: int = 18, indices=None,
+                 padding: float = 0., decim: int = 1, average: bool = False):
+        """``method`` (pac_bins_batch's outs: mi, hr, pref_phase, bin_amp, bin_sum) from the amplitude at
+        ``amp_freqs`` averaged within ``nbins`` bins of the phase at ``phase_freqs``: (E, P, Fp, Fa), and
+        (E, P, Fp, Fa, nbins) for the histogram ``bin_amp``.  Frequency lists, ``indices``, ``padding``, ``decim``
+        and ``average`` as in pac (``average=True`` is a ValueError for pref_phase and bin_sum)."""
+        waves = self._pick(ch_names)
+        window = self._padded(waves.shape[-1], padding)
+        pf, af = list(phase_freqs), list(amp_freqs)
+        return self.wavelet.pac_bins_batch(waves, pf + af, reuse=False, phase=np.arange(len(pf)),
+                                           amp=np.arange(len(pf), len(pf) + len(af)), out=method, nbins=nbins,
+                                           indices=indices, window=window, decim=decim, average=average)
+
     # -- connectivity between many channels: one transform per epoch and channel, every pair's
     #    sums from it (WaveletBase.connectivity_batch; no reference counterpart) ---------------
     def connectivity(self, ch_names, freqs, method: str = 'coherence', indices=None, decim: int = 1):
