@@ -167,6 +167,9 @@ typedef struct nw_stats {
 #define NW_REDUCE_PAC_BINS 7   /* nw_execute_pac_bins: per-signal rows per chunk, every (epoch, pair,
                                   phase scale, amplitude scale, phase bin) summed over the window
                                   by nw_pac_bins_kernel                                         */
+#define NW_REDUCE_ERPAC 8      /* nw_execute_erpac: per-signal rows per chunk, every (pair, phase
+                                  scale, amplitude scale, window sample) added in epoch order by
+                                  nw_erpac_kernel                                               */
 
 /* nw_stats.kernel: which kernel wrote the output rows (the dominant kernel of a step) */
 #define NW_K_NONE        0
@@ -407,6 +410,34 @@ int nw_execute_pac_bins(nw_plan* plan, const void* x, int64_t nepochs, int32_t n
                         const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam,
                         int64_t t0, int64_t t1, int64_t step, int32_t nbins,
                         void* out_sum, void* out_count, int mem);
+
+/* Event-related phase-amplitude coupling (ERPAC; Voytek et al. 2013): nw_execute_pac's quantities
+ * summed over the EPOCHS at every sample of a window instead of over the samples of every epoch -- what
+ * the circular-linear correlation across epochs of the phase and the amplitude (tensorpac's
+ * EventRelatedPac(method='circular')) and the across-epoch forms of nw_execute_pac's measures are formed
+ * from.  x, ip / ia, fph / fam, nchan, chunking (max_batch / nchan epochs, max_batch >= nchan), mem, every
+ * engine form, decimated plans, the window (t0, t1, step) in the plan's OUTPUT samples and its count T are
+ * nw_execute_pac's, with the same checks.  With, in fp64, for epoch e at the window sample s_j = t0 + j step,
+ *   A = hypot(re, im)                              of y_{e, ia[p]}[fam[k], s_j]   (amp: of channel c)
+ *   (c, s) = (re / h, im / h), h = hypot(re, im)   of y_{e, ip[p]}[fph[i], s_j]   (phase: of channel c)
+ *   u = c + i s   (nw_execute_pac's unit phasor, NaN where |y| = 0)
+ * the outputs are sums over e = 0 .. nepochs - 1, the sample index j innermost:
+ *   out_m     complex128 (npairs, nph, nam, T) = sum_e A u
+ *   out_amp   float64    (nchan, nam, T, 2)    = {sum_e A, sum_e (re re + im im)}             (may be NULL)
+ *   out_phase float64    (nchan, nph, 5, T)    = the planes sum_e c, sum_e s, sum_e c c, sum_e s s,
+ *                                                sum_e c s                                      (may be NULL)
+ * Every product and every term is rounded on its own (no fma into a sum).  Each output value has ONE fp64
+ * accumulator that starts at +0.0 and adds the epochs' terms in epoch order, so a value depends only on
+ * its rows and on its sample: not on the pair list, the scale lists, their tiling, the window or on how
+ * the epochs are chunked; out_amp[..., 1] is bit-identical to nw_execute_conn's out_power of the same row
+ * and sample.  nepochs = 0: zero sums; npairs = 0 or an empty list: that output is empty; t0 == t1: empty
+ * outputs.  The accumulators live in the plan (nw_stats.device_bytes); NW_E_NOMEM if they do not fit,
+ * NW_E_INVALID if a launch would need more than 2^31 - 1 blocks.  nw_stats.reduce_path: NW_REDUCE_ERPAC. */
+int nw_execute_erpac(nw_plan* plan, const void* x, int64_t nepochs, int32_t nchan,
+                     const int32_t* ip, const int32_t* ia, int64_t npairs,
+                     const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam,
+                     int64_t t0, int64_t t1, int64_t step,
+                     void* out_m, void* out_amp, void* out_phase, int mem);
 
 /* Envelope correlation (Hipp et al. 2012; mne-connectivity's envelope_correlation): per epoch, channel
  * pair and scale the sums from which the Pearson correlation over time of two amplitude envelopes is

@@ -26,9 +26,9 @@ import numpy as np
 from scipy.fftpack import fft, ifft
 
 from . import _lib as L
-from .engine import (CONN_OUTS, ENV_OUTS, LAG_OUTS, PAC_BIN_OUTS, PAC_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim,
+from .engine import (CONN_OUTS, ENV_OUTS, ERPAC_OUTS, LAG_OUTS, PAC_BIN_OUTS, PAC_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim,
                      check_indices, check_nbins, check_pac_indices, check_scales, execute_multi, finalize_conn,
-                     finalize_conn_time, finalize_env, finalize_lag, finalize_pac, finalize_pac_bins, finalize_pair,
+                     finalize_conn_time, finalize_env, finalize_erpac, finalize_lag, finalize_pac, finalize_pac_bins, finalize_pair,
                      np_dtype, time_window)
 from .engine import make_wavelets as _make_wavelets_dev
 
@@ -581,10 +581,10 @@ class WaveletBase:
                                lambda plan, *a: plan.execute_conn_time(*a, out_kind=outs[out]), finalize)
 
     def _time_sums(self, waves, freqs, reuse, out, names, check_pairs, indices, window, decim, average, min_count,
-                   execute, finalize, scales=None):
+                   execute, finalize, scales=None, min_epochs=0):
         """The over-time measures of (E, C, N) epochs: the argument checks (``out`` one of ``names``,
-        the pair list by ``check_pairs``, at least ``min_count`` window samples; ``scales``: pac_batch's
-        (phase, amp) lists), the cache, the plan of the first device with max_batch >= C and its
+        the pair list by ``check_pairs``, at least ``min_count`` window samples and ``min_epochs`` epochs;
+        ``scales``: pac_batch's (phase, amp) lists), the cache, the plan of the first device with max_batch >= C and its
         eviction, sums = execute(plan, waves, pairs, *scales, window, step) and
         finalize(sums, *pairs, count), averaged over the epochs where asked."""
         decim = check_decim(decim)
@@ -594,6 +594,8 @@ class WaveletBase:
             raise ValueError(f'average=True takes a finalised measure, not the sums {out!r}')
         waves, nep, nchan, n = _epochs(waves)
         pairs = check_pairs(indices, nchan)
+        if nep < min_epochs:
+            raise ValueError(f'{out} needs at least {min_epochs} epochs, got {nep}')
         rebuild = (not reuse) or self._cache is None
         if scales is not None:
             nfreq = len(list(freqs)) if rebuild else len(self._cache.freqs)     # the scale list the call will use
@@ -655,6 +657,29 @@ class WaveletBase:
                                window, decim, average, 0 if out == 'pac_sum' else 1,
                                lambda plan, *a: plan.execute_pac(*a),
                                lambda sums, *a: finalize_pac(out, *sums, *a), scales=(phase, amp))
+
+    def erpac_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, phase=None, amp=None,
+                    out: str = 'circular', indices=None, window=None, decim: int = 1):
+        """Event-related phase-amplitude coupling of ``waves`` (E, C, N) (ERPAC; Voytek et al. 2013): WHEN,
+        relative to the event the epochs are locked to, the amplitude of the scales ``amp`` follows the phase
+        of the scales ``phase`` -- the coupling is formed ACROSS the epochs at every sample, one time course
+        per pair and (phase scale, amplitude scale): (P, Fp, Fa, N') float64.  Every signal is transformed once
+        and reduced on the device; the (E, C, F, N) rows never leave it.  ``out`` (engine.finalize_erpac):
+        ``circular`` (the circular-linear correlation of phase and amplitude over the epochs, tensorpac's
+        EventRelatedPac(method='circular')), ``circular_pval`` (its p-value), and pac_batch's mvl, mvl_norm,
+        direct_pac and debiased_pac taken over the epochs; ``erpac_sum`` returns the sums (M (P, Fp, Fa, N'), amp
+        (C, Fa, N', 2), phase (C, Fp, 5, N')).  ``phase``, ``amp`` and ``indices`` as in pac_batch; ``window`` =
+        (t0, t1) in full-rate samples (None: the whole epoch) and ``decim`` as in connectivity_time_batch: N' is
+        the number of decimated samples j * decim in [t0, t1).  The circular kinds need E >= 2, the others
+        E >= 1.  There is no ``average``: the epochs are already reduced.  The plan takes as many epochs per
+        chunk as the plan-size policy allows: the device reads and writes its (P, Fp, Fa, N') accumulators once
+        per chunk, so the rate depends on the epochs per chunk.  Cache semantics, device choice
+        and plan eviction as in connectivity_batch."""
+        need = 0 if out == 'erpac_sum' else 2 if str(out).startswith('circular') else 1
+        return self._time_sums(waves, freqs, reuse, out, dict.fromkeys(sorted(ERPAC_OUTS)), check_pac_indices, indices,
+                               window, decim, False, 0, lambda plan, *a: plan.execute_erpac(*a),
+                               lambda sums, ip, ia, count: finalize_erpac(out, *sums, ip, ia, len(waves)),
+                               scales=(phase, amp), min_epochs=need)
 
     def pac_bins_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, phase=None, amp=None, out: str = 'mi',
                        nbins: int = 18, indices=None, window=None, decim: int = 1, average: bool = False):

@@ -270,7 +270,7 @@ struct nw_plan {
     DevBuf d_acc;                    // epoch reductions: fp64 (F, n) sums (x2 for phases); nw_execute_conn:
                                      // complex (npairs, F, n) | (nchan, F, n) | the pair tiles
     std::vector<nw::ConnTile> conn_tiles;   // nw_execute_conn: the last call's tiles (the upload's source)
-    std::vector<int32_t> pac_lists;         // nw_execute_pac: the last call's ip | ia | fph | fam (likewise)
+    std::vector<int32_t> pac_lists;         // nw_execute_pac, _pac_bins, _erpac: the last call's ip | ia | fph | fam (likewise)
     // nw_execute_multi_device reductions: this device's fp64 partial sums, and (device 0's
     // plan) the peer-copy landing buffer; kept across calls (a hipFree per call would
     // synchronise the device on every epoch-loop iteration)
@@ -965,7 +965,7 @@ int execute_pair(nw_plan* p, const nw::WDesc& d, const void* xa, const void* xb,
     return end_reduce(p, host);
 }
 
-// The epoch-chunk reductions (nw_execute_conn, _conn_time, _env_time, _pac) share one layout of d_acc
+// The epoch-chunk reductions (nw_execute_conn, _conn_time, _env_time, _pac, _pac_bins, _erpac) share one layout of d_acc
 // and one loop.  d_acc holds the call's fp64 output regions one after the other and then, 16-aligned,
 // one auxiliary blob (tile descriptors or index lists) that is built and uploaded once per call.
 struct SumRegion {
@@ -1177,6 +1177,50 @@ int execute_pac(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, 
                                nw::launch_pac(p->dtype, rows, r[0].at(e0), r[1].at(e0), r[2].at(e0), d_ip, d_ia, d_fph,
                                               d_fam, ec, nchan, p->nfreq, p->n_out(), npairs, nph, nam, t0, count, step,
                                               xcd, p->stream));
+    });
+}
+
+// Event-related phase-amplitude coupling (nw_execute_erpac): execute_pac's staging and lists with the sums
+// taken over the epochs: per chunk nw_erpac_kernel adds the chunk's epochs to the (P, nph, nam, T) sums, which
+// it reads and writes once per chunk, and nw_erpac_rows_kernel to the per-channel sums.  The three regions
+// belong to the call as a whole (epoch = 0) and start at zero.
+int execute_erpac(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ip,
+                  const int32_t* ia, int64_t npairs, const int32_t* fph, int nph, const int32_t* fam, int nam,
+                  int64_t t0, int64_t t1, int64_t step, void* out_m, void* out_amp, void* out_phase, bool host) {
+    const int64_t count = nw::conn_time_count(t0, t1, step);
+    SumRegion r[3] = {{out_m, (size_t)npairs * nph * nam * count * 2 * sizeof(double), 0},
+                      {out_amp, out_amp ? (size_t)nchan * nam * count * 2 * sizeof(double) : 0, 0},
+                      {out_phase, out_phase ? (size_t)nchan * nph * count * 5 * sizeof(double) : 0, 0}};
+    std::vector<int32_t>& lists = p->pac_lists;                   // ip, ia, fph, fam
+    lists.clear();
+    lists.insert(lists.end(), ip, ip + npairs);
+    lists.insert(lists.end(), ia, ia + npairs);
+    lists.insert(lists.end(), fph, fph + nph);
+    lists.insert(lists.end(), fam, fam + nam);
+    const char* d_lists = nullptr;
+    NW_TRY(place_sums(p, r, 3, lists.data(), lists.size() * sizeof(int32_t), &d_lists, true,
+                      "nw_execute_erpac: the fp64 accumulators of " + std::to_string(npairs) + " pairs, " +
+                          std::to_string(nph) + " x " + std::to_string(nam) + " scales and " + std::to_string(count) +
+                          " samples"));
+    const int32_t* const d_ip = (const int32_t*)d_lists;
+    const int32_t* const d_ia = d_ip + npairs;
+    const int32_t* const d_fph = d_ia + npairs;
+    const int32_t* const d_fam = d_fph + nph;
+    const bool xcd = xcd_order();
+    nw_logf(1, "plan %p: erpac sums, %lld epochs x %d channels, %lld pairs, %d phase x %d amplitude scales in %lld tiles "
+               "x %lld sample tiles (%lld epochs per chunk), window [%lld, %lld) step %lld of %lld samples, %s buffers: "
+               "per-signal rows per chunk, every (pair, phase scale, amplitude scale, sample) of the window's %lld added "
+               "in epoch order in fp64",
+            (void*)p, (long long)nepochs, nchan, (long long)npairs, nph, nam, (long long)nw::pac_tiles(nph, nam),
+            (long long)nw::erpac_sample_tiles(count), (long long)(p->max_batch / nchan), (long long)t0, (long long)t1,
+            (long long)step, (long long)p->n_out(), host ? "host" : "device", (long long)count);
+    p->stats.reduce_path = NW_REDUCE_ERPAC;
+    return run_epoch_chunks(p, d, x, nepochs, nchan, r, 3, host, [&](int64_t, int64_t ec, void* rows) -> int {
+        if (!(r[0].bytes + r[1].bytes + r[2].bytes)) return NW_OK;
+        return NW_KERNEL_STAGE(p, ST_EPI, true,
+                               nw::launch_erpac(p->dtype, rows, r[0].dev, r[1].dev, r[2].dev, d_ip, d_ia, d_fph, d_fam,
+                                                ec, nchan, p->nfreq, p->n_out(), npairs, nph, nam, t0, count, step, xcd,
+                                                p->stream));
     });
 }
 
@@ -1869,6 +1913,33 @@ int nw_execute_pac(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, co
     NW_TRY(begin_execute(p, &d));
     NW_TRY(execute_pac(p, d, x, nepochs, nchan, ip, ia, npairs, fph, nph, fam, nam, t0, t1, step, out_m, out_amp,
                        out_phase, mem == NW_MEM_HOST));
+    return dcheck_collect(p->stream);
+}
+
+int nw_execute_erpac(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ip, const int32_t* ia,
+                     int64_t npairs, const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam, int64_t t0,
+                     int64_t t1, int64_t step, void* out_m, void* out_amp, void* out_phase, int mem) {
+    const char* const who = "nw_execute_erpac";
+    NW_TRY(check_epoch_call(who, p, !p || (!x && nepochs > 0) || (!out_m && npairs > 0 && nph > 0 && nam > 0 && t0 < t1),
+                            nullptr, mem, nepochs, nchan, ip, ia, npairs));
+    NW_TRY(check_scale_lists(who, p, fph, nph, fam, nam));
+    NW_TRY(check_chunk(who, p, nchan));
+    NW_TRY(check_window(who, p->n_out(), t0, t1, step));
+    // the grid of a launch (block indices are 32-bit): it does not depend on the chunk
+    const int64_t blocks = nw::erpac_blocks(npairs, nw::erpac_sample_tiles(nw::conn_time_count(t0, t1, step)),
+                                            nw::pac_tiles(nph, nam), true);
+    // ... and nw_erpac_rows_kernel's, one thread per (channel, listed scale, sample) of the outputs asked for
+    const int64_t row_blocks = ((int64_t)nchan * ((out_amp ? (int64_t)nam : 0) + (out_phase ? (int64_t)nph : 0)) *
+                                    nw::conn_time_count(t0, t1, step) + 255) / 256;
+    if (blocks < 0 || blocks > 0x7fffffff || row_blocks > 0x7fffffff)
+        return fail(NW_E_INVALID, std::string(who) + ": " + std::to_string(npairs) + " pairs x " + std::to_string(nph) + " x " +
+                                      std::to_string(nam) + " scales x " + std::to_string(nw::conn_time_count(t0, t1, step)) +
+                                      " samples need more than 2^31 - 1 blocks");
+    DeviceGuard guard(p->device);
+    nw::WDesc d;
+    NW_TRY(begin_execute(p, &d));
+    NW_TRY(execute_erpac(p, d, x, nepochs, nchan, ip, ia, npairs, fph, nph, fam, nam, t0, t1, step, out_m, out_amp,
+                         out_phase, mem == NW_MEM_HOST));
     return dcheck_collect(p->stream);
 }
 

@@ -275,6 +275,14 @@ hipError_t launch_pac(int dtype, const void* src, void* m, void* amp, void* phas
                       const int32_t* fph, const int32_t* fam, int64_t ec, int nchan, int nfreq, int64_t n_out,
                       int64_t npairs, int nph, int nam, int64_t t0, int64_t count, int64_t step, bool xcd,
                       hipStream_t s);
+// event-related phase-amplitude coupling (nw_erpac.hip): src, the lists and the window as launch_pac, the
+// chunk's ec epochs ADDED in epoch order to m (npairs, nph, nam, count) complex fp64 += A u, amp (nchan, nam,
+// count, 2) fp64 += {A, |y|^2} and phase (nchan, nph, 5, count) fp64 += {c, s, c c, s s, c s} (null: not
+// formed): every value is read, added to and written once per launch.
+hipError_t launch_erpac(int dtype, const void* src, void* m, void* amp, void* phase, const int32_t* ip,
+                        const int32_t* ia, const int32_t* fph, const int32_t* fam, int64_t ec, int nchan, int nfreq,
+                        int64_t n_out, int64_t npairs, int nph, int nam, int64_t t0, int64_t count, int64_t step,
+                        bool xcd, hipStream_t s);
 // phase-binned phase-amplitude coupling (nw_pac_bins.hip): src, the lists and the window as launch_pac;
 // sum (ec, npairs, nph, nam, nbins) fp64 = per phase bin of channel ip[p]'s row fph[i] the sum of A over
 // the window samples in that bin, in the order of conn_time_lane per bin; cnt (ec, nchan, nph, nbins) fp64 =

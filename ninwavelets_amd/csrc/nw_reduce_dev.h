@@ -1,5 +1,5 @@
 // nw_reduce_dev.h — the device pieces the epoch-chunk reductions share (nw_conn.hip, nw_conn_time.hip,
-// nw_env.hip, nw_pac.hip): the rounded fp64 arithmetic, the fold of a wave, the pair arithmetic as
+// nw_env.hip, nw_pac.hip, nw_erpac.hip): the rounded fp64 arithmetic, the fold of a wave, the pair arithmetic as
 // policy types, and the two kernel skeletons of the over-time sums.  The summation order is the
 // contract (ninwave.h): a change here changes every kernel that uses the piece, identically.
 //

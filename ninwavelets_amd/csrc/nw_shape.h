@@ -13,6 +13,8 @@
 //     map, block count, the sample count of a window and the lane of a sample (the order contract);
 //   - the phase-amplitude coupling kernel (nw_pac.hip): its scale tile, the tile counts and its
 //     block -> (epoch, pair, phase tile, amplitude tile) map;
+//   - the event-related coupling kernel (nw_erpac.hip): its sample-tile count, its block -> (pair,
+//     sample tile, phase tile, amplitude tile) map and its block count;
 //   - the phase-binned coupling kernel (nw_pac_bins.hip): the geometry chosen from nbins, its LDS
 //     bytes and its tile counts;
 //   - the two-pass engine (nw_large.hip): the (N1, N2) split and its visitor, the row pass's
@@ -475,6 +477,38 @@ static_assert(pac_tiles_ph(8) == 1 && pac_tiles_ph(9) == 2 && pac_tiles_am(16) =
                   pac_tiles(9, 17) == 4 && pac_tiles(0, 5) == 0,
               "scale tile counts");
 static_assert(pac_blocks(2, 5, 4, false) == 40 && pac_blocks(2, 5, 4, true) == 64 && pac_blocks(0, 5, 4, true) == 0,
+              "block count");
+
+// ---- event-related phase-amplitude coupling (nw_erpac.hip) -------------------------------------
+
+// nw_erpac_kernel: nw_pac_kernel's scale tile and wave split with the sum taken over the EPOCHS of the
+// chunk: a block owns one channel pair, one sample tile of kConnTileN consecutive window samples (lane =
+// sample) and one scale tile; its kPacAmWave * kPacPh complex fp64 accumulators per lane are loaded from
+// the call's sums at the start of a launch and stored back at its end.
+constexpr int64_t erpac_sample_tiles(int64_t count) { return conn_time_tiles(count); }
+// block -> (pair, sample tile, phase tile, amplitude tile).  The unit of conn_slot is pair * nst + st: in
+// the XCD order the scale tiles of one (pair, sample tile) -- which read the same samples of the same two
+// channels' rows -- are neighbours on one XCD, and the units are padded to a multiple of 8 (a slot with
+// pair >= npairs is padding and its block returns).  nst = erpac_sample_tiles(T) >= 1, ntiles =
+// pac_tiles(nph, nam) >= 1, nta = pac_tiles_am(nam).
+struct ErpacSlot {
+    int64_t pair;   // >= npairs: padding of the XCD order
+    int64_t st;
+    int tp, ta;
+};
+NW_SHAPE_HD NW_INLINE ErpacSlot erpac_slot(int64_t b, int64_t nst, int ntiles, int nta, bool xcd) {
+    const ConnSlot sl = conn_slot(b, ntiles, xcd);
+    return {sl.unit / nst, sl.unit % nst, sl.tile / nta, sl.tile % nta};
+}
+// (-1 where the scale tiles do not fit conn_slot's 32-bit tile index; 0 for an empty window)
+constexpr int64_t erpac_blocks(int64_t npairs, int64_t nst, int64_t ntiles, bool xcd) {
+    return ntiles > 0x7fffffff ? -1 : conn_blocks(npairs * nst, (int)ntiles, xcd);
+}
+static_assert(erpac_sample_tiles(0) == 0 && erpac_sample_tiles(64) == 1 && erpac_sample_tiles(65) == 2 &&
+                  erpac_sample_tiles(1201) == 19,
+              "sample tile count");
+static_assert(erpac_blocks(5, 19, 4, false) == 380 && erpac_blocks(5, 19, 4, true) == 384 && erpac_blocks(5, 0, 4, true) == 0 &&
+                  erpac_blocks(0, 19, 4, true) == 0,
               "block count");
 
 // ---- phase-binned phase-amplitude coupling (nw_pac_bins.hip) -----------------------------------

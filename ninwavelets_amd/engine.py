@@ -38,6 +38,8 @@ LAG_OUTS = {'lag_sum': 'lag_sum', 'pli': 'lag_sum', 'pli2_unbiased': 'lag_sum', 
             'wpli': 'lag_sum', 'wpli2_debiased': 'lag_sum', 'ciplv': 'plv_sum', 'ppc': 'plv_sum'}
 # phase-amplitude coupling (Plan.execute_pac): what finalize_pac forms from its sums (M, amp, phase)
 PAC_OUTS = {'pac_sum', 'mvl', 'mvl_norm', 'direct_pac', 'debiased_pac'}
+# event-related coupling (Plan.execute_erpac): what finalize_erpac forms from its across-epoch sums (M, amp, phase)
+ERPAC_OUTS = {'erpac_sum', 'circular', 'circular_pval', 'mvl', 'mvl_norm', 'direct_pac', 'debiased_pac'}
 # phase-binned coupling (Plan.execute_pac_bins): what finalize_pac_bins forms from its sums (S, count)
 PAC_BIN_OUTS = {'bin_sum', 'bin_amp', 'mi', 'hr', 'pref_phase'}
 # envelope correlation (Plan.execute_env_time): the Pearson sums of two amplitude envelopes, plain
@@ -401,6 +403,54 @@ def finalize_env(kind: str, pair, chan, ia, ib, nsamples: int):
     if kind == 'aec_orth':
         return (np.abs(r_ab) + np.abs(r_ba)) / 2
     return (r_ab + r_ba) / 2
+
+
+def finalize_erpac(kind: str, M, amp, phase, ip, ia, nepochs: int):
+    """The event-related phase-amplitude coupling ``kind`` per pair, (phase scale, amplitude scale) and window
+    sample from the sums of Plan.execute_erpac over E = ``nepochs`` epochs: ``M`` complex128 (P, Fp, Fa, T) =
+    sum_e A u, ``amp`` float64 (C, Fa, T, 2) = {sum A, sum A^2} and ``phase`` float64 (C, Fp, 5, T) = the planes
+    sum c, sum s, sum c^2, sum s^2, sum c s, with A the amplitude of channel ia[p] and u = c + i s the unit
+    phasor of channel ip[p].  With r the Pearson correlation over the epochs (_pearson: 0 where a variance is
+    <= 0), r_xc = r(A, c), r_xs = r(A, s) and r_cs = r(c, s):
+      circular       rho = sqrt((r_xc^2 + r_xs^2 - 2 r_xc r_xs r_cs) / (1 - r_cs^2)), the circular-linear
+                     correlation (Berens 2009, circ_corrcl; tensorpac's EventRelatedPac(method='circular'),
+                     Voytek et al. 2013); a radicand below 0 from rounding gives 0, and 1 - r_cs^2 <= 0 gives 0
+                     (the zero-denominator convention of finalize_pac); NaN sums stay NaN
+      circular_pval  exp(-E rho^2 / 2): the chi-square survival function with 2 degrees of freedom at E rho^2
+      mvl, mvl_norm, direct_pac, debiased_pac   finalize_pac's, with the epoch count in the place of the sample
+                     count: one value per window sample
+    float64 (P, Fp, Fa, T).  ``erpac_sum`` returns (M, amp, phase) unchanged.  The two circular kinds need
+    E >= 2, the others E >= 1 (ValueError)."""
+    if kind not in ERPAC_OUTS:
+        raise ValueError(f"out must be one of {', '.join(sorted(ERPAC_OUTS))}; got {kind!r}")
+    if kind == 'erpac_sum':
+        return M, amp, phase
+    E = int(nepochs)
+    need = 2 if kind.startswith('circular') else 1
+    if E < need:
+        raise ValueError(f'{kind} needs at least {need} epoch{"s" if need > 1 else ""}, got {E}')
+    M = np.asarray(M, dtype=np.complex128)
+    amp, phase = np.asarray(amp, dtype=np.float64), np.asarray(phase, dtype=np.float64)
+    if M.ndim != 4 or amp.ndim != 4 or amp.shape[-1] != 2 or phase.ndim != 4 or phase.shape[2] != 5:
+        raise ValueError(f'M must be (pairs, phase scales, amplitude scales, samples), amp (channels, amplitude scales, '
+                         f'samples, 2) and phase (channels, phase scales, 5, samples), got shapes {M.shape}, {amp.shape} '
+                         f'and {phase.shape}')
+    ip, ia = np.asarray(ip, dtype=np.intp), np.asarray(ia, dtype=np.intp)
+    if not kind.startswith('circular'):           # finalize_pac with the sample axis in the place of its epoch axis
+        u = np.empty(phase.shape[:2] + phase.shape[3:], dtype=np.complex128)
+        u.real, u.imag = phase[:, :, 0], phase[:, :, 1]
+        res = finalize_pac(kind, np.moveaxis(M, -1, 0), np.moveaxis(amp, 2, 0), np.moveaxis(u, -1, 0), ip, ia, E)
+        return np.ascontiguousarray(np.moveaxis(res, 0, -1))
+    sa, saa = amp[ia][:, None, :, :, 0], amp[ia][:, None, :, :, 1]              # (P, 1, Fa, T)
+    sc, ss, scc, sss, scs = (phase[ip][:, :, None, k] for k in range(5))         # (P, Fp, 1, T)
+    r_xc = _pearson(M.real, sa, sc, saa, scc, E)
+    r_xs = _pearson(M.imag, sa, ss, saa, sss, E)
+    r_cs = _pearson(scs, sc, ss, scc, sss, E)
+    den = 1. - r_cs * r_cs
+    flat = den <= 0
+    rad = (r_xc * r_xc + r_xs * r_xs - 2. * r_xc * r_xs * r_cs) / np.where(flat, 1., den)
+    rho = np.sqrt(np.where(flat | (rad < 0), 0., rad))
+    return rho if kind == 'circular' else np.exp(-E * rho * rho / 2.)
 
 
 def time_window(n: int, decim: int, window, on_device: bool):
@@ -892,6 +942,34 @@ class Plan:
                                        ('amp', (nep, nchan, nam, 2), np.float64, True),
                                        ('phase', (nep, nchan, nph), np.complex128, True)])
         self._epoch_execute(L.lib().nw_execute_pac, x,
+                            (nep, nchan, _ptr(ip), _ptr(ia), npairs, _ptr(fph), nph, _ptr(fam), nam, t0, t1, step), outs)
+        return out if dev else tuple(outs)
+
+    def execute_erpac(self, x, indices=None, phase=None, amp=None, window=None, step: int = 1, out=None):
+        """Event-related phase-amplitude coupling sums (nw_execute_erpac): x, ``indices``, ``phase``, ``amp``,
+        ``window`` and ``step`` as in execute_pac, the sums taken over the EPOCHS at each of the window's T samples
+        t0, t0 + step, ... < t1.  Returns (M complex128 (P, Fp, Fa, T) = sum_e |y_a| u_p, amp float64
+        (C, Fa, T, 2) = {sum_e |y|, sum_e |y|^2}, phase float64 (C, Fp, 5, T) = the planes sum_e c, s, c^2, s^2, c s
+        of the unit phasor u = c + i s); see finalize_erpac.  Every value is added in epoch order in one fp64
+        accumulator: it does not depend on the lists, the window or the chunks.  numpy arrays: synchronous,
+        ``out`` optional.  Device tensors: asynchronous on the plan stream, ``out`` = (M, amp, phase) required (amp
+        and phase may be None: not formed).  The plan needs max_batch >= C; the accumulators are read and written
+        once per chunk of max_batch // C epochs, so the rate depends on the epochs per chunk."""
+        nep, nchan = _epochs(x)
+        ip, ia = check_pac_indices(indices, nchan)
+        npairs = int(ip.size)
+        fph, fam = check_scales('phase', phase, self.nfreq), check_scales('amp', amp, self.nfreq)
+        nph, nam = int(fph.size), int(fam.size)
+        t0, t1, step = self._window(window, step)
+        count = len(range(t0, t1, step))
+        x = self._epoch_input(x, nep * nchan, out)
+        dev = _is_device_tensor(x)
+        outs = _unpack(out, 3, 'device output must be (M, amp, phase) tensors (amp and phase may be None)' if dev else
+                       'out must be (M, amp, phase) arrays')
+        outs = self._outputs(x, outs, [('M', (npairs, nph, nam, count), np.complex128, False),
+                                       ('amp', (nchan, nam, count, 2), np.float64, True),
+                                       ('phase', (nchan, nph, 5, count), np.float64, True)])
+        self._epoch_execute(L.lib().nw_execute_erpac, x,
                             (nep, nchan, _ptr(ip), _ptr(ia), npairs, _ptr(fph), nph, _ptr(fam), nam, t0, t1, step), outs)
         return out if dev else tuple(outs)
 

@@ -153,6 +153,22 @@ class EpochsWavelet:
                                       amp=np.arange(len(pf), len(pf) + len(af)), out=method, indices=indices,
                                       window=window, decim=decim, average=average)
 
+    # -- event-related phase-amplitude coupling: across the epochs, one time course per pair and cell
+    #    (WaveletBase.erpac_batch) ---------------------------------------------------------------
+    def erpac(self, ch_names, phase_freqs, amp_freqs, method: str = 'circular', indices=None, padding: float = 0.,
+              decim: int = 1):
+        """``method`` (erpac_batch's outs: circular, circular_pval, mvl, mvl_norm, direct_pac, debiased_pac,
+        erpac_sum) between the phase at ``phase_freqs`` and the amplitude at ``amp_freqs`` ACROSS the epochs
+        at every sample, (P, Fp, Fa, N'): when, relative to the event, the coupling appears (tensorpac's
+        EventRelatedPac).  Frequency lists, ``indices``, ``padding`` and ``decim`` as in pac: the samples
+        [k, N - k), k = round(padding * sfreq), are kept."""
+        waves = self._pick(ch_names)
+        window = self._padded(waves.shape[-1], padding)
+        pf, af = list(phase_freqs), list(amp_freqs)
+        return self.wavelet.erpac_batch(waves, pf + af, reuse=False, phase=np.arange(len(pf)),
+                                        amp=np.arange(len(pf), len(pf) + len(af)), out=method, indices=indices,
+                                        window=window, decim=decim)
+
     def pac_bins(self, ch_names, phase_freqs, amp_freqs, method: str = 'mi', nbins: int = 18, indices=None,
                  padding: float = 0., decim: int = 1, average: bool = False):
         """``method`` (pac_bins_batch's outs: mi, hr, pref_phase, bin_amp, bin_sum) from the amplitude at
