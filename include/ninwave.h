@@ -86,7 +86,8 @@ extern "C" {
 #define NW_OUT_ABS   1   /* real    (S, F, N)   base.py:427-443 */
 #define NW_OUT_POWER 2   /* real    (S, F, N)   base.py:409-425 */
 /* Reductions over the nsig signals (EpochsWavelet, mneutils.py:42-71): out is (F, N),
- * summed in signal order in fp64 on the device; (E, F, N) is never materialised. */
+ * summed in signal order in fp64 on the device; (E, F, N) is never materialised.  The sums do
+ * not depend on the plan's max_batch (nw_stats.reduce_path: on either path). */
 #define NW_OUT_POWER_MEAN 3  /* real (F, N), compute dtype: mean_s |y|^2    mneutils.py:42-55 */
 #define NW_OUT_ITC        4  /* real (F, N), compute dtype: |mean_s y/|y||  mneutils.py:57-71;
                                 |y| = 0 gives NaN, as 0/0 does in the reference */

@@ -281,6 +281,9 @@ struct nw_plan {
     // execute_reduce, chirp-z partial sums: the chunk being run continues the signal group of the
     // one before it, whose partial row the kernel adds to (chirp_psum_chunk, nw_shape.h)
     bool chirp_carry = false;
+    // execute_reduce, one-pass partial sums: the chunk being run lies inside a signal group, so the
+    // kernel leaves one fp64 row per signal (the terms) and execute_reduce adds them as a block would
+    bool psum_per_signal = false;
     // chirp-z rows of a tentative length wider than the largest on-chip transform: computed
     // by the rocFFT path on a view of just those rows into d_oscr and scattered to their
     // scales (k_expand_rows), the other rows stay on chip
@@ -674,7 +677,7 @@ int run_one_pass(nw_plan* p, const nw::WDesc& d, const void* xs_dev, int64_t c, 
         p->stats.kernel = nw::fused_psum_kernel_id(p->n, p->dtype, out_kind == OUT_PHSUM);
         return NW_KERNEL_STAGE(p, ST_FUSED, false,
                                nw::fused_power_partials(d, p->dtype, out_kind == OUT_PHSUM, p->d_X.ptr, p->d_wtab.ptr,
-                                                        dst, c, p->stream));
+                                                        dst, c, p->psum_per_signal, p->stream));
     }
     if (out_kind == OUT_XSUM || out_kind == OUT_PLVSUM) {
         p->stats.kernel = NW_K_FUSED_PAIR;
@@ -784,7 +787,7 @@ int run_chunk(nw_plan* p, const nw::WDesc& d, const void* xs_dev, int64_t c, voi
     const bool psum = out_kind == OUT_PSUM || out_kind == OUT_PHSUM;   // fp64 partial rows, one per block of signals
     const size_t row = psum ? (size_t)p->n_out() * sizeof(double) * (out_kind == OUT_PHSUM ? 2 : 1)
                             : (size_t)p->n_out() * (out_kind == NW_OUT_CWT ? 2 : 1) * p->esz;
-    const int64_t crows = psum ? nw::fused_psum_groups(c) : c;
+    const int64_t crows = psum && !p->psum_per_signal ? nw::fused_psum_groups(c) : c;
     NW_TRY(p->d_uout.ensure((size_t)c * p->uniq.U * row));   // crows <= c
     // d_uout is scratch of the CWT's row size: K1 may write it
     NW_TRY(run_chunk_rows(p, d, xs_dev, c, p->d_uout.ptr, out_kind, true));
@@ -838,14 +841,12 @@ int end_reduce(nw_plan* p, bool host) {
 int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, void* out, int out_kind, bool host) {
     const bool phase = is_phase(out_kind);
     const int64_t fn = (int64_t)p->nfreq * p->n_out();
-    const size_t acc_bytes = (size_t)fn * (phase ? 2 : 1) * sizeof(double);
-    NW_TRY(p->d_acc.ensure(acc_bytes));
-    double* const acc = (double*)p->d_acc.ptr;
-    NW_HIP(hipMemsetAsync(acc, 0, acc_bytes, p->stream));
+    const int64_t nacc = phase ? 2 * fn : fn;   // fp64 values of the accumulator (phase sums as 2 fn reals)
+    const size_t acc_bytes = (size_t)nacc * sizeof(double);
     const bool fused = p->form != FORM_ROCFFT;
-    // fp32 reductions at the register-resident fused sizes: the kernel sums |y|^2 (ITC: y / |y|)
-    // over each block of 8 signals in fp64, the accumulator adds the ceil(c / 8) fp64 partials
-    // (the same fp64 additions of the same fp32-derived values, regrouped; with the dedup view
+    // One-pass reductions with analytic rows: the kernel sums |y|^2 (ITC: y / |y|) over each block
+    // of 8 signals in fp64, the accumulator adds the ceil(c / 8) fp64 partials (the same fp64
+    // additions of the same values, grouped by 8 signals; with the dedup view
     // the partials of the distinct rows are expanded like any output row)
     // The chirp-z form (lengths 2n - 1 <= M_max, every row on chip) read-modify-writes its
     // block partial rows instead (no accumulator registers; any kind, fp32 and fp64); its
@@ -861,6 +862,16 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
     const bool psum = (p->form == FORM_ONE_PASS && p->decim == 1 && nw::fused_psum_supported(p->n, p->dtype, d.kind, phase)) ||
                       chirp_psum;
     const int sig_kind = psum ? (phase ? OUT_PHSUM : OUT_PSUM) : (fused && !phase) ? NW_OUT_POWER : NW_OUT_CWT;
+    // One-pass partial sums of a plan whose chunks are shorter than a signal group: the kernel's
+    // accumulators are registers that start at zero, so a chunk cannot carry a group's row on as the
+    // chirp-z kernel does.  Such a chunk leaves one fp64 row per signal (the terms a block adds),
+    // which are added in signal order into the group's row `grp` behind the accumulator, and that
+    // row is added to the accumulator once the group is complete: a block's additions, in its order.
+    const bool per_signal = psum && !chirp_psum && p->max_batch < nw::kPsumGroup && nsig > p->max_batch;
+    NW_TRY(p->d_acc.ensure(per_signal ? 2 * acc_bytes : acc_bytes));
+    double* const acc = (double*)p->d_acc.ptr;
+    double* const grp = acc + nacc;
+    NW_HIP(hipMemsetAsync(acc, 0, per_signal ? 2 * acc_bytes : acc_bytes, p->stream));
     nw_logf(1, "plan %p: %s over %lld signals: %s", (void*)p, out_name(out_kind), (long long)nsig,
             psum ? "fp64 block partial sums inside the transform kernel"
                  : "per-signal rows per chunk, added in signal order in fp64");
@@ -869,30 +880,36 @@ int execute_reduce(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nsig, 
     const int src_kind = psum ? nw::ACC_POWER_REAL
                               : phase ? nw::ACC_PHASE_Y : (fused ? nw::ACC_POWER_REAL : nw::ACC_POWER_Y);
     size_t sb = (size_t)p->max_batch * fn * (phase ? 2 : 1) * p->esz;
-    if (psum) sb = std::max(sb, (size_t)nw::fused_psum_groups(p->max_batch) * fn * (phase ? 2 : 1) * sizeof(double));
+    if (psum) sb = std::max(sb, (size_t)(per_signal ? p->max_batch : nw::fused_psum_groups(p->max_batch)) * acc_bytes);
     void* scratch = nullptr;
     NW_TRY(reduce_scratch(p, sb, &scratch));
-    // The chirp-z partial rows are those of the call's signal groups 0-7, 8-15, ... whatever
-    // max_batch (chirp_psum_chunk), so the sums do not depend on it: a chunk shorter than a group
+    // The partial rows are those of the call's signal groups 0-7, 8-15, ... whatever max_batch
+    // (chirp_psum_chunk), so the sums do not depend on it: a chirp-z chunk shorter than a group
     // carries the group's row on, and the row is added once the group is complete.
     for (int64_t s0 = 0, c = 0; s0 < nsig; s0 += c) {
-        c = chirp_psum ? nw::chirp_psum_chunk(s0, nsig, p->max_batch) : std::min<int64_t>(p->max_batch, nsig - s0);
+        c = psum ? nw::chirp_psum_chunk(s0, nsig, p->max_batch) : std::min<int64_t>(p->max_batch, nsig - s0);
         const void* xs = (const char*)x + (size_t)s0 * p->n * p->esz;
         if (host) {
             NW_TRY(stage_chunk(p, xs, (size_t)c * p->n * p->esz));
             xs = p->d_x.ptr;
         }
         p->chirp_carry = chirp_psum && s0 % nw::kPsumGroup != 0;
+        p->psum_per_signal = per_signal;
         const int rc = run_chunk(p, d, xs, c, scratch, sig_kind, false);
-        p->chirp_carry = false;
+        p->chirp_carry = p->psum_per_signal = false;
         NW_TRY(rc);
         p->stats.chunks++;
-        if (chirp_psum && (s0 + c) % nw::kPsumGroup != 0 && s0 + c < nsig) continue;   // the group goes on
-        const int64_t rows = psum ? nw::fused_psum_groups(c) : c;
+        const bool goes_on = (s0 + c) % nw::kPsumGroup != 0 && s0 + c < nsig;   // the group: its next chunk follows
         // chained: run_chunk ends with a stage
+        if (per_signal)
+            NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, true,
+                                   nw::launch_accumulate(NW_F64, src_kind, scratch, grp, nacc, c, p->stream)));
+        if ((chirp_psum || per_signal) && goes_on) continue;
+        const int64_t rows = per_signal ? 1 : psum ? nw::fused_psum_groups(c) : c;
         NW_TRY(NW_KERNEL_STAGE(p, ST_EPI, true,
-                               nw::launch_accumulate(psum ? NW_F64 : p->dtype, src_kind, scratch, acc,
-                                                     psum && phase ? 2 * fn : fn, rows, p->stream)));
+                               nw::launch_accumulate(psum ? NW_F64 : p->dtype, src_kind, per_signal ? grp : scratch, acc,
+                                                     psum ? nacc : fn, rows, p->stream)));
+        if (per_signal) NW_HIP(hipMemsetAsync(grp, 0, acc_bytes, p->stream));
     }
     const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (out_kind == NW_OUT_POWER_SUM || out_kind == NW_OUT_PHASE_SUM) {

@@ -647,17 +647,19 @@ hipError_t launch_n(const WDesc& d, int out_kind, const void* X, const void* wta
     });
 }
 
+// (group: the signals a block sums into its partial row, kGroup or 1)
 template <typename T, int N, int E, int OUT, int WSH>
-hipError_t launch_psum(const WDesc& d, const void* X, const void* wtab, void* partials, int64_t nsig, hipStream_t s) {
+hipError_t launch_psum(const WDesc& d, const void* X, const void* wtab, void* partials, int64_t nsig, int group,
+                       hipStream_t s) {
     void* tw = nullptr;
     hipError_t e = twiddles_for(N, kDtypeOf<T>, &tw);
     if (e != hipSuccess) return e;
     FusedShape sh{};
-    if (!shape_for(E, kGroup, kTileFT<T>, kTileGT<T>, nsig, d.nfreq, &sh)) return hipErrorInvalidConfiguration;
+    if (!shape_for(E, group, kTileFT<T>, kTileGT<T>, nsig, d.nfreq, &sh)) return hipErrorInvalidConfiguration;
     const int* wnz = wtab_wnz(wtab, N, d.nfreq, sizeof(T), true);
     auto go = [&](auto kernel, int lds) {
         return nw_launch_lds(kernel, (unsigned)sh.blocks, N / E, lds, s, d, reinterpret_cast<const cplx<T>*>(X), wtab,
-                             partials, reinterpret_cast<const C2<T>*>(tw), nsig, kGroup, (int)sh.nsg_pad, wnz,
+                             partials, reinterpret_cast<const C2<T>*>(tw), nsig, group, (int)sh.nsg_pad, wnz,
                              sh.tile_g);
     };
     // power partials on the signal-pair kernel: the same values as its power output
@@ -752,15 +754,16 @@ int fused_psum_kernel_id(int64_t n, int dtype, bool phase) {
 }
 
 hipError_t fused_power_partials(const WDesc& d, int dtype, bool phase, const void* X, const void* wtab,
-                                void* partials, int64_t nsig, hipStream_t s) {
+                                void* partials, int64_t nsig, bool per_signal, hipStream_t s) {
+    const int group = per_signal ? 1 : kGroup;
     return for_fused_size(d.n, dtype, hipErrorNotSupported, [&]<typename T, int N, int E>(FusedSize<T, N, E>) {
         if constexpr (kPhSumOK<T, N, E>) {
             constexpr int PE = kPsE<T, E, true>;
-            if (phase) return launch_psum<T, N, PE, kOutPhSum, kPsShift<E, PE>>(d, X, wtab, partials, nsig, s);
+            if (phase) return launch_psum<T, N, PE, kOutPhSum, kPsShift<E, PE>>(d, X, wtab, partials, nsig, group, s);
         }
         if constexpr (kPSumOK<T, N, E>) {
             constexpr int PE = kPsE<T, E, false>;
-            if (!phase) return launch_psum<T, N, PE, kOutPSum, kPsShift<E, PE>>(d, X, wtab, partials, nsig, s);
+            if (!phase) return launch_psum<T, N, PE, kOutPSum, kPsShift<E, PE>>(d, X, wtab, partials, nsig, group, s);
         }
         return hipErrorNotSupported;
     });
@@ -774,10 +777,10 @@ hipError_t fused_pair_partials(const WDesc& d, int dtype, bool plv, const void* 
     return for_fused_size(d.n, dtype, hipErrorNotSupported, [&]<typename T, int N, int E>(FusedSize<T, N, E>) {
         if constexpr (kPairMode<T, E, true>) {
             if constexpr (kPairXSumOK<N>) {
-                if (!plv) return launch_psum<T, N, E, kOutXSum, 0>(d, X, wtab, partials, nsig, s);
+                if (!plv) return launch_psum<T, N, E, kOutXSum, 0>(d, X, wtab, partials, nsig, kGroup, s);
             }
             if constexpr (kPairPlvSumOK<N>) {
-                if (plv) return launch_psum<T, N, E, kOutPlvSum, 0>(d, X, wtab, partials, nsig, s);
+                if (plv) return launch_psum<T, N, E, kOutPlvSum, 0>(d, X, wtab, partials, nsig, kGroup, s);
             }
         }
         return hipErrorNotSupported;

@@ -352,7 +352,8 @@ hipError_t launch_fused_decim(const WDesc& d, int dtype, int out_kind, int decim
 // or with phase of y / |y|; one
 // (groups, F, n) row of fp64 (phase: complex fp64) per (group, scale);
 // groups = fused_psum_groups(nsig)
-// (kPsumGroup signals per row, nw_shape.h)
+// (kPsumGroup signals per row, nw_shape.h; per_signal: one row per signal -- the terms a block
+// would add, for a chunk that lies inside a signal group: execute_reduce adds them in its place)
 
 // W support for the pruned pass 0 / row pass (wsupport_kernel, kmax_kernel): the last bin
 // whose |W| exceeds kTailRel x the row's max |W|.  The bins past it (the far tail of a Morse
@@ -372,7 +373,7 @@ bool fused_psum_supported(int64_t n, int dtype, int kind, bool phase);
 int64_t fused_psum_groups(int64_t nsig);
 int fused_psum_kernel_id(int64_t n, int dtype, bool phase);   // NW_K_FUSED or NW_K_FUSED_PAIR
 hipError_t fused_power_partials(const WDesc& d, int dtype, bool phase, const void* X, const void* wtab,
-                                void* partials, int64_t nsig, hipStream_t s);
+                                void* partials, int64_t nsig, bool per_signal, hipStream_t s);
 // cross-channel partials of nsig interleaved signals a0, b0, a1, ... (nw_execute_pair; where
 // pair_partials_supported): (fused_psum_groups(nsig), F, n, 4) fp64 {Re, Im of y_a conj(y_b),
 // |y_a|^2, |y_b|^2} summed over each block's pairs in pair order, or with plv (.., 2) the

@@ -763,7 +763,9 @@ constexpr bool chirp_psum_ok(int dtype, bool phase, const int64_t* counts) {
 // kPsumGroup g .. kPsumGroup g + kPsumGroup - 1 of the whole call: a chunk is whole groups (the
 // call's last one ragged) or, where max_batch is shorter than a group, lies inside one group,
 // whose partial row the next chunk carries on (s0 % kPsumGroup != 0) and which is added once
-// complete.
+// complete.  The one-pass partial sums take the same chunks (execute_reduce, nw_api.cpp): their
+// kernels cannot carry a row on, so a chunk inside a group leaves its signals' terms and the host
+// path adds them in the block's order.
 constexpr int64_t chirp_psum_chunk(int64_t s0, int64_t nsig, int64_t max_batch) {
     const int64_t left = nsig - s0, in_group = s0 % kPsumGroup;
     if (in_group == 0 && left <= max_batch) return left;

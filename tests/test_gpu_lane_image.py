@@ -1,8 +1,11 @@
 """GPU parity of the fp32 n = 16384 one-pass kernels, whose two LDS exchanges run on the
 lane-addressed images (nw_shape.h, lane_image; ds_write_addtid_b32 stores).
 
-fp32, n = 16384, 9 signals: one block of 8 signals (the next signal's X by LDS-DMA into the image
-region) and one block with a single signal.  Morse scales 2, 60, 120, 170, 200, 230, 256 Hz at
+fp32, n = 16384, 9 signals and 9 scales: the output kernels run blocks of 2, 2, 2, 2 and 1 signals
+(group_filling, nw_shape.h, halves the block of a launch this small; the next signal's X by LDS-DMA
+into the image region over one signal boundary), the partial-sum kernel behind power_mean a block
+of 8 and a block of one.  Blocks of 8 of the output kernels: tests/test_gpu_fused_rows.py,
+tests/test_gpu_chunk_parity.py.  Morse scales 2, 60, 120, 170, 200, 230, 256 Hz at
 1 kHz run the pass-0 variants 4, 8, 12, 16 and 20; 320 and 450 Hz add 24 and 32 (rows that read
 mirrored bins), so all seven variants of the kernel run.  Which variant a row runs is read off the
 plan's own W rows by the rule of tests/fused_variants.py (compared with nw_shape.h by

@@ -2,9 +2,12 @@
 inline asm (NW_LDS_ASM_READS, nw_shape.h: the 1 -> 2 image's pairs and the pass-1 twiddle table).
 
 Morse scales 2, 60, 120, 170, 200, 230, 256, 320 and 450 Hz at 1 kHz run all seven pass-0 variants
-(asserted with tests/fused_variants.py), whose pruned outputs feed the table's twiddles.  9
-signals are a full block of 8 (the loop-carried DMA and its counted wait) and a block of one; 2
-signals a block of two.  cwt, |y|, |y|^2 and power_mean against oracle.nw_oracle at the bounds of
+(asserted with tests/fused_variants.py), whose pruned outputs feed the table's twiddles.  With
+9 signals and 9 scales the output kernels run blocks of 2, 2, 2, 2 and 1 signals (group_filling,
+nw_shape.h, halves the block of a launch this small: the loop-carried DMA and its counted wait
+over one signal boundary), 2 signals a block of two; only the partial-sum kernel behind power_mean
+keeps a block of 8 and a block of one.  Blocks of 8 of the output kernels:
+tests/test_gpu_fused_rows.py, tests/test_gpu_chunk_parity.py.  cwt, |y|, |y|^2 and power_mean against oracle.nw_oracle at the bounds of
 tests/test_gpu_parity.py (1e-5 of max; 2e-5 for |y|^2 and power_mean).
 
 A complex-table-row wavelet (the `paul` plugin of tests/plugins.py; 3 scales x 3 signals, cwt and
