@@ -171,6 +171,9 @@ typedef struct nw_stats {
 #define NW_REDUCE_ERPAC 8      /* nw_execute_erpac: per-signal rows per chunk, every (pair, phase
                                   scale, amplitude scale, window sample) added in epoch order by
                                   nw_erpac_kernel                                               */
+#define NW_REDUCE_PAC_SURR 9   /* nw_execute_pac_surr: per-signal rows per chunk, staged once as unit
+                                  phasors and magnitudes, every (epoch, pair, phase scale, amplitude
+                                  scale) summed once per lag by nw_pac_surr_kernel              */
 
 /* nw_stats.kernel: which kernel wrote the output rows (the dominant kernel of a step) */
 #define NW_K_NONE        0
@@ -411,6 +414,46 @@ int nw_execute_pac_bins(nw_plan* plan, const void* x, int64_t nepochs, int32_t n
                         const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam,
                         int64_t t0, int64_t t1, int64_t step, int32_t nbins,
                         void* out_sum, void* out_count, int mem);
+
+/* Time-lag surrogate statistics of nw_execute_pac's coupling (Canolty et al. 2006; tensorpac's surrogate
+ * "swap amplitude time blocks"): the sum M with the amplitude cut at a sample and its two blocks swapped --
+ * a circular shift inside the window -- once per listed lag, and per cell the statistics of the surrogate
+ * values from which a z-score or a p-value of the observed one is formed.  All arguments, checks, chunking,
+ * mem, engine forms, decimated plans, the window (t0, t1, step) and its sample count T are nw_execute_pac's.
+ * lags: HOST array [nlags] of shifts in WINDOW samples, any list (repeats, 0); every lag must lie in [0, T) and
+ * nlags in [0, NW_PAC_MAX_LAGS], anything else is NW_E_INVALID and the message names the value (so T = 0
+ * requires nlags = 0).  centre: NW_PAC_SURR_PLAIN or NW_PAC_SURR_DEBIASED.  In fp64, with A and u as
+ * nw_execute_pac defines them, indexed by the window index j = 0 .. T - 1:
+ *   M_l  = sum_j A[(j + l) mod T] u[j]      every product rounded on its own, the sum in
+ *                                           nw_execute_conn_time's SUMMATION ORDER on the term index j
+ *   Mc_l = M_l                              (NW_PAC_SURR_PLAIN)
+ *   Mc_l = M_l - D,  D = ((P.re S_A) / T, (P.im S_A) / T),  P = sum u of (ip[p], fph[i]),  S_A = sum A of
+ *          (ia[p], fam[k]), each operation rounded on its own      (NW_PAC_SURR_DEBIASED: the centring of
+ *          debiased_pac; the device forms P and S_A whether or not out_phase / out_amp are given)
+ *   q_l  = Mc.re Mc.re + Mc.im Mc.im  (two products and one sum, each rounded),  h_l = sqrt(q_l) correctly
+ *          rounded;  q_0 is that of the lag 0
+ * so M_0 is bit-identical to out_m, and out_m, out_amp and out_phase are bit-identical to nw_execute_pac's.
+ * The normalisations of mvl_norm and direct_pac do not change under a circular shift: one set of statistics
+ * serves every measure of the same centring.  Outputs, epoch-major:
+ *   out_m, out_amp, out_phase   nw_execute_pac's
+ *   out_stat float64    (nepochs, npairs, nph, nam, 4)     = {sum_s h_s, sum_s q_s, #{s : q_s >= q_0}, max_s q_s},
+ *            s over the list in list order; each sum starts at +0.0; the max starts at +0.0 and is replaced
+ *            where q_s > max; NaN compares false                                   (NULL only if out_all is not)
+ *   out_all  complex128 (nepochs, npairs, nph, nam, nlags) = M_{lags[s]} (M, not Mc)               (may be NULL)
+ * A value depends only on its rows, the window and the lag list (out_all: on its own lag): not on the pair or
+ * scale lists, their tiling or the chunks.  A sample with |y_p| = 0 makes that cell's sums NaN and its count
+ * 0.  The regions and the staged phasors and magnitudes of one chunk (ec C (2 nph + nam) T fp64 values) live
+ * in the plan (nw_stats.device_bytes); NW_E_NOMEM if they do not fit.  nw_stats.reduce_path:
+ * NW_REDUCE_PAC_SURR. */
+#define NW_PAC_MAX_LAGS 4096
+#define NW_PAC_SURR_PLAIN 0
+#define NW_PAC_SURR_DEBIASED 1
+int nw_execute_pac_surr(nw_plan* plan, const void* x, int64_t nepochs, int32_t nchan,
+                        const int32_t* ip, const int32_t* ia, int64_t npairs,
+                        const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam,
+                        int64_t t0, int64_t t1, int64_t step,
+                        const int64_t* lags, int32_t nlags, int centre,
+                        void* out_m, void* out_amp, void* out_phase, void* out_stat, void* out_all, int mem);
 
 /* Event-related phase-amplitude coupling (ERPAC; Voytek et al. 2013): nw_execute_pac's quantities
  * summed over the EPOCHS at every sample of a window instead of over the samples of every epoch -- what

@@ -13,11 +13,11 @@ from .base import WaveletBase, WaveletMode, pad_to, interpolate_alias
 from .wavelets import Morse, MorseMNE, Morlet, Haar, MexicanHat, Shannon
 from .mneutils import EpochsWavelet
 from .baseline import Baseline, baseline_of
-from .engine import Plan, execute_multi, execute_multi_device, finalize_lag, finalize_conn_time, finalize_pac, finalize_env
+from .engine import Plan, execute_multi, execute_multi_device, finalize_lag, finalize_conn_time, finalize_pac, finalize_pac_surr, finalize_env
 from .engine import finalize_pac_bins, finalize_erpac
 from . import _lib
 
 __all__ = ['Baseline', 'baseline_of', 'WaveletBase', 'WaveletMode', 'Morse', 'MorseMNE', 'Morlet', 'Haar', 'MexicanHat',
-           'Shannon', 'EpochsWavelet', 'Plan', 'execute_multi', 'execute_multi_device', 'finalize_lag', 'finalize_conn_time', 'finalize_pac', 'finalize_pac_bins', 'finalize_erpac', 'finalize_env', 'pad_to',
+           'Shannon', 'EpochsWavelet', 'Plan', 'execute_multi', 'execute_multi_device', 'finalize_lag', 'finalize_conn_time', 'finalize_pac', 'finalize_pac_surr', 'finalize_pac_bins', 'finalize_erpac', 'finalize_env', 'pad_to',
            'interpolate_alias']
 __version__ = '0.1.0'

@@ -47,6 +47,9 @@ NW_REDUCE_PAC = 5                                               # ... of nw_exec
 NW_REDUCE_ENV = 6                                               # ... of nw_execute_env_time
 NW_REDUCE_PAC_BINS = 7                                          # ... of nw_execute_pac_bins
 NW_REDUCE_ERPAC = 8                                             # ... of nw_execute_erpac
+NW_REDUCE_PAC_SURR = 9                                          # ... of nw_execute_pac_surr
+NW_PAC_MAX_LAGS = 4096                                          # nw_execute_pac_surr: at most this many lags
+NW_PAC_SURR_PLAIN, NW_PAC_SURR_DEBIASED = 0, 1                  # nw_execute_pac_surr's centre
 NW_PAC_MAX_BINS = 36                                            # nw_execute_pac_bins: nbins even, 2 .. 36
 NW_ENV_PLAIN, NW_ENV_ORTH = 0, 1                                # nw_execute_env_time's env_kind
 NW_MEM_HOST, NW_MEM_DEVICE = 0, 1
@@ -110,6 +113,9 @@ SIGNATURES = [
                                            ctypes.c_int, ctypes.c_int]),
     ('nw_execute_pac', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _P, ctypes.c_int32, _P, ctypes.c_int32,
                                       _I64, _I64, _I64, _P, _P, _P, ctypes.c_int]),
+    ('nw_execute_pac_surr', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _P, ctypes.c_int32, _P,
+                                           ctypes.c_int32, _I64, _I64, _I64, _P, ctypes.c_int32, ctypes.c_int, _P, _P, _P,
+                                           _P, _P, ctypes.c_int]),
     ('nw_execute_erpac', ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P, _I64, _P, ctypes.c_int32, _P, ctypes.c_int32,
                                         _I64, _I64, _I64, _P, _P, _P, ctypes.c_int]),
     ('nw_pac_bin_edges', ctypes.c_int, [ctypes.c_int32, _P]),

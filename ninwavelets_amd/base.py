@@ -26,10 +26,10 @@ import numpy as np
 from scipy.fftpack import fft, ifft
 
 from . import _lib as L
-from .engine import (CONN_OUTS, ENV_OUTS, ERPAC_OUTS, LAG_OUTS, PAC_BIN_OUTS, PAC_OUTS, PAIR_OUTS, REDUCTIONS, Plan, check_decim,
-                     check_indices, check_nbins, check_pac_indices, check_scales, execute_multi, finalize_conn,
-                     finalize_conn_time, finalize_env, finalize_erpac, finalize_lag, finalize_pac, finalize_pac_bins, finalize_pair,
-                     np_dtype, time_window)
+from .engine import (CONN_OUTS, ENV_OUTS, ERPAC_OUTS, LAG_OUTS, PAC_BIN_OUTS, PAC_OUTS, PAC_SURR_STATS, PAIR_OUTS, REDUCTIONS,
+                     Plan, check_decim, check_indices, check_lags, check_nbins, check_pac_indices, check_scales, draw_lags,
+                     execute_multi, finalize_conn, finalize_conn_time, finalize_env, finalize_erpac, finalize_lag, finalize_pac,
+                     finalize_pac_bins, finalize_pac_surr, finalize_pair, np_dtype, time_window)
 from .engine import make_wavelets as _make_wavelets_dev
 
 # Device working-set budget per plan chunk (bytes); signals are streamed through it.
@@ -657,6 +657,48 @@ class WaveletBase:
                                window, decim, average, 0 if out == 'pac_sum' else 1,
                                lambda plan, *a: plan.execute_pac(*a),
                                lambda sums, *a: finalize_pac(out, *sums, *a), scales=(phase, amp))
+
+    def pac_surrogates_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, phase=None, amp=None,
+                             out: str = 'direct_pac', stat: str = 'zscore', n_surrogates: int = 200, lags=None,
+                             min_lag=None, seed=None, indices=None, window=None, decim: int = 1, average: bool = False):
+        """Whether pac_batch's coupling is above chance: time-lag surrogates (Canolty et al. 2006; tensorpac's
+        "swap amplitude time blocks").  The amplitude of every epoch is cut at a random sample of the window and
+        its two blocks are swapped -- a circular shift -- which keeps both signals' spectra and breaks their
+        timing; the measure ``out`` (mvl, mvl_norm, direct_pac, debiased_pac) is formed again for every shift, all
+        on the device from ONE transform per epoch and channel.  ``stat`` (engine.finalize_pac_surr): ``zscore``
+        (the observed value against the surrogates' mean and sd), ``pvalue`` ((1 + #{surrogate >= observed}) /
+        (1 + S)), ``surr_mean``, ``surr_std``, ``surr_max`` (in the measure's units), each (E, P, Fp, Fa) float64;
+        ``surrogates``: every surrogate value, (E, P, Fp, Fa, S); ``surr_sum``: the sums (M, amp, phase, stat, None).
+        ``lags``: the shifts in window samples, integers in [0, T) (at most NW_PAC_MAX_LAGS; the same list for
+        every epoch, pair and cell); None: default_rng(``seed``).integers(min_lag, T - min_lag + 1,
+        ``n_surrogates``) with ``min_lag`` = max(1, T // 10) unless given (ValueError if T < 2 min_lag).
+        ``phase``, ``amp``, ``indices``, ``window`` and ``decim`` as in pac_batch (T: the window's decimated
+        samples); ``average=True``: the mean over the epochs of zscore, surr_mean or surr_std, (P, Fp, Fa)
+        (ValueError for the other kinds).  zscore and surr_std need at least 2 surrogates.  A strictly periodic
+        driver keeps its coupling under a shift: its z is small by construction.  Cache semantics, device choice
+        and plan eviction as in connectivity_batch."""
+        kinds = dict.fromkeys(sorted(PAC_OUTS - {'pac_sum'}))
+        if stat not in PAC_SURR_STATS:
+            raise ValueError(f"stat must be one of {', '.join(sorted(PAC_SURR_STATS))}; got {stat!r}")
+        if average and stat not in ('zscore', 'surr_mean', 'surr_std'):
+            raise ValueError(f'average=True takes zscore, surr_mean or surr_std, not {stat!r}')
+        if out not in kinds:
+            raise ValueError(f"out must be one of {', '.join(kinds)}; got {out!r}")
+        _, _, _, n = _epochs(waves)
+        T = time_window(n, check_decim(decim), window, False)[3]
+        if T < 1:
+            raise ValueError(f'{stat} needs at least 1 sample in the window, got {T}')
+        lags = draw_lags(T, n_surrogates, min_lag, seed) if lags is None else check_lags(lags, T)
+        need = 2 if stat in ('zscore', 'surr_std') else 0 if stat == 'surr_sum' else 1
+        if lags.size < need:
+            raise ValueError(f'{stat} needs at least {need} surrogate{"s" if need > 1 else ""}, got {lags.size}')
+        centre = 'debiased' if out == 'debiased_pac' else 'plain'
+        keep = stat == 'surrogates'
+        return self._time_sums(waves, freqs, reuse, out, kinds, check_pac_indices, indices, window, decim, average, 1,
+                               lambda plan, *a: plan.execute_pac_surr(a[0], lags, *a[1:], centre=centre, keep_all=keep),
+                               lambda sums, ip, ia, count: finalize_pac_surr(out, stat, *sums[:4], sums[4] if keep else None,
+                                                                             ip, ia, count, lags.size),
+                               scales=(phase, amp))
 
     def erpac_batch(self, waves: np.ndarray, freqs=None, reuse: bool = True, phase=None, amp=None,
                     out: str = 'circular', indices=None, window=None, decim: int = 1):

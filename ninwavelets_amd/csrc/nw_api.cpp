@@ -271,6 +271,8 @@ struct nw_plan {
                                      // complex (npairs, F, n) | (nchan, F, n) | the pair tiles
     std::vector<nw::ConnTile> conn_tiles;   // nw_execute_conn: the last call's tiles (the upload's source)
     std::vector<int32_t> pac_lists;         // nw_execute_pac, _pac_bins, _erpac: the last call's ip | ia | fph | fam (likewise)
+    DevBuf d_pstage;                 // nw_execute_pac_surr: one chunk's staged unit phasors and magnitudes, then its
+                                     // per-channel sums where the caller gave no buffer for them
     // nw_execute_multi_device reductions: this device's fp64 partial sums, and (device 0's
     // plan) the peer-copy landing buffer; kept across calls (a hipFree per call would
     // synchronise the device on every epoch-loop iteration)
@@ -311,7 +313,7 @@ struct nw_plan {
     size_t device_bytes() const {
         size_t sum = 0;
         for (const DevBuf* b : {&d_x, &d_X, &d_table, &d_uout, &d_Y, &d_out, &d_acc, &d_part, &d_gather, &d_wtab,
-                                &d_oscr, &d_scratch, &work})
+                                &d_oscr, &d_scratch, &d_pstage, &work})
             sum += b->bytes;
         return sum;
     }
@@ -982,7 +984,7 @@ int execute_pair(nw_plan* p, const nw::WDesc& d, const void* xa, const void* xb,
     return end_reduce(p, host);
 }
 
-// The epoch-chunk reductions (nw_execute_conn, _conn_time, _env_time, _pac, _pac_bins, _erpac) share one layout of d_acc
+// The epoch-chunk reductions (nw_execute_conn, _conn_time, _env_time, _pac, _pac_surr, _pac_bins, _erpac) share one layout of d_acc
 // and one loop.  d_acc holds the call's fp64 output regions one after the other and then, 16-aligned,
 // one auxiliary blob (tile descriptors or index lists) that is built and uploaded once per call.
 struct SumRegion {
@@ -1194,6 +1196,75 @@ int execute_pac(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, 
                                nw::launch_pac(p->dtype, rows, r[0].at(e0), r[1].at(e0), r[2].at(e0), d_ip, d_ia, d_fph,
                                               d_fam, ec, nchan, p->nfreq, p->n_out(), npairs, nph, nam, t0, count, step,
                                               xcd, p->stream));
+    });
+}
+
+// Time-lag surrogates of the coupling (nw_execute_pac_surr): execute_pac's regions, then the statistics and, where
+// asked, every surrogate sum; the blob is the pair and scale lists, padded to 16 bytes, and then the lags.  Per
+// chunk, one kernel stage: nw_pac_rows_kernel's per-channel sums (into the caller's regions, or into the tail of
+// d_pstage: the debiased centring reads them), nw_pac_stage_kernel's unit phasors and magnitudes of the chunk into
+// d_pstage, and nw_pac_surr_kernel, which writes the chunk's epochs' slice of M, the statistics and the surrogates.
+int execute_pac_surr(nw_plan* p, const nw::WDesc& d, const void* x, int64_t nepochs, int nchan, const int32_t* ip,
+                     const int32_t* ia, int64_t npairs, const int32_t* fph, int nph, const int32_t* fam, int nam,
+                     int64_t t0, int64_t t1, int64_t step, const int64_t* lags, int nlags, int centre, void* out_m,
+                     void* out_amp, void* out_phase, void* out_stat, void* out_all, bool host) {
+    const int64_t count = nw::conn_time_count(t0, t1, step);
+    const size_t cells = (size_t)npairs * nph * nam;                               // of one epoch
+    const size_t amp_epoch = (size_t)nchan * nam * 2 * sizeof(double);
+    const size_t phase_epoch = (size_t)nchan * nph * 2 * sizeof(double);
+    const size_t stat_epoch = cells * 4 * sizeof(double), all_epoch = cells * nlags * 2 * sizeof(double);
+    SumRegion r[5] = {{out_m, (size_t)nepochs * cells * 2 * sizeof(double), cells * 2 * sizeof(double)},
+                      {out_amp, out_amp ? (size_t)nepochs * amp_epoch : 0, amp_epoch},
+                      {out_phase, out_phase ? (size_t)nepochs * phase_epoch : 0, phase_epoch},
+                      {out_stat, out_stat ? (size_t)nepochs * stat_epoch : 0, stat_epoch},
+                      {out_all, out_all ? (size_t)nepochs * all_epoch : 0, all_epoch}};
+    std::vector<int32_t>& lists = p->pac_lists;                   // ip, ia, fph, fam, padding, the lags
+    lists.clear();
+    lists.insert(lists.end(), ip, ip + npairs);
+    lists.insert(lists.end(), ia, ia + npairs);
+    lists.insert(lists.end(), fph, fph + nph);
+    lists.insert(lists.end(), fam, fam + nam);
+    lists.resize((lists.size() + 3) / 4 * 4, 0);
+    const size_t lags_at = lists.size();
+    lists.resize(lags_at + (size_t)nlags * 2);
+    if (nlags) std::memcpy(lists.data() + lags_at, lags, (size_t)nlags * sizeof(int64_t));
+    const std::string what = "nw_execute_pac_surr: the fp64 sums of " + std::to_string(nepochs) + " epochs, " +
+                             std::to_string(npairs) + " pairs, " + std::to_string(nph) + " x " + std::to_string(nam) +
+                             " scales and " + std::to_string(nlags) + " lags";
+    const char* d_lists = nullptr;
+    NW_TRY(place_sums(p, r, 5, lists.data(), lists.size() * sizeof(int32_t), &d_lists, false, what));
+    // one chunk's staged values and, after them, its per-channel sums
+    const int64_t per = std::min<int64_t>(p->max_batch / nchan, std::max<int64_t>(nepochs, 1));
+    const size_t stage_bytes = (size_t)nw::pac_surr_stage_doubles(per * nchan, nph, nam, count) * sizeof(double);
+    const int got = p->d_pstage.ensure(stage_bytes + (size_t)per * (amp_epoch + phase_epoch) + 16);
+    if (got != NW_OK && got != NW_E_NOMEM) return got;
+    if (got == NW_E_NOMEM)
+        return fail(NW_E_NOMEM, what + ": the staged unit phasors and magnitudes of a chunk of " + std::to_string(per) +
+                                    " epochs need " + std::to_string(stage_bytes) + " bytes of device memory: " + g_last_error);
+    char* const spare_amp = p->d_pstage.at(stage_bytes);
+    char* const spare_phase = spare_amp + (size_t)per * amp_epoch;
+    const int32_t* const d_ip = (const int32_t*)d_lists;
+    const int32_t* const d_ia = d_ip + npairs;
+    const int32_t* const d_fph = d_ia + npairs;
+    const int32_t* const d_fam = d_fph + nph;
+    const int64_t* const d_lags = (const int64_t*)((const int32_t*)d_lists + lags_at);
+    const bool xcd = xcd_order();
+    nw_logf(1, "plan %p: pac surrogate sums (%s), %lld epochs x %d channels, %lld pairs, %d phase x %d amplitude scales "
+               "in %lld tiles, %d lags%s (%lld epochs per chunk, %lld B staged), window [%lld, %lld) step %lld of %lld "
+               "samples, %s buffers: per-signal rows per chunk, staged once as unit phasors and magnitudes, every "
+               "(epoch, pair, phase scale, amplitude scale) summed over its %lld samples once per lag in fp64 in lane order",
+            (void*)p, centre == NW_PAC_SURR_DEBIASED ? "debiased" : "plain", (long long)nepochs, nchan,
+            (long long)npairs, nph, nam, (long long)nw::pac_tiles(nph, nam), nlags, out_all ? ", every sum kept" : "",
+            (long long)(p->max_batch / nchan), (long long)stage_bytes, (long long)t0, (long long)t1, (long long)step,
+            (long long)p->n_out(), host ? "host" : "device", (long long)count);
+    p->stats.reduce_path = NW_REDUCE_PAC_SURR;
+    return run_epoch_chunks(p, d, x, nepochs, nchan, r, 5, host, [&](int64_t e0, int64_t ec, void* rows) -> int {
+        return NW_KERNEL_STAGE(p, ST_EPI, true,
+                               nw::launch_pac_surr(p->dtype, rows, p->d_pstage.ptr, r[0].at(e0),
+                                                   r[1].dev ? r[1].at(e0) : spare_amp,
+                                                   r[2].dev ? r[2].at(e0) : spare_phase, r[3].at(e0), r[4].at(e0), d_ip,
+                                                   d_ia, d_fph, d_fam, d_lags, nlags, centre, ec, nchan, p->nfreq,
+                                                   p->n_out(), npairs, nph, nam, t0, count, step, xcd, p->stream));
     });
 }
 
@@ -1930,6 +2001,43 @@ int nw_execute_pac(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, co
     NW_TRY(begin_execute(p, &d));
     NW_TRY(execute_pac(p, d, x, nepochs, nchan, ip, ia, npairs, fph, nph, fam, nam, t0, t1, step, out_m, out_amp,
                        out_phase, mem == NW_MEM_HOST));
+    return dcheck_collect(p->stream);
+}
+
+int nw_execute_pac_surr(nw_plan* p, const void* x, int64_t nepochs, int32_t nchan, const int32_t* ip, const int32_t* ia,
+                        int64_t npairs, const int32_t* fph, int32_t nph, const int32_t* fam, int32_t nam, int64_t t0,
+                        int64_t t1, int64_t step, const int64_t* lags, int32_t nlags, int centre, void* out_m,
+                        void* out_amp, void* out_phase, void* out_stat, void* out_all, int mem) {
+    const char* const who = "nw_execute_pac_surr";
+    const bool cells = npairs > 0 && nepochs > 0 && nph > 0 && nam > 0;
+    NW_TRY(check_epoch_call(who, p, !p || (!x && nepochs > 0) || (!out_m && cells) || (!out_stat && !out_all) ||
+                                        (!lags && nlags > 0),
+                            centre != NW_PAC_SURR_PLAIN && centre != NW_PAC_SURR_DEBIASED
+                                ? "centre must be NW_PAC_SURR_PLAIN or NW_PAC_SURR_DEBIASED" : nullptr,
+                            mem, nepochs, nchan, ip, ia, npairs));
+    NW_TRY(check_scale_lists(who, p, fph, nph, fam, nam));
+    NW_TRY(check_chunk(who, p, nchan));
+    NW_TRY(check_window(who, p->n_out(), t0, t1, step));
+    const int64_t count = nw::conn_time_count(t0, t1, step);
+    if (nlags < 0 || nlags > NW_PAC_MAX_LAGS)
+        return fail(NW_E_INVALID, std::string(who) + ": nlags (" + std::to_string(nlags) + ") must lie in [0, " +
+                                      std::to_string(NW_PAC_MAX_LAGS) + "]");
+    for (int32_t s = 0; s < nlags; ++s)
+        if (lags[s] < 0 || lags[s] >= count)
+            return fail(NW_E_INVALID, std::string(who) + ": lag " + std::to_string(s) + " = " + std::to_string(lags[s]) +
+                                          " is outside [0, " + std::to_string(count) + "), the window's samples");
+    // the grids of one chunk's launches (block indices are 32-bit)
+    const int64_t per = std::max<int64_t>(p->max_batch / nchan, 1);
+    const int64_t blocks = nw::pac_blocks(per, npairs, nw::pac_tiles(nph, nam), true);
+    const int64_t stage_blocks = nw::pac_surr_stage_blocks(per * nchan * ((int64_t)nph + nam), count);
+    if (blocks < 0 || blocks > 0x7fffffff || stage_blocks > 0x7fffffff)
+        return fail(NW_E_INVALID, std::string(who) + ": " + std::to_string(npairs) + " pairs x " + std::to_string(nph) + " x " +
+                                      std::to_string(nam) + " scales per chunk need more than 2^31 - 1 blocks");
+    DeviceGuard guard(p->device);
+    nw::WDesc d;
+    NW_TRY(begin_execute(p, &d));
+    NW_TRY(execute_pac_surr(p, d, x, nepochs, nchan, ip, ia, npairs, fph, nph, fam, nam, t0, t1, step, lags, nlags, centre,
+                            out_m, out_amp, out_phase, out_stat, out_all, mem == NW_MEM_HOST));
     return dcheck_collect(p->stream);
 }
 

@@ -275,6 +275,15 @@ hipError_t launch_pac(int dtype, const void* src, void* m, void* amp, void* phas
                       const int32_t* fph, const int32_t* fam, int64_t ec, int nchan, int nfreq, int64_t n_out,
                       int64_t npairs, int nph, int nam, int64_t t0, int64_t count, int64_t step, bool xcd,
                       hipStream_t s);
+// time-lag surrogates of the coupling (nw_pac_surr.hip): src, the lists and the window as launch_pac; amp and
+// phase (never null: the caller's regions or plan scratch) by nw_pac_rows_kernel, then the chunk's listed rows
+// staged once in `stage` (pac_surr_stage_doubles fp64 values) and m (ec, npairs, nph, nam) = M_0, stat (.., 4) and
+// all (.., nlags) = M_{lags[s]} (stat or all null: not formed) by nw_pac_surr_kernel.  lags: device array.
+hipError_t launch_pac_surr(int dtype, const void* src, void* stage, void* m, void* amp, void* phase, void* stat, void* all,
+                           const int32_t* ip, const int32_t* ia, const int32_t* fph, const int32_t* fam,
+                           const int64_t* lags, int nlags, int centre, int64_t ec, int nchan, int nfreq, int64_t n_out,
+                           int64_t npairs, int nph, int nam, int64_t t0, int64_t count, int64_t step, bool xcd,
+                           hipStream_t s);
 // event-related phase-amplitude coupling (nw_erpac.hip): src, the lists and the window as launch_pac, the
 // chunk's ec epochs ADDED in epoch order to m (npairs, nph, nam, count) complex fp64 += A u, amp (nchan, nam,
 // count, 2) fp64 += {A, |y|^2} and phase (nchan, nph, 5, count) fp64 += {c, s, c c, s s, c s} (null: not

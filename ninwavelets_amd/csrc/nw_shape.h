@@ -13,6 +13,8 @@
 //     map, block count, the sample count of a window and the lane of a sample (the order contract);
 //   - the phase-amplitude coupling kernel (nw_pac.hip): its scale tile, the tile counts and its
 //     block -> (epoch, pair, phase tile, amplitude tile) map;
+//   - the surrogate kernels of the coupling (nw_pac_surr.hip): the layout of the staged unit phasors and
+//     magnitudes, the staging launch's blocks, the circular shift and the lane of a cell;
 //   - the event-related coupling kernel (nw_erpac.hip): its sample-tile count, its block -> (pair,
 //     sample tile, phase tile, amplitude tile) map and its block count;
 //   - the phase-binned coupling kernel (nw_pac_bins.hip): the geometry chosen from nbins, its LDS
@@ -478,6 +480,46 @@ static_assert(pac_tiles_ph(8) == 1 && pac_tiles_ph(9) == 2 && pac_tiles_am(16) =
               "scale tile counts");
 static_assert(pac_blocks(2, 5, 4, false) == 40 && pac_blocks(2, 5, 4, true) == 64 && pac_blocks(0, 5, 4, true) == 0,
               "block count");
+
+// ---- time-lag surrogates of the phase-amplitude coupling (nw_pac_surr.hip) ---------------------
+
+// nw_pac_stage_kernel leaves, per chunk and in WINDOW order (index j = 0 .. T - 1: t0 and step drop out), the
+// unit phasors of every signal's listed phase scales as two planes and the magnitudes of its listed
+// amplitude scales, in fp64; a thread owns one (row, j), kPacSurrStageThreads consecutive j per block:
+//   [pac_surr_phase_at(sig, i, comp, nph, T) + j]        comp 0: re, 1: im       2 nsig nph T doubles, then
+//   [pac_surr_amp_at(nsig, sig, k, nph, nam, T) + j]                              nsig nam T doubles
+// nw_pac_surr_kernel: nw_pac_kernel's block map, tile and wave split on those values; for the lag l the
+// amplitude sample of the term j is pac_surr_wrap(j, l, T) (l in [0, T): one conditional subtract, no %),
+// and after each lag's fold lane pac_surr_cell_lane(k, q) of a wave keeps the cell (amplitude slot k of the
+// wave, phase slot q)'s statistics.
+constexpr int kPacSurrStageThreads = 256;
+constexpr int64_t pac_surr_stage_doubles(int64_t nsig, int64_t nph, int64_t nam, int64_t T) {
+    return nsig * (2 * nph + nam) * T;
+}
+constexpr int64_t pac_surr_phase_at(int64_t sig, int64_t i, int comp, int64_t nph, int64_t T) {
+    return ((sig * nph + i) * 2 + comp) * T;
+}
+constexpr int64_t pac_surr_amp_at(int64_t nsig, int64_t sig, int64_t k, int64_t nph, int64_t nam, int64_t T) {
+    return nsig * 2 * nph * T + (sig * nam + k) * T;
+}
+// the blocks of the staging launch: nrows = nsig (nph + nam) rows of T samples
+constexpr int64_t pac_surr_stage_tiles(int64_t T) { return (T + kPacSurrStageThreads - 1) / kPacSurrStageThreads; }
+constexpr int64_t pac_surr_stage_blocks(int64_t nrows, int64_t T) { return nrows * pac_surr_stage_tiles(T); }
+constexpr int64_t pac_surr_wrap(int64_t j, int64_t l, int64_t T) { return j + l >= T ? j + l - T : j + l; }
+constexpr int pac_surr_cell_lane(int k, int q) { return k * kPacPh + q; }
+static_assert(kPacAmWave * kPacPh <= 64, "a wave's cells: one lane each");
+static_assert(pac_surr_stage_doubles(6, 4, 5, 964) == 6 * 13 * 964 &&
+                  pac_surr_amp_at(6, 0, 0, 4, 5, 964) == pac_surr_phase_at(6, 0, 0, 4, 964) &&
+                  pac_surr_amp_at(6, 5, 4, 4, 5, 964) + 964 == pac_surr_stage_doubles(6, 4, 5, 964),
+              "the staged planes tile the scratch");
+static_assert(pac_surr_stage_tiles(0) == 0 && pac_surr_stage_tiles(256) == 1 && pac_surr_stage_tiles(257) == 2 &&
+                  pac_surr_stage_blocks(78, 964) == 312,
+              "staging blocks");
+static_assert(pac_surr_wrap(0, 0, 5) == 0 && pac_surr_wrap(4, 4, 5) == 3 && pac_surr_wrap(1, 4, 5) == 0 &&
+                  pac_surr_wrap(0, 4, 5) == 4 && pac_surr_wrap(0, 0, 1) == 0,
+              "the circular shift");
+static_assert(pac_surr_cell_lane(0, 0) == 0 && pac_surr_cell_lane(kPacAmWave - 1, kPacPh - 1) == kPacAmWave * kPacPh - 1,
+              "cell lanes");
 
 // ---- event-related phase-amplitude coupling (nw_erpac.hip) -------------------------------------
 

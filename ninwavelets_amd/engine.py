@@ -38,6 +38,9 @@ LAG_OUTS = {'lag_sum': 'lag_sum', 'pli': 'lag_sum', 'pli2_unbiased': 'lag_sum', 
             'wpli': 'lag_sum', 'wpli2_debiased': 'lag_sum', 'ciplv': 'plv_sum', 'ppc': 'plv_sum'}
 # phase-amplitude coupling (Plan.execute_pac): what finalize_pac forms from its sums (M, amp, phase)
 PAC_OUTS = {'pac_sum', 'mvl', 'mvl_norm', 'direct_pac', 'debiased_pac'}
+# time-lag surrogates (Plan.execute_pac_surr): what finalize_pac_surr forms from its sums for a measure of PAC_OUTS
+PAC_SURR_STATS = {'surr_sum', 'zscore', 'pvalue', 'surr_mean', 'surr_std', 'surr_max', 'surrogates'}
+PAC_SURR_CENTRES = {'plain': L.NW_PAC_SURR_PLAIN, 'debiased': L.NW_PAC_SURR_DEBIASED}
 # event-related coupling (Plan.execute_erpac): what finalize_erpac forms from its across-epoch sums (M, amp, phase)
 ERPAC_OUTS = {'erpac_sum', 'circular', 'circular_pval', 'mvl', 'mvl_norm', 'direct_pac', 'debiased_pac'}
 # phase-binned coupling (Plan.execute_pac_bins): what finalize_pac_bins forms from its sums (S, count)
@@ -303,6 +306,113 @@ def finalize_pac(kind: str, M, amp, phase, ip, ia, nsamples: int):
     den = np.broadcast_to(den, M.shape)
     zero = den == 0
     return np.where(zero, 0., np.abs(M) / np.where(zero, 1., den))
+
+
+def check_lags(lags, nsamples: int) -> np.ndarray:
+    """``lags`` of the surrogate calls, circular shifts in window samples, as a contiguous int64 array: a 1-D
+    list (it may be empty or repeat) of at most NW_PAC_MAX_LAGS integers in [0, T), T = ``nsamples``;
+    ValueError naming ``lags`` otherwise."""
+    try:
+        arr = np.asarray(lags)
+    except (TypeError, ValueError):
+        raise ValueError(f'lags must be a list of integer shifts, got {lags!r}') from None
+    if arr.ndim != 1 or arr.dtype == object:
+        raise ValueError(f'lags must be a 1-D list of integer shifts, got shape {arr.shape}')
+    if arr.size and not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f'lags must hold integers, got {arr.dtype}')
+    if arr.size > L.NW_PAC_MAX_LAGS:
+        raise ValueError(f'lags holds {arr.size} shifts, more than NW_PAC_MAX_LAGS = {L.NW_PAC_MAX_LAGS}')
+    if arr.size and (arr.min() < 0 or arr.max() >= nsamples):
+        raise ValueError(f'lags must lie in [0, {int(nsamples)}), the window\'s samples: got {int(arr.min())} .. '
+                         f'{int(arr.max())}')
+    return np.ascontiguousarray(arr, dtype=np.int64)
+
+
+def draw_lags(nsamples: int, n_surrogates: int = 200, min_lag=None, seed=None) -> np.ndarray:
+    """The default lags of the surrogate calls: default_rng(seed).integers(min_lag, T - min_lag + 1,
+    n_surrogates) with T = ``nsamples``, so that every cut leaves both blocks at least ``min_lag`` samples long
+    (None: max(1, T // 10)); int64.  ValueError unless 1 <= n_surrogates <= NW_PAC_MAX_LAGS, min_lag >= 1 and
+    T >= 2 min_lag."""
+    import operator
+    T = int(nsamples)
+    try:
+        S = operator.index(n_surrogates)
+        lo = max(1, T // 10) if min_lag is None else operator.index(min_lag)
+    except TypeError:
+        raise ValueError(f'n_surrogates and min_lag must be integers, got {n_surrogates!r} and {min_lag!r}') from None
+    if not 1 <= S <= L.NW_PAC_MAX_LAGS:
+        raise ValueError(f'n_surrogates must lie in [1, {L.NW_PAC_MAX_LAGS}], got {S}')
+    if lo < 1:
+        raise ValueError(f'min_lag must be >= 1, got {lo}')
+    if T < 2 * lo:
+        raise ValueError(f'a window of {T} samples has no lag with both blocks at least min_lag = {lo} long')
+    return np.random.default_rng(seed).integers(lo, T - lo + 1, S).astype(np.int64)
+
+
+def finalize_pac_surr(kind: str, stat_kind: str, M, amp, phase, stat, all, ip, ia, nsamples: int, nlags: int):
+    """The surrogate statistic ``stat_kind`` of the coupling measure ``kind`` (mvl, mvl_norm, direct_pac,
+    debiased_pac: finalize_pac's) per epoch, pair and (phase scale, amplitude scale) from the sums of
+    Plan.execute_pac_surr over T = ``nsamples`` window samples and S = ``nlags`` lags: ``M``, ``amp``, ``phase`` as
+    in finalize_pac, ``stat`` float64 (E, P, Fp, Fa, 4) = {sum_s h_s, sum_s q_s, #{s : q_s >= q_0}, max_s q_s} and
+    ``all`` complex128 (E, P, Fp, Fa, S) = the surrogate sums M_s (``surrogates`` only; None otherwise), h = |Mc|,
+    q = |Mc|^2, Mc = M for the first three kinds and M - (sum u)(sum A) / T for debiased_pac -- the sums must
+    come from a call with that centring.  The measure is h times ``norm`` = 1 / (finalize_pac's denominator of
+    ``kind``), 0 where that is 0; a circular shift does not change it, so with h_0 = |Mc_0|, mean = sum h / S and
+    sd = sqrt(max(0, sum q / S - mean^2)) (the population sd):
+      zscore      (h_0 - mean) / sd, 0 where sd = 0       pvalue      (1 + count) / (1 + S)
+      surr_mean   mean norm                               surr_std    sd norm
+      surr_max    sqrt(max q) norm                        surrogates  |Mc_s| norm, (E, P, Fp, Fa, S)
+    float64 (E, P, Fp, Fa).  ``surr_sum`` returns (M, amp, phase, stat, all) unchanged.  The finalised kinds need
+    T >= 1 and S >= 1, zscore and surr_std S >= 2 (ValueError)."""
+    if kind not in PAC_OUTS or (kind == 'pac_sum' and stat_kind != 'surr_sum'):
+        raise ValueError(f"out must be one of {', '.join(sorted(PAC_OUTS - {'pac_sum'}))}; got {kind!r}")
+    if stat_kind not in PAC_SURR_STATS:
+        raise ValueError(f"stat must be one of {', '.join(sorted(PAC_SURR_STATS))}; got {stat_kind!r}")
+    if stat_kind == 'surr_sum':
+        return M, amp, phase, stat, all
+    T, S = int(nsamples), int(nlags)
+    if T < 1:
+        raise ValueError(f'{stat_kind} needs at least 1 sample in the window, got {T}')
+    need = 2 if stat_kind in ('zscore', 'surr_std') else 1
+    if S < need:
+        raise ValueError(f'{stat_kind} needs at least {need} surrogate{"s" if need > 1 else ""}, got {S}')
+    M = np.asarray(M, dtype=np.complex128)
+    if M.ndim != 4:
+        raise ValueError(f'M must be (epochs, pairs, phase scales, amplitude scales), got shape {M.shape}')
+    ip, ia = np.asarray(ip, dtype=np.intp), np.asarray(ia, dtype=np.intp)
+    amp = np.asarray(amp, dtype=np.float64)
+    sA = amp[:, ia][:, :, None, :, 0]
+    if kind in ('mvl', 'debiased_pac'):
+        den = np.full(M.shape, float(T))
+    else:
+        den = np.broadcast_to(sA if kind == 'mvl_norm' else np.sqrt(T * amp[:, ia][:, :, None, :, 1]), M.shape)
+    zero = den == 0
+    norm = np.where(zero, 0., 1. / np.where(zero, 1., den))
+    D = 0.
+    if kind == 'debiased_pac':                    # the device's D: each operation rounded on its own
+        P = np.asarray(phase, dtype=np.complex128)[:, ip][:, :, :, None]
+        D = (P.real * sA) / T + 1j * ((P.imag * sA) / T)
+    if stat_kind == 'surrogates':
+        if all is None:
+            raise ValueError('surrogates needs the surrogate sums: execute_pac_surr(..., keep_all=True)')
+        return np.abs(np.asarray(all, dtype=np.complex128) - np.asarray(D)[..., None]) * norm[..., None]
+    stat = np.asarray(stat, dtype=np.float64)
+    if stat.shape != M.shape + (4,):
+        raise ValueError(f'stat must be {M.shape + (4,)}, got {stat.shape}')
+    if stat_kind == 'pvalue':
+        return (1. + stat[..., 2]) / (1. + S)
+    if stat_kind == 'surr_max':
+        return np.sqrt(stat[..., 3]) * norm
+    mean = stat[..., 0] / S
+    if stat_kind == 'surr_mean':
+        return mean * norm
+    sd = np.sqrt(np.maximum(0., stat[..., 1] / S - mean * mean))
+    if stat_kind == 'surr_std':
+        return sd * norm
+    Mc = M - D
+    h0 = np.sqrt(Mc.real * Mc.real + Mc.imag * Mc.imag)
+    flat = sd == 0
+    return np.where(flat, 0., (h0 - mean) / np.where(flat, 1., sd))
 
 
 check_nbins = L.check_nbins     # nbins of the phase-binned calls, checked before any device work
@@ -943,6 +1053,42 @@ class Plan:
                                        ('phase', (nep, nchan, nph), np.complex128, True)])
         self._epoch_execute(L.lib().nw_execute_pac, x,
                             (nep, nchan, _ptr(ip), _ptr(ia), npairs, _ptr(fph), nph, _ptr(fam), nam, t0, t1, step), outs)
+        return out if dev else tuple(outs)
+
+    def execute_pac_surr(self, x, lags, indices=None, phase=None, amp=None, window=None, step: int = 1,
+                         centre: str = 'plain', keep_all: bool = False, out=None):
+        """Time-lag surrogate sums of the coupling (nw_execute_pac_surr): x, ``indices``, ``phase``, ``amp``,
+        ``window`` and ``step`` as in execute_pac; ``lags``: circular shifts of the amplitude inside the window,
+        integers in [0, T) (check_lags; any list, at most NW_PAC_MAX_LAGS); ``centre``: 'plain' (mvl, mvl_norm,
+        direct_pac) or 'debiased' (debiased_pac: M - (sum u)(sum A) / T).  Returns (M, amp, phase) as execute_pac,
+        bit for bit, then stat float64 (E, P, Fp, Fa, 4) = {sum_s |Mc_s|, sum_s |Mc_s|^2, #{s : |Mc_s|^2 >=
+        |Mc_0|^2}, max_s |Mc_s|^2} and, with ``keep_all``, all complex128 (E, P, Fp, Fa, S) = M_{lags[s]}; see
+        finalize_pac_surr.  numpy arrays: synchronous, ``out`` optional.  Device tensors: asynchronous on the
+        plan stream, ``out`` = (M, amp, phase, stat[, all]) required (amp and phase may be None: not returned).
+        The plan needs max_batch >= C; one chunk's listed rows are staged in fp64 on the device
+        ((max_batch // C) C (2 Fp + Fa) T values)."""
+        nep, nchan = _epochs(x)
+        ip, ia = check_pac_indices(indices, nchan)
+        npairs = int(ip.size)
+        fph, fam = check_scales('phase', phase, self.nfreq), check_scales('amp', amp, self.nfreq)
+        nph, nam = int(fph.size), int(fam.size)
+        t0, t1, step = self._window(window, step)
+        lags = check_lags(lags, len(range(t0, t1, step)))
+        nlags = int(lags.size)
+        if centre not in PAC_SURR_CENTRES:
+            raise ValueError(f"centre must be one of {', '.join(PAC_SURR_CENTRES)}; got {centre!r}")
+        x = self._epoch_input(x, nep * nchan, out)
+        dev = _is_device_tensor(x)
+        nout = 5 if keep_all else 4
+        outs = _unpack(out, nout, 'device output must be (M, amp, phase, stat[, all]) tensors (amp and phase may be None)'
+                       if dev else 'out must be (M, amp, phase, stat[, all]) arrays')
+        specs = [('M', (nep, npairs, nph, nam), np.complex128, False), ('amp', (nep, nchan, nam, 2), np.float64, True),
+                 ('phase', (nep, nchan, nph), np.complex128, True), ('stat', (nep, npairs, nph, nam, 4), np.float64, False),
+                 ('all', (nep, npairs, nph, nam, nlags), np.complex128, False)][:nout]
+        outs = self._outputs(x, outs, specs)
+        self._epoch_execute(L.lib().nw_execute_pac_surr, x,
+                            (nep, nchan, _ptr(ip), _ptr(ia), npairs, _ptr(fph), nph, _ptr(fam), nam, t0, t1, step,
+                             _ptr(lags), nlags, PAC_SURR_CENTRES[centre]), outs + [None] * (5 - nout))
         return out if dev else tuple(outs)
 
     def execute_erpac(self, x, indices=None, phase=None, amp=None, window=None, step: int = 1, out=None):

@@ -153,6 +153,23 @@ class EpochsWavelet:
                                       amp=np.arange(len(pf), len(pf) + len(af)), out=method, indices=indices,
                                       window=window, decim=decim, average=average)
 
+    def pac_surrogates(self, ch_names, phase_freqs, amp_freqs, method: str = 'direct_pac', stat: str = 'zscore',
+                       n_surrogates: int = 200, lags=None, min_lag=None, seed=None, indices=None, padding: float = 0.,
+                       decim: int = 1, average: bool = False):
+        """``stat`` (pac_surrogates_batch's: zscore, pvalue, surr_mean, surr_std, surr_max, surrogates, surr_sum)
+        of the coupling ``method`` (mvl, mvl_norm, direct_pac, debiased_pac) against time-lag surrogates, the
+        amplitude shifted circularly inside the kept samples: (E, P, Fp, Fa), and (E, P, Fp, Fa, S) for
+        ``surrogates``.  ``n_surrogates``, ``lags`` (in the kept, decimated samples), ``min_lag`` and ``seed`` as in
+        pac_surrogates_batch; frequency lists, ``indices``, ``padding``, ``decim`` and ``average`` as in pac
+        (``average=True``: zscore, surr_mean and surr_std only)."""
+        waves = self._pick(ch_names)
+        window = self._padded(waves.shape[-1], padding)
+        pf, af = list(phase_freqs), list(amp_freqs)
+        return self.wavelet.pac_surrogates_batch(waves, pf + af, reuse=False, phase=np.arange(len(pf)),
+                                                 amp=np.arange(len(pf), len(pf) + len(af)), out=method, stat=stat,
+                                                 n_surrogates=n_surrogates, lags=lags, min_lag=min_lag, seed=seed,
+                                                 indices=indices, window=window, decim=decim, average=average)
+
     # -- event-related phase-amplitude coupling: across the epochs, one time course per pair and cell
     #    (WaveletBase.erpac_batch) ---------------------------------------------------------------
     def erpac(self, ch_names, phase_freqs, amp_freqs, method: str = 'circular', indices=None, padding: float = 0.,
